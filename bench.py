@@ -8,9 +8,21 @@ every rank's interleaved 8-row bands gathered to rank 0 over RCCL by the library
 is read back to the host inside the timed region.  The process never imports torch: the only
 HIP runtime in it is the one librt_hip.so links (/opt/rocm).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...; the
   launcher only starts the processes -- ranks meet through the library's RCCL communicator)
+
+A plain run does what the headline needs and no more: set-up, the count pass, warm-up, the K
+timed steps and the result line (headline + its roofline, priced from the timed steps' own
+events).  --full adds, at N = 1, the measurements that take runs of their own: the drop-in
+per-frame loop (`drop_in`), the other BASELINE configs (`configs`) and the CPU baseline
+(`cpu_baseline`); --no-drop-in / --no-configs / --no-cpu-baseline drop single ones from it.
+
+--dump-outputs DIR: after the timed steps, rank 0 reads back the image the last timed step left
+(the output buffer a caller would read; the gathered image for N > 1) and writes
+DIR/radiance.npy: float32 (n, 3), the RGB radiance of a fixed sample of pixels (all of them up
+to DUMP_MAX_PIXELS, else a seeded choice in ascending pixel order).  Seeds and scene are fixed,
+so two runs with the same arguments see identical inputs.
 
 Rays are counted as the reference's Intersect() calls over all bounces and frames
 (SURVEY.md 8(d)); the count comes from an instrumented pass before the timed region and is
@@ -32,7 +44,7 @@ Roofline of the dominant kernel (KernelEntry's render launch), per launch:
     those bytes are LDS reads, not HBM traffic.
 cpu_baseline: the reference kernel itself (kernel_bvh.cl compiled unmodified for x86-64,
 oracle/_ref/libref_cpu.so) over all 8 frames of the same render on the host cores, rank 0,
-N = 1 only.
+N = 1 with --full only.
 """
 import argparse
 import glob
@@ -58,6 +70,8 @@ SIMDS = 256 * 4                    # MI355X: 256 CUs x 4 SIMD-32
 VALU_PEAK = SIMDS * 2.4e9 / 2.0    # wave64 VALU instructions per second (2 cycles each)
 CAMERA = ((0.0, -25.0, 8.5), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
 PMC_PATH = os.path.join(REPO, "profiles", "pmc.json")
+DUMP_MAX_PIXELS = 4 << 20          # --dump-outputs: 4 Mi pixels x 3 x f32 = 48 MiB
+DUMP_SEED = 20240611
 
 
 def parse(argv=None):
@@ -89,12 +103,18 @@ def parse(argv=None):
                    help="rtKernelSetTuning parameter (clrt._native.TUNING names); results unchanged")
     p.add_argument("--no-accum-overlap", action="store_true",
                    help="fused frames: accumulate on the main stream (rtContextSetAccumOverlap 0)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="N = 1: after the headline also run the drop-in per-frame loop (`drop_in`), the other "
+                        "BASELINE configs (`configs`) and the CPU baseline (`cpu_baseline`)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last step's image (a fixed pixel sample, RGB f32) "
+                        "to DIR/radiance.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without `cpu_baseline`")
     p.add_argument("--no-drop-in", action="store_true",
-                   help="skip the extra per-frame (drop-in RenderFrame loop) measurement reported beside "
-                        "the fused headline at N = 1")
+                   help="--full without the extra per-frame (drop-in RenderFrame loop) measurement reported "
+                        "beside the fused headline")
     p.add_argument("--no-configs", action="store_true",
-                   help="skip the other BASELINE configs timed after the headline at N = 1 (the `configs` key)")
+                   help="--full without the other BASELINE configs timed after the headline (the `configs` key)")
     p.add_argument("--cpu-threads", type=int, default=16)
     p.add_argument("--gather-sync", action="store_true",
                    help="N>1: wait for each step's gather before queueing the next step (no pipelining)")
@@ -417,6 +437,18 @@ def roofline(args, world, frames_per_launch, kernel_ms, period_ms, local_counts,
     return rl
 
 
+def dump_outputs(ctx, buf, pixels, path):
+    """--dump-outputs: the image in `buf` (pixels x float4; .w is always written 0) -> path/radiance.npy,
+    RGB of every pixel, or of DUMP_MAX_PIXELS of them chosen once from DUMP_SEED."""
+    host = np.empty((pixels, 4), np.float32)
+    ctx.ReadBuffer(buf, host, blocking=True)
+    if pixels > DUMP_MAX_PIXELS:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels, DUMP_MAX_PIXELS, replace=False))
+        host = host[pick]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "radiance.npy"), np.ascontiguousarray(host[:, :3]))
+
+
 def comm_report(comm, ks, args):
     """What the N > 1 flow actually ran, rank by rank, gathered to every rank (collective): the
     communicator's world size, each rank's effective transport (a world whose copy-engine links
@@ -520,6 +552,8 @@ def main():
     if comm is not None:
         elapsed = float(mg.Comm.allreduce([comm], [elapsed], N.COMM_MAX)[0][0])
         comm_line = comm_report(comm, ks, args)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r.ctx, img if comm is not None else r.out, r.W * r.H, args.dump_outputs)
 
     check = None
     if args.check_gather and comm is not None and rank == 0:
@@ -596,11 +630,11 @@ def main():
         line["comm"] = comm_line
     if check:
         line["check_gather"] = check
-    if world == 1 and comm is None and args.launch == "fused" and not args.no_drop_in:
+    if args.full and world == 1 and comm is None and args.launch == "fused" and not args.no_drop_in:
         line["drop_in"] = drop_in(r, args, rays_per_step, steps=args.steps)
-    if world == 1 and comm is None and not args.no_configs:
+    if args.full and world == 1 and comm is None and not args.no_configs:
         line["configs"] = extra_configs(local)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(scene, args, pinned_rays(r, args))
     print(json.dumps(line))
     if comm is not None:

@@ -27,7 +27,7 @@ for step in "$@"; do
   case $step in
     tests) run pytest_gpu 900 python -u -m pytest tests -m gpu --maxfail 8 -v --timeout 120 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     prof) run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-configs ;;
     dist1) run dist1_rccl 300 python bench.py --force-dist --check-gather --steps 5 --warmup 1 --no-cpu-baseline && \
            run dist1_rccl_sync 300 python bench.py --force-dist --gather-sync --steps 5 --warmup 1 --no-cpu-baseline ;;
@@ -49,7 +49,7 @@ for step in "$@"; do
                  run pmc_1080p 900 bash scripts/profile.sh 1080p --width 1920 --height 1080 --bounces 2 --frames 1 && \
                  run pmc_pinned 900 bash scripts/profile.sh pinned --math pinned && \
                  cp gpurun_out/pmc_pinned/pmc.json profiles/pmc.json && \
-                 run bench_default 600 python bench.py && \
+                 run bench_default 600 python bench.py --full && \
                  run bench_trace 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/final_trace -o run -- python bench.py --steps 20 --warmup 1 --no-cpu-baseline --no-drop-in --no-configs ;;
     #   final_configs: the other configs (no CPU baseline / drop-in) and the emulated ranks
     final_configs) for c in "bunny --scene bunny" "perframe --launch per-frame --steps 5" "pinned --math pinned --steps 5" \
@@ -62,7 +62,7 @@ for step in "$@"; do
                    for sc in cornell bunny; do
                      RT_EMU_SCENE=$sc run rank_emulation_$sc 600 python scripts/rank_emulation.py
                    done ;;
-    configs) run cfg3_default 600 python bench.py && \
+    configs) run cfg3_default 600 python bench.py --full && \
              run cfg3_pinned 300 python bench.py --math pinned --no-cpu-baseline && \
              run cfg2_1080p 300 python bench.py --width 1920 --height 1080 --bounces 2 --frames 1 --steps 20 --no-cpu-baseline && \
              run cfg1_512 300 python bench.py --width 512 --height 512 --bounces 1 --frames 1 --steps 50 --no-cpu-baseline && \

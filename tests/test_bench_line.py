@@ -15,7 +15,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_default_bench_line_carries_every_config():
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-drop-in"], capture_output=True, text=True, timeout=240, cwd=REPO)
+                        "--full", "--no-cpu-baseline", "--no-drop-in"], capture_output=True, text=True, timeout=240, cwd=REPO)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0
@@ -32,6 +32,74 @@ def test_default_bench_line_carries_every_config():
     # flip a hit (SURVEY.md 7 hard part 1), by far less than a percent
     rel = abs(cfg["cfg3_pinned"]["rays_per_step"] - line["config"]["rays_per_step"]) / line["config"]["rays_per_step"]
     assert rel < 1e-3
+
+
+SMALL = ["--width", "640", "--height", "360"]
+
+
+def _bench(*extra):
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        *extra], capture_output=True, text=True, timeout=120, cwd=REPO)
+    assert p.returncode == 0, p.stderr[-2000:]
+    return json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_the_timed_path_computed(tmp_path, cornell):
+    """A plain run carries the headline and its roofline only (what takes runs of its own waits for
+    --full); --dump-outputs writes the image the last timed step left, the same bits in every run
+    and the same bits a caller of that path reads back."""
+    import numpy as np
+
+    import bench
+    line = _bench(*SMALL, "--dump-outputs", str(tmp_path / "a"))
+    assert not {"drop_in", "configs", "cpu_baseline"} & set(line)
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["value"] > 0 and line["unit"] == "Mrays/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["metric"].startswith("Mrays/s (640x360 Cornell box")
+    assert line["ms_per_step"] > 0 and line["roofline"]["launch_ms"] > 0
+    # value = rays per step / time per step; ms_per_step is printed to 1e-4 ms and a step here takes > 0.02 ms
+    assert line["value"] == pytest.approx(line["config"]["rays_per_step"] / line["ms_per_step"] / 1e3, rel=5e-3)
+    _bench(*SMALL, "--dump-outputs", str(tmp_path / "b"))
+    assert os.listdir(tmp_path / "a") == ["radiance.npy"]
+    a = np.load(tmp_path / "a" / "radiance.npy")
+    b = np.load(tmp_path / "b" / "radiance.npy")
+    assert a.dtype == np.float32 and a.shape == (640 * 360, 3)
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    args = bench.parse(SMALL)
+    r = bench.Rank(cornell, args, 0)
+    r.render()
+    want = np.empty((640 * 360, 4), np.float32)
+    r.ctx.ReadBuffer(r.out, want, blocking=True)
+    r.release()
+    assert np.isfinite(want).all() and (want[:, :3] > 0).any()
+    assert np.array_equal(a.view(np.uint32), np.ascontiguousarray(want[:, :3]).view(np.uint32))
+
+
+def test_dump_outputs_samples_a_large_image(tmp_path, monkeypatch):
+    """CPU: an image over the dump's size limit is written as a fixed, seeded choice of its pixels
+    in ascending order -- the same pixels every time."""
+    import numpy as np
+
+    import bench
+    n = 5000
+    img = np.arange(n * 4, dtype=np.float32).reshape(n, 4)
+
+    class Ctx:
+        def ReadBuffer(self, buf, host, blocking=True):
+            host[:] = buf
+
+    monkeypatch.setattr(bench, "DUMP_MAX_PIXELS", 1000)
+    bench.dump_outputs(Ctx(), img, n, str(tmp_path / "a"))
+    bench.dump_outputs(Ctx(), img, n, str(tmp_path / "b"))
+    a = np.load(tmp_path / "a" / "radiance.npy")
+    assert a.dtype == np.float32 and a.shape == (1000, 3)
+    assert np.array_equal(a, np.load(tmp_path / "b" / "radiance.npy"))
+    px = (a[:, 0] / 4).astype(np.int64)
+    assert np.all(np.diff(px) > 0) and np.array_equal(a, img[px, :3])
+    monkeypatch.setattr(bench, "DUMP_MAX_PIXELS", n)
+    bench.dump_outputs(Ctx(), img, n, str(tmp_path / "c"))
+    assert np.array_equal(np.load(tmp_path / "c" / "radiance.npy"), img[:, :3])
 
 
 def test_every_bench_config_has_a_pmc_record():
