@@ -12,6 +12,8 @@
 // launch that uses them (child indices strictly increasing, leaf ranges inside the
 // triangle array, material indices in range, depth <= 64), so a malformed scene is an
 // error code, never an out-of-bounds or non-terminating GPU walk.
+// That validation and the record packing live in rt_scene_pack.cpp, and how a launch hands its
+// work out in rt_launch_plan.cpp (both pure host code); this file keeps resources, streams, launches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,34 +29,16 @@
 #include "rt_bvh.hpp"
 #include "rt_internal.hpp"
 #include "rt_kernels.hpp"
+#include "rt_launch_plan.hpp"
+#include "rt_scene_pack.hpp"
 
 namespace {
 
 constexpr uint64_t kKnownFlags =
     RT_MEM_READ_WRITE | RT_MEM_WRITE_ONLY | RT_MEM_READ_ONLY | RT_MEM_COPY_HOST_PTR;
 constexpr int kStatWords = 20;                // rt_stats counters kept on the device
-constexpr size_t kLdsBudget = 64 * 1024;       // per-workgroup LDS the scene path may use
 #ifndef RT_TIMELINE
 #define RT_TIMELINE 0
-#endif
-#ifndef RT_STATIC_FIRST
-#define RT_STATIC_FIRST 1
-#endif
-// per-frame launches without a bulk region: tail counters on this many partitions (a power of two, <=
-// rtk::kMaxParts; step_body next_chunk_parts) -- 1080p 2-bounce frames 0.172 -> 0.165 ms with 128-pixel
-// tail chunks, which on one counter took 0.231 (profiles/r06/work_handout_ab.txt)
-#ifndef RT_COUNTER_PARTS
-#define RT_COUNTER_PARTS 8
-#endif
-#ifndef RT_PF_COUNTER_SLOTS
-#define RT_PF_COUNTER_SLOTS 1
-#endif
-// tail chunks: sized so that every `RT_TAIL_SHARE_WAVES` waves get >= 2.5 of them (1: every wave; 4:
-// every workgroup, whose waves split the last one by work stealing): fewer atomics on the tail
-// counter for small launches (1080p 2-bounce frames 0.282 -> 0.218 ms alone; 4K launches already
-// take the largest chunk, profiles/r06/work_handout_ab.txt)
-#ifndef RT_TAIL_SHARE_WAVES
-#define RT_TAIL_SHARE_WAVES 4
 #endif
 // diagnostic timeline builds (-DRT_TIMELINE=1, scripts/timeline.py) write three 64-bin histograms after
 // the primary hit ids: such a build requires hit buffers that long
@@ -64,6 +48,13 @@ constexpr size_t kHitPad = RT_TIMELINE ? 192 : 0;
 
 using rti::map_hip;
 using rti::qs;
+using rtp::build_global_nodes;
+using rtp::build_oct_nodes;
+using rtp::build_oct_nodes_grouped;
+using rtp::build_skips;
+using rtp::check_nodes;
+using rtp::kLeafMin;
+using rtp::oct_records;
 
 struct rt_kernel_s {
     rt_context ctx = nullptr;
@@ -152,7 +143,7 @@ struct rt_kernel_s {
     float4* g_nodes = nullptr;         // global-scene node records (64 B, top of the tree first)
     size_t g_nodes_cap = 0;
     uint32_t n_top = 0, top_limit = 384;  // nodes of g_nodes staged in LDS (global path; swept, profiles/r01/bunny_top_nodes_sweep_2.txt)
-    size_t packed_tris_cap = 0, oct_nodes_cap = 0;
+    size_t packed_tris_cap = 0, oct_nodes_cap = 0;  // float4s
     uint32_t n_nodes = 0, n_tris = 0, n_mats = 0;
     int depth = 0;
     bool last_lds = false;
@@ -210,188 +201,6 @@ int host_bytes(rt_mem m, std::vector<uint8_t>& tmp, const uint8_t** out) {
     return RT_SUCCESS;
 }
 
-// Validate the flattened BVH (CLBVHnode.cpp:161-183 contract) and return its depth and its
-// node count.  The tree is the prefix [0, end) of the array: in the depth-first layout (first
-// child = parent + 1, second child after the first child's subtree) the root's subtree ends
-// after the leaf its chain of second children reaches.  Nodes past `end` are never read -- by
-// the reference's walk from node 0 either -- so a buffer may be larger than the tree it holds
-// (rtBuildBVH writes `count` nodes into a buffer of 2n-1).  Within the tree every node is
-// checked and each one but the root must have exactly one parent; since a parent's index is
-// smaller than its children's, that makes every node reachable from node 0 and the
-// skip-pointer walk a finite depth-first order (a child shared by two parents would make it
-// loop).
-int check_nodes(const rt_cl_bvh_node* nd, uint32_t n, uint32_t n_tris, int* depth_out, uint32_t* n_used) {
-    if (n == 0) return RT_INVALID_MEM_OBJECT;
-    uint32_t last = 0;  // the root's chain of second children (offsets strictly increase)
-    while (nd[last].nPrimitives == 0) {
-        if (nd[last].offset <= last || nd[last].offset >= n) return RT_INVALID_MEM_OBJECT;
-        last = nd[last].offset;
-    }
-    n = last + 1;
-    std::vector<int> depth(n, -1);
-    std::vector<uint8_t> parents(n, 0);
-    depth[0] = 0;
-    int max_depth = 0;
-    // children have larger indices than their parent, so one forward sweep sets depths
-    for (uint32_t i = 0; i < n; ++i) {
-        const rt_cl_bvh_node& x = nd[i];
-        if (i > 0 && parents[i] != 1) return RT_INVALID_MEM_OBJECT;  // orphan: unreachable
-        if (x.nPrimitives > 0) {
-            if ((uint64_t)x.offset + x.nPrimitives > n_tris) return RT_INVALID_MEM_OBJECT;
-            max_depth = std::max(max_depth, depth[i]);
-        } else {
-            if (x.axis > 2) return RT_INVALID_MEM_OBJECT;
-            const uint64_t a = (uint64_t)i + 1, b = x.offset;
-            if (a >= n || b >= n || b <= a) return RT_INVALID_MEM_OBJECT;
-            if (parents[a]++ != 0 || parents[b]++ != 0) return RT_INVALID_MEM_OBJECT;  // shared child
-            depth[a] = depth[i] + 1;
-            depth[b] = depth[i] + 1;
-        }
-    }
-    *depth_out = max_depth;
-    *n_used = n;
-    // The reference's 64-entry stack (kernel_bvh.cl:181) would overflow past depth 64; the
-    // stackless walk here has no such limit, so deeper trees are rendered, not rejected.
-    return RT_SUCCESS;
-}
-
-// Per-octant skip pointers (see rt_kernels.hip, intersect): for octant o (bit i = the ray
-// direction's sign on axis i) the reference visits an interior node's second child first
-// when bit axis(n) is set (kernel_bvh.cl:200-207).  skip[n][o] is the node the reference
-// pops after finishing n's subtree: near child -> far child, far child -> skip of parent.
-// Children have larger indices than their parent, so one forward sweep fills the table.
-void build_skips(const rt_cl_bvh_node* nd, uint32_t n, std::vector<uint32_t>& skips) {
-    skips.assign((size_t)n * 8, 0xffffffffu);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (nd[i].nPrimitives > 0) continue;
-        const uint32_t first = i + 1, second = nd[i].offset;
-        for (uint32_t o = 0; o < 8; ++o) {
-            const bool swap = (o >> nd[i].axis) & 1u;
-            const uint32_t nearc = swap ? second : first, farc = swap ? first : second;
-            skips[(size_t)nearc * 8 + o] = farc;
-            skips[(size_t)farc * 8 + o] = skips[(size_t)i * 8 + o];
-        }
-    }
-}
-
-// Octant-resolved node records for LDS-resident scenes (stored as 16 planes of float4:
-// A[octant][node], then B[octant][node], each plane n + 1 records): for node i and ray
-// octant o,
-//   A = {near.x, near.y, near.z, far.x}, B = {far.y, far.z, hit_next, miss_next}
-// where near/far are the slab planes kernel_bvh.cl:156-169 selects by the ray's signs
-// (bit-exact copies of pmin/pmax), miss_next = skip[i][o] and hit_next is the near child
-// (interior, < 2^24) or the leaf code count << 24 | first (count 1..127).  The reference's
-// "stack empty" is record n, a sentinel every ray misses (its near planes are +inf along the
-// octant's direction, so t0 = +inf) whose successors are n itself: a finished walk parks
-// there, and the kernel needs no end test per step.  A node step is two b128 reads, the slab
-// arithmetic and two selects.  Returns false when a leaf does not fit (> 127 primitives or
-// first + count > 2^24): such a scene is rendered from the global layout instead (LDS scenes
-// are small, so this takes an unusual hand-made BVH).
-constexpr uint32_t kLeafMin = 1u << 24;
-
-// records per octant plane: the n nodes, the END sentinel, and one pad record when that count is
-// even -- an odd plane stride (x 16 B) staggers the eight planes over the LDS banks, so lanes of
-// different octants at the same node do not collide (an even stride of 40 put planes o and o+2
-// on the same banks: +40 % bank-conflict cycles)
-inline uint32_t oct_stride(uint32_t n) { return (n + 1) | 1u; }
-// float4 offset of the B planes: rtk::kOctB for trees of at most kOctBMaxStride records per plane
-// (a node step then reads B at an immediate offset from A), else right after the A planes
-inline uint32_t oct_b(uint32_t n) {
-    return oct_stride(n) <= rtk::kOctBMaxStride ? rtk::kOctB : 8u * oct_stride(n);
-}
-inline uint32_t oct_records(uint32_t n) { return oct_b(n) + 8u * oct_stride(n); }
-
-bool build_oct_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
-                     std::vector<uint32_t>& out) {
-    const uint32_t stride = oct_stride(n), bofs = oct_b(n);
-    out.assign((size_t)oct_records(n) * 4, 0u);
-    bool ok = n < kLeafMin;
-    auto bits = [](float f) {
-        uint32_t u;
-        std::memcpy(&u, &f, 4);
-        return u;
-    };
-    const float inf = std::numeric_limits<float>::infinity();
-    for (uint32_t i = 0; i <= n; ++i) {
-        uint32_t leaf = 0;
-        float lo[3], hi[3];
-        if (i < n) {
-            const rt_cl_bvh_node& x = nd[i];
-            if (x.nPrimitives > 0) {
-                if (x.nPrimitives <= 127 && (uint64_t)x.offset + x.nPrimitives <= kLeafMin)
-                    leaf = ((uint32_t)x.nPrimitives << 24) | x.offset;
-                else
-                    ok = false;
-            }
-            lo[0] = x.bounds.pmin.x, lo[1] = x.bounds.pmin.y, lo[2] = x.bounds.pmin.z;
-            hi[0] = x.bounds.pmax.x, hi[1] = x.bounds.pmax.y, hi[2] = x.bounds.pmax.z;
-        } else {
-            // END sentinel: near plane +inf (octant bit clear: near = pmin) or -inf (set: near =
-            // pmax), i.e. lo = +inf, hi = -inf -- (near - o) * invDir = +inf on every axis
-            for (int ax = 0; ax < 3; ++ax) lo[ax] = inf, hi[ax] = -inf;
-        }
-        for (uint32_t o = 0; o < 8; ++o) {
-            // octant-major planes A[o][node], B[o][node] (16 B each): lanes visiting different
-            // nodes in the same octant hit different LDS banks
-            uint32_t* ra = &out[((size_t)o * stride + i) * 4];
-            uint32_t* rb = &out[((size_t)bofs + (size_t)o * stride + i) * 4];
-            float nr[3], fr[3];
-            for (int ax = 0; ax < 3; ++ax) {
-                const bool neg = (o >> ax) & 1u;
-                nr[ax] = neg ? hi[ax] : lo[ax];
-                fr[ax] = neg ? lo[ax] : hi[ax];
-            }
-            ra[0] = bits(nr[0]);
-            ra[1] = bits(nr[1]);
-            ra[2] = bits(nr[2]);
-            ra[3] = bits(fr[0]);
-            rb[0] = bits(fr[1]);
-            rb[1] = bits(fr[2]);
-            if (i == n) {
-                rb[2] = rb[3] = n;
-                continue;
-            }
-            const uint32_t skip = skips[(size_t)i * 8 + o];
-            rb[2] = nd[i].nPrimitives > 0 ? leaf : (((o >> nd[i].axis) & 1u) ? nd[i].offset : i + 1);
-            rb[3] = skip == 0xffffffffu ? n : skip;
-        }
-    }
-    return ok;
-}
-
-#ifndef RT_GOCT_GROUP
-#define RT_GOCT_GROUP 1  // node-major: bunny proxy fused 1.405 -> 1.393 ms/frame (profiles/r03/goct_layout_ab.txt)
-#endif
-// The same octant records regrouped for the walk over HBM/L2 (RT_GOCT_GROUP = G > 0): blocks of G
-// consecutive nodes, each block laid out octant-major ([block][octant][G nodes], A planes then B
-// planes), so G = 1 puts the eight octants' records of a node in one 128-B line (lanes of different
-// octants at the same node -- every traversal starts at the root -- read one line, not eight) and
-// larger G keeps neighbouring nodes of one octant together as the octant-major layout does.  Links
-// are stored as walk words (block * 8G + node in block), so the kernel's index (octant x octStride
-// + word) holds with octStride = G; END = rtk::kEndWalk, a word that is neither a node nor a leaf (a
-// walk that reaches it leaves the node and triangle steps at once: no sentinel loads).
-inline uint32_t goct_word(uint32_t i, uint32_t G) { return (i / G) * 8u * G + i % G; }
-void build_oct_nodes_grouped(const std::vector<uint32_t>& oct, uint32_t n, uint32_t G, std::vector<uint32_t>& out,
-                             uint32_t* b_ofs) {
-    const uint32_t stride = oct_stride(n), bofs = oct_b(n);
-    const uint32_t na = ((n + 1 + G - 1) / G) * 8u * G;  // A records, sentinel included, whole blocks
-    *b_ofs = na;
-    out.assign((size_t)2 * na * 4, 0u);
-    for (uint32_t i = 0; i <= n; ++i)
-        for (uint32_t o = 0; o < 8; ++o) {
-            const uint32_t* ra = &oct[((size_t)o * stride + i) * 4];
-            const uint32_t* rb = &oct[((size_t)bofs + (size_t)o * stride + i) * 4];
-            const size_t at = (size_t)goct_word(i, G) + (size_t)o * G;
-            uint32_t* wa = &out[at * 4];
-            uint32_t* wb = &out[((size_t)na + at) * 4];
-            for (int c = 0; c < 4; ++c) wa[c] = ra[c];
-            wb[0] = rb[0];
-            wb[1] = rb[1];
-            wb[2] = rb[2] >= kLeafMin ? rb[2] : goct_word(rb[2], G);  // leaf code as it is, else the near child
-            wb[3] = rb[3] >= n && RT_GOCT_END_WORD ? rtk::kEndWalk : goct_word(rb[3], G);  // END: the non-walk word
-        }
-}
-
 template <class T>
 int ensure_dev(T*& p, size_t& cap, size_t count) {
     if (cap >= count) return RT_SUCCESS;
@@ -402,61 +211,6 @@ int ensure_dev(T*& p, size_t& cap, size_t count) {
     if (e != hipSuccess) return map_hip(e);
     cap = count;
     return RT_SUCCESS;
-}
-
-// Node records for scenes read from HBM/L2 (64 B = half a cache line, so one visit touches
-// one line): q0 = {bmin.xyz, bmax.x}, q1 = {bmax.yz, c0, c1}, q2/q3 = skip[8].  Interior:
-// c0 = first child, c1 = second child | axis << 30; leaf: c0 = first triangle,
-// c1 = count | 3 << 30.  Children and skips are explicit, so the nodes can be renumbered:
-// the first `top` nodes in breadth-first order (the top of the tree, visited by nearly every
-// ray) come first and are staged in LDS; the rest keep their depth-first order.  The walk is
-// the same tree and skip table, so visits, tests and results are unchanged.
-void build_global_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
-                        uint32_t top, std::vector<uint32_t>& out, uint32_t* n_top) {
-    std::vector<uint32_t> order, newid(n, 0xffffffffu);
-    order.reserve(n);
-    std::vector<uint32_t> q = {0};
-    for (size_t h = 0; h < q.size() && order.size() < top; ++h) {
-        const uint32_t i = q[h];
-        newid[i] = (uint32_t)order.size();
-        order.push_back(i);
-        if (nd[i].nPrimitives == 0) {
-            q.push_back(i + 1);
-            q.push_back(nd[i].offset);
-        }
-    }
-    *n_top = (uint32_t)order.size();
-    for (uint32_t i = 0; i < n; ++i)
-        if (newid[i] == 0xffffffffu) {
-            newid[i] = (uint32_t)order.size();
-            order.push_back(i);
-        }
-    auto map = [&](uint32_t x) { return x == 0xffffffffu ? x : newid[x]; };
-    auto bits = [](float f) {
-        uint32_t u;
-        std::memcpy(&u, &f, 4);
-        return u;
-    };
-    out.assign((size_t)n * 16, 0u);
-    for (uint32_t p = 0; p < n; ++p) {
-        const uint32_t i = order[p];
-        const rt_cl_bvh_node& x = nd[i];
-        uint32_t* r = &out[(size_t)p * 16];
-        r[0] = bits(x.bounds.pmin.x);
-        r[1] = bits(x.bounds.pmin.y);
-        r[2] = bits(x.bounds.pmin.z);
-        r[3] = bits(x.bounds.pmax.x);
-        r[4] = bits(x.bounds.pmax.y);
-        r[5] = bits(x.bounds.pmax.z);
-        if (x.nPrimitives > 0) {
-            r[6] = x.offset;
-            r[7] = (uint32_t)x.nPrimitives | (3u << 30);
-        } else {
-            r[6] = map(i + 1);
-            r[7] = map(x.offset) | ((uint32_t)x.axis << 30);
-        }
-        for (int o = 0; o < 8; ++o) r[8 + o] = map(skips[(size_t)i * 8 + o]);
-    }
 }
 
 int prepare_scene(rt_kernel k) {
@@ -521,14 +275,8 @@ int prepare_scene(rt_kernel k) {
         if (e == hipSuccess) e = hipStreamSynchronize(qs(k->ctx));
         if (e != hipSuccess) return map_hip(e);
     }
-    if (k->packed_tris_cap < (size_t)nt) {
-        if (k->packed_tris) (void)hipFree(k->packed_tris);
-        k->packed_tris = nullptr;
-        k->packed_tris_cap = 0;
-        hipError_t e = hipMalloc(&k->packed_tris, (size_t)nt * 3 * sizeof(float4));
-        if (e != hipSuccess) return map_hip(e);
-        k->packed_tris_cap = nt;
-    }
+    rc = ensure_dev(k->packed_tris, k->packed_tris_cap, (size_t)nt * 3);
+    if (rc) return rc;
     rc = ensure_dev(k->shade_tris, k->shade_tris_cap, (size_t)nt * 3);
     if (rc) return rc;
     // two material tables: IEEE divisions (pinned, devicelib), then the shipped policy's
@@ -936,7 +684,222 @@ int rtEnqueueKernelFrames(rt_context ctx, rt_kernel k, size_t global_work_size, 
     return rc;
 }
 
+// ---- enqueue's steps: the resources, streams and launches of one LaunchPlan (rt_launch_plan.hpp) ----
+
+// the plan's inputs: plain values of the launch, the kernel's settings and its packed scene
+static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_t n_frames, bool fused) {
+    rtp::PlanIn in{};
+    std::memcpy(&in.W, &k->u32[RT_ARG_WIDTH], 4);
+    std::memcpy(&in.H, &k->u32[RT_ARG_HEIGHT], 4);
+    std::memcpy(&in.light_bounces, &k->u32[RT_ARG_LIGHT_BOUNCES], 4);
+    in.gws = global_work_size;
+    in.range_first = k->range_first, in.range_last = k->range_last;
+    in.n_frames = n_frames;
+    in.sched = k->sched, in.math = k->math;
+    in.stats = k->stats, in.hit_bound = k->hit_ids != nullptr;
+    in.fused = fused, in.overlap = ctx->overlap;
+    in.band_period = k->band_period, in.band_phase = k->band_phase;
+    in.n_nodes = k->n_nodes, in.n_tris = k->n_tris, in.n_mats = k->n_mats, in.n_top = k->n_top;
+    in.oct_ok = k->oct_ok;
+    in.goct_available = k->goct_nodes != nullptr, in.goct_b = k->goct_b;
+    in.force_global = k->force_global, in.global_oct = k->global_oct;
+    in.refill_min = k->refill_min, in.shade_min = k->shade_min, in.refill_min_set = k->refill_min_set;
+    in.refill_min_g = k->refill_min_g, in.shade_min_g = k->shade_min_g;
+    in.w_node = k->w_node, in.w_leaf = k->w_leaf, in.w_node_g = k->w_node_g, in.w_leaf_g = k->w_leaf_g;
+    in.chunk_pixels = k->chunk_pixels, in.tail_chunk = k->tail_chunk, in.bulk_percent = k->bulk_percent;
+    in.tile_major = k->tile_major, in.pf_sky = k->pf_sky, in.max_blocks = k->max_blocks;
+    in.wf_top_limit = k->wf_top_limit, in.wf_streams_per_cu = k->wf_streams_per_cu;
+    in.wf_refill_min = k->wf_refill_min;
+    in.num_cus = ctx->num_cus;
+    return in;
+}
+
+// workgroups per CU of the kernel the plan chose, at the plan's LDS size (cached per variant)
+static int lookup_occupancy(rt_kernel k, const rtp::LaunchPlan& p, bool fused) {
+    int& occ = k->occ_cache[p.si][k->math][p.lds][k->stats][p.var];
+    size_t& at = k->occ_smem[p.si][k->math][p.lds][k->stats][p.var];
+    if (occ == 0 || at != p.smem) {
+        occ = p.wf ? rtk::occupancy_wf_extend(k->math, p.lds, k->stats, p.bofs, p.smem, p.goct)
+                   : rtk::occupancy_kernel_entry(p.si, k->math, p.lds, k->stats, p.bofs, p.smem, p.goct, fused);
+        at = p.smem;
+    }
+    return occ;
+}
+
+// KernelEntry's arguments: the plan's scalars plus the kernel's pointers (the radiance set and the
+// work counters follow, once their resources are there)
+static void fill_args(rt_kernel k, const rtp::LaunchPlan& p, rtk::KernelArgs* args) {
+    rtk::KernelArgs& a = *args;
+    std::memset(&a, 0, sizeof(a));
+    a.result = static_cast<float4*>(k->bufs[RT_ARG_BUFFER_OUT]->dptr);
+    a.trisFull = static_cast<const rt_cl_triangle*>(k->bufs[RT_ARG_BUFFER_SCENE]->dptr);
+    a.materials = static_cast<const rt_cl_material*>(k->bufs[RT_ARG_BUFFER_MATERIAL]->dptr);
+    a.packedTris = k->packed_tris;
+    a.octNodes = p.regrouped ? k->goct_nodes : k->oct_nodes;
+    a.gNodes = k->g_nodes;
+    a.shadeTris = k->shade_tris;
+    a.shadeMats = k->shade_mats + (k->math == RT_MATH_SHIPPED ? 4 * (size_t)k->n_mats : 0);
+    a.nMats = k->n_mats, a.nTris = k->n_tris;
+    a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords, a.nTop = p.nTop;
+    std::memcpy(&a.width, &k->u32[RT_ARG_WIDTH], 4);
+    std::memcpy(&a.height, &k->u32[RT_ARG_HEIGHT], 4);
+    std::memcpy(&a.frameCount, &k->u32[RT_ARG_FRAME_COUNT], 4);
+    std::memcpy(&a.lightBounces, &k->u32[RT_ARG_LIGHT_BOUNCES], 4);
+    std::memcpy(&a.lightType, &k->u32[RT_ARG_LIGHT_TYPE], 4);
+    std::memcpy(&a.skyboxIntensity, &k->u32[RT_ARG_SKYBOX_INTENSITY], 4);
+    for (int i = 0; i < 3; ++i) {
+        a.camPos[i] = k->f3[0][i];
+        a.camFront[i] = k->f3[1][i];
+        a.camUp[i] = k->f3[2][i];
+    }
+    a.gidBegin = p.gidBegin, a.gidEnd = p.gidEnd;
+    a.rowBegin = p.rowBegin, a.rowCount = p.rowCount, a.tilesX = p.tilesX, a.nTiles = p.nTiles;
+    a.bandPeriod = p.bandPeriod, a.bandPhase = p.bandPhase;
+    a.chunkPixels = p.chunkPixels, a.tailChunk = p.tailChunk, a.chunkSplit = p.chunkSplit, a.tailBase = p.tailBase;
+    a.staticFirst = p.staticFirst, a.nParts = p.nParts, a.partLen = p.partLen;
+    a.refillMin = p.refillMin, a.shadeMin = p.shadeMin;
+    a.stepWeightNode = p.stepWeightNode, a.stepWeightLeaf = p.stepWeightLeaf;
+    a.flagTiles = p.flagTiles, a.tileMajor = p.tileMajor, a.nFrames = p.nFrames, a.radStride = p.radStride;
+    a.hitIds = k->hit_ids ? static_cast<int32_t*>(k->hit_ids->dptr) : nullptr;
+    a.hitT = k->hit_t ? static_cast<float*>(k->hit_t->dptr) : nullptr;
+    a.stats = k->dstats;
+    // per-frame launches: their own counters (two slots in turn with RT_PF_COUNTER_SLOTS, below)
+    a.workCounter = k->work_counter + 4 * RT_RAD_SETS;
+    if (p.use_pf_sky) {
+        a.pfKeyIn = k->accum_key + 4 + k->pf_parity;
+        a.pfKeyOut = k->accum_key + 4 + (k->pf_parity ^ 1);
+    }
+}
+
+// radiance set `rs` holds `need` radiance slots and `fneed` frame-flag bytes, and the events that
+// order its renders and accumulations exist
+static int ensure_radiance_set(rt_context ctx, rt_kernel k, int rs, size_t need, size_t fneed) {
+    if (k->rad_buf_cap[rs] >= need && k->flag_cap[rs] >= fneed) return RT_SUCCESS;
+    // the set may still be read by an accumulation in flight
+    hipError_t me = hipStreamSynchronize(ctx->astream);
+    if (me != hipSuccess) return map_hip(me);
+    if (k->rad_buf[rs]) (void)hipFree(k->rad_buf[rs]);
+    if (k->frame_flags[rs]) (void)hipFree(k->frame_flags[rs]);
+    k->rad_buf[rs] = nullptr;
+    k->frame_flags[rs] = nullptr;
+    k->rad_buf_cap[rs] = 0;
+    k->flag_cap[rs] = 0;
+    me = hipMalloc(&k->rad_buf[rs], need * sizeof(float4));
+    if (me == hipSuccess) me = hipMalloc(&k->frame_flags[rs], fneed);
+    if (me == hipSuccess && !k->rad_free[rs])
+        me = hipEventCreateWithFlags(&k->rad_free[rs], hipEventDisableTiming);
+    if (me == hipSuccess && !k->render_done)
+        me = hipEventCreateWithFlags(&k->render_done, hipEventDisableTiming);
+    if (me != hipSuccess) return map_hip(me);
+    k->rad_buf_cap[rs] = need;
+    k->flag_cap[rs] = fneed;
+    return RT_SUCCESS;
+}
+
+// the stream a fused render of radiance set `rs` goes to, made to wait for what it must follow
+static int pick_render_stream(rt_context ctx, rt_kernel k, bool own_stream, int rs, hipStream_t* rstr) {
+    if (own_stream) {
+        // the set's own render stream, after everything queued on the main stream so far
+        // (buffer writes, per-frame launches) but not after the previous step's render or
+        // accumulation: it fills the CUs that render's draining waves free.  (With hit
+        // buffers bound the renders stay in order on the main stream: each writes them.)
+        *rstr = ctx->rstream[ctx->rnext];
+        ctx->rnext = (ctx->rnext + 1) % RT_RENDER_STREAMS;
+        hipError_t me = rti::main_tail_wait(ctx, *rstr);
+        if (me != hipSuccess) return map_hip(me);
+    }
+    // the render writes the set: after the accumulation that last read it
+    if (k->rad_busy[rs]) {
+        hipError_t me = hipStreamWaitEvent(*rstr, k->rad_free[rs], 0);
+        if (me != hipSuccess) return map_hip(me);
+        k->rad_busy[rs] = false;
+    }
+    return RT_SUCCESS;
+}
+
+// the wavefront schedule's ray queues hold `cap` entries per plane, its counts G streams
+static int ensure_wavefront_queues(rt_kernel k, size_t cap, uint32_t G, hipStream_t rstr) {
+    if (k->wf_cap < cap) {
+        // earlier renders on this stream may still read them
+        hipError_t me = hipStreamSynchronize(rstr);
+        for (float4*& q : k->wf_q) {
+            if (q) (void)hipFree(q);
+            q = nullptr;
+        }
+        if (k->wf_hits) (void)hipFree(k->wf_hits);
+        k->wf_hits = nullptr;
+        k->wf_cap = 0;
+        for (float4*& q : k->wf_q)
+            if (me == hipSuccess) me = hipMalloc(&q, cap * 4 * sizeof(float4));
+        if (me == hipSuccess) me = hipMalloc(&k->wf_hits, cap * sizeof(float2));
+        if (me != hipSuccess) return map_hip(me);
+        k->wf_cap = cap;
+    }
+    if (k->wf_cnt_cap < 2 * ((size_t)G + 1)) {
+        hipError_t me = hipStreamSynchronize(rstr);
+        if (k->wf_cnt) (void)hipFree(k->wf_cnt);
+        k->wf_cnt = nullptr;
+        k->wf_cnt_cap = 0;
+        if (me == hipSuccess) me = hipMalloc(&k->wf_cnt, 2 * ((size_t)G + 1) * sizeof(uint32_t));
+        if (me != hipSuccess) return map_hip(me);
+        k->wf_cnt_cap = 2 * ((size_t)G + 1);
+    }
+    return RT_SUCCESS;
+}
+
+// fused frames: the gamma accumulation of every frame, in order, per pixel -- on the
+// accumulation stream after this render, overlapping whatever the main stream runs next
+// (the next fused render uses the other radiance set); qs() joins it back
+static int enqueue_accum(rt_context ctx, rt_kernel k, const rtk::KernelArgs& a, hipStream_t rstr) {
+    hipStream_t as = ctx->stream;
+    if (!ctx->overlap) ctx->mdirty = true;
+    // The render left its chunk counters for this accumulation to clear (accum_key_body); if
+    // the accumulation cannot be enqueued, clear them behind the render (same stream as the
+    // set's next render), so that render does not start with spent counters and skip tiles.
+    auto fail = [&](int rc) {
+        (void)hipMemsetAsync(a.workCounter, 0, 16, rstr);
+        return rc;
+    };
+    hipError_t e = hipSuccess;
+    if (ctx->overlap) {
+        as = ctx->astream;
+        e = hipEventRecord(k->render_done, rstr);
+        if (e == hipSuccess) e = hipStreamWaitEvent(as, k->render_done, 0);
+        if (e != hipSuccess) return fail(map_hip(e));
+    }
+    hipEvent_t ea = nullptr, eb = nullptr;
+    if (k->timing) {
+        ea = take_event(k);
+        eb = take_event(k);
+        if (!ea || !eb) return fail(RT_OUT_OF_RESOURCES);
+        (void)hipEventRecord(ea, as);
+    }
+    // (a root's gather copies of the previous image read `out`: the accumulation that rewrites
+    // it comes after them)
+    e = rti::out_read_wait(ctx, as);
+    if (e != hipSuccess) return fail(map_hip(e));
+#ifndef RT_DIAG_NO_ACCUM  // diagnostic A/B builds only (wrong images): the render without its accumulation
+    e = rtk::launch_accum_frames(a, k->math, k->accum_key, as);
+    if (e != hipSuccess) return fail(map_hip(e));
+#endif
+    if (k->timing) {
+        (void)hipEventRecord(eb, as);
+        k->pending_accum.emplace_back(ea, eb);
+    }
+    if (ctx->overlap) {
+        const int rs = k->rad_set;
+        e = hipEventRecord(k->rad_free[rs], as);
+        if (e == hipSuccess) e = hipEventRecord(ctx->atail, as);
+        if (e != hipSuccess) return map_hip(e);
+        k->rad_busy[rs] = true;
+        k->rad_set = (k->rad_set + 1) % RT_RAD_SETS;
+        ctx->apending = true;
+    }
+    return RT_SUCCESS;
+}
+
 static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_t n_frames) {
+    // 1. the handles, the arguments, the scene
     int rc = ensure_device(ctx);
     if (rc) return rc;
     if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
@@ -947,18 +910,17 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     std::memcpy(&W, &k->u32[RT_ARG_WIDTH], 4);
     std::memcpy(&H, &k->u32[RT_ARG_HEIGHT], 4);
     if (W == 0 || H == 0) return RT_INVALID_KERNEL_ARGS;
-    rt_mem out = k->bufs[RT_ARG_BUFFER_OUT];
-    if (out->size < global_work_size * 16) return RT_INVALID_GLOBAL_WORK_SIZE;
+    if (k->bufs[RT_ARG_BUFFER_OUT]->size < global_work_size * 16) return RT_INVALID_GLOBAL_WORK_SIZE;
     if (k->hit_ids && (k->hit_ids->size < (global_work_size + kHitPad) * 4 || k->hit_t->size < global_work_size * 4))
         return RT_INVALID_MEM_OBJECT;
     rc = prepare_scene(k);
     if (rc) return rc;
-    // the schedule this launch runs: the wavefront one needs a bounded bounce loop (two launches
-    // per bounce), else the step schedule renders it (same bits)
+
+    // 2. defer, fused
     int32_t lb;
     std::memcpy(&lb, &k->u32[RT_ARG_LIGHT_BOUNCES], 4);
-    const bool wf = k->sched == RT_SCHED_WAVEFRONT && lb >= 1 && lb <= rtk::kWfMaxBounces;
-    const int si = wf ? rtk::kSchedWavefront : (k->sched == RT_SCHED_WAVEFRONT ? RT_SCHED_STEP : k->sched);
+    const int si = rtp::resolve_schedule(k->sched, lb);
+    const bool wf = si == rtk::kSchedWavefront;
     // radiance per (frame slot, work-item) + the accumulation launch: fused frames, every wavefront
     // render, and (RT_TUNE_PERFRAME_DEFER) per-frame step launches -- then consecutive renders need
     // not wait for each other, only the accumulations are ordered
@@ -982,115 +944,29 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     // accumulations
     if (!fused) (void)qs(ctx);
 
-    uint64_t g0 = std::min<uint64_t>(k->range_first, global_work_size);
-    uint64_t g1 = k->range_last ? std::min<uint64_t>(k->range_last, global_work_size) : global_work_size;
-    if (g1 <= g0) return RT_SUCCESS;  // nothing in range
+    // 3. the plan (rt_launch_plan.cpp), with the kernel's occupancy at the LDS size it chose
+    const rtp::PlanIn in = plan_inputs(ctx, k, global_work_size, n_frames, fused);
+    rtp::LaunchPlan p;
+    rc = rtp::plan_shape(in, &p);
+    if (rc || p.nothing) return rc;
+    if (wf) {
+        int& occ_s = k->wf_shade_occ[k->math][k->stats];
+        if (occ_s == 0) occ_s = rtk::occupancy_wf_shade(k->math, k->stats);
+    }
+    rtp::plan_handout(in, lookup_occupancy(k, p, fused), k->wf_shade_occ[k->math][k->stats], &p);
 
+    // 4. the kernel's arguments
     rtk::KernelArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.result = static_cast<float4*>(out->dptr);
-    a.trisFull = static_cast<const rt_cl_triangle*>(k->bufs[RT_ARG_BUFFER_SCENE]->dptr);
-    a.materials = static_cast<const rt_cl_material*>(k->bufs[RT_ARG_BUFFER_MATERIAL]->dptr);
-    a.packedTris = k->packed_tris;
-    a.octNodes = k->oct_nodes;
-    a.gNodes = k->g_nodes;
-    a.shadeTris = k->shade_tris;
-    a.shadeMats = k->shade_mats + (k->math == RT_MATH_SHIPPED ? 4 * (size_t)k->n_mats : 0);
-    a.nMats = k->n_mats;
-    a.nNodes = k->n_nodes;
-    a.octStride = oct_stride(k->n_nodes);
-    a.octB = oct_b(k->n_nodes);
-    a.octRecords = oct_records(k->n_nodes);
-    a.nTris = k->n_tris;
-    a.width = W;
-    a.height = H;
-    std::memcpy(&a.frameCount, &k->u32[RT_ARG_FRAME_COUNT], 4);
-    std::memcpy(&a.lightBounces, &k->u32[RT_ARG_LIGHT_BOUNCES], 4);
-    std::memcpy(&a.lightType, &k->u32[RT_ARG_LIGHT_TYPE], 4);
-    std::memcpy(&a.skyboxIntensity, &k->u32[RT_ARG_SKYBOX_INTENSITY], 4);
-    for (int i = 0; i < 3; ++i) {
-        a.camPos[i] = k->f3[0][i];
-        a.camFront[i] = k->f3[1][i];
-        a.camUp[i] = k->f3[2][i];
-    }
-    a.gidBegin = g0;
-    a.gidEnd = g1;
-    const uint64_t row0 = g0 / W, row1 = (g1 + W - 1) / W;
-    a.rowBegin = (uint32_t)row0;
-    a.rowCount = (uint32_t)(row1 - row0);
-    const uint32_t tile = si == RT_SCHED_TILES ? 16u : 8u;
-    if (k->band_period > 1 && si == RT_SCHED_TILES) return RT_INVALID_OPERATION;
-    a.tilesX = (W + tile - 1) / tile;
-    uint64_t tilesY = (row1 - row0 + tile - 1) / tile;
-    a.bandPeriod = k->band_period;
-    a.bandPhase = k->band_phase;
-    if (k->band_period > 1) {  // bands phase, phase + period, ... of the row window
-        tilesY = tilesY > k->band_phase ? (tilesY - k->band_phase + k->band_period - 1) / k->band_period : 0;
-        if (tilesY == 0) return RT_SUCCESS;
-    }
-    const uint64_t n_tiles = tilesY * a.tilesX;
-    if (n_tiles * 64 > 0xfff00000ull) return RT_INVALID_GLOBAL_WORK_SIZE;
-    a.nTiles = (uint32_t)n_tiles;
-    // per-frame launches: their own counters (two slots in turn with RT_PF_COUNTER_SLOTS, below)
-    a.workCounter = k->work_counter + 4 * RT_RAD_SETS;
-    a.workCounterClear = nullptr;
-    a.chunkPixels = k->chunk_pixels ? k->chunk_pixels : 512u;  // (the launch's order decides below)
-    a.tailChunk = k->tail_chunk;
-    a.refillMin = k->refill_min;
-    a.shadeMin = k->shade_min;
-    a.stepWeightNode = k->w_node;
-    a.stepWeightLeaf = k->w_leaf;
-    a.nFrames = n_frames;
-    a.radStride = (uint32_t)g1;
-    a.radBuf = nullptr;
-    hipStream_t rstr = ctx->stream;  // the stream this launch's render goes to
+    fill_args(k, p, &a);
+
+    // 5, 6. fused: the radiance set and the stream this launch's render goes to
+    hipStream_t rstr = ctx->stream;
     if (fused) {
-        // fused frames: radiance slots indexed by global work-item id (the lane packs
-        // slot * g1 + gid into 32 bits); tiles x frames work items
-        // (work items stay below 2^32 - 2^20: the work-stealing ranges add a few tiles past
-        // their end in 32-bit fields)
-        if ((uint64_t)n_frames * g1 > 0xffffffffull || n_tiles * 64 * n_frames > 0xfff00000ull)
-            return RT_INVALID_GLOBAL_WORK_SIZE;
-        const size_t need = (size_t)n_frames * g1;
-        // frame flags: a byte per (slot, work item), or a 64-bit word per (slot, tile) (flagTiles)
-        const size_t fneed = std::max<size_t>(need, (size_t)n_frames * n_tiles * 8u);
         const int rs = ctx->overlap ? k->rad_set : 0;
-        if (k->rad_buf_cap[rs] < need || k->flag_cap[rs] < fneed) {
-            // the set may still be read by an accumulation in flight
-            hipError_t me = hipStreamSynchronize(ctx->astream);
-            if (me != hipSuccess) return map_hip(me);
-            if (k->rad_buf[rs]) (void)hipFree(k->rad_buf[rs]);
-            if (k->frame_flags[rs]) (void)hipFree(k->frame_flags[rs]);
-            k->rad_buf[rs] = nullptr;
-            k->frame_flags[rs] = nullptr;
-            k->rad_buf_cap[rs] = 0;
-            k->flag_cap[rs] = 0;
-            me = hipMalloc(&k->rad_buf[rs], need * sizeof(float4));
-            if (me == hipSuccess) me = hipMalloc(&k->frame_flags[rs], fneed);
-            if (me == hipSuccess && !k->rad_free[rs])
-                me = hipEventCreateWithFlags(&k->rad_free[rs], hipEventDisableTiming);
-            if (me == hipSuccess && !k->render_done)
-                me = hipEventCreateWithFlags(&k->render_done, hipEventDisableTiming);
-            if (me != hipSuccess) return map_hip(me);
-            k->rad_buf_cap[rs] = need;
-            k->flag_cap[rs] = fneed;
-        }
-        if (ctx->overlap && !k->hit_ids && !wf) {
-            // the set's own render stream, after everything queued on the main stream so far
-            // (buffer writes, per-frame launches) but not after the previous step's render or
-            // accumulation: it fills the CUs that render's draining waves free.  (With hit
-            // buffers bound the renders stay in order on the main stream: each writes them.)
-            rstr = ctx->rstream[ctx->rnext];
-            ctx->rnext = (ctx->rnext + 1) % RT_RENDER_STREAMS;
-            hipError_t me = rti::main_tail_wait(ctx, rstr);
-            if (me != hipSuccess) return map_hip(me);
-        }
-        // the render writes the set: after the accumulation that last read it
-        if (k->rad_busy[rs]) {
-            hipError_t me = hipStreamWaitEvent(rstr, k->rad_free[rs], 0);
-            if (me != hipSuccess) return map_hip(me);
-            k->rad_busy[rs] = false;
-        }
+        rc = ensure_radiance_set(ctx, k, rs, p.need, p.fneed);
+        if (rc) return rc;
+        rc = pick_render_stream(ctx, k, p.own_stream, rs, &rstr);
+        if (rc) return rc;
         a.radBuf = k->rad_buf[rs];
         a.frameFlags = k->frame_flags[rs];
         // one chunk counter per radiance set: renders of the two sets may run together
@@ -1099,211 +975,26 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     // everything below (counter clear, timing events, the render; the accumulation when it is not
     // overlapped) goes to rstr: the main stream unless a render stream was taken above
     if (rstr == ctx->stream) ctx->mdirty = true;
-    a.hitIds = k->hit_ids ? static_cast<int32_t*>(k->hit_ids->dptr) : nullptr;
-    a.hitT = k->hit_t ? static_cast<float*>(k->hit_t->dptr) : nullptr;
-    a.stats = k->dstats;
+    k->last_lds = p.lds;
 
-    // LDS: octant node records (8 x 32 B per node), triangles (48 B), shading records
-    // (48 B per triangle, 64 B per material); no stack
-    const size_t scene_bytes = (size_t)oct_records(k->n_nodes) * 16 + (size_t)k->n_tris * 96 + (size_t)k->n_mats * 64;
-    const bool lds = !k->force_global && k->oct_ok && scene_bytes <= kLdsBudget;
-
-    // scenes too large for LDS: the step schedule may walk the octant records in HBM/L2
-    // (RT_TUNE_GLOBAL_OCT) instead of the 64-B global node records
-    const bool goct = !lds && (wf || si == RT_SCHED_STEP) && k->oct_ok && k->global_oct;
-    a.nTop = lds || goct ? 0u : k->n_top;  // global path: top-of-tree node records staged in LDS
-    if (goct && RT_GOCT_GROUP && k->goct_nodes && k->goct_b) {
-        // regrouped records, links as walk words (build_oct_nodes_grouped)
-        a.octNodes = k->goct_nodes;
-        a.octStride = RT_GOCT_GROUP;
-        a.octB = k->goct_b;
-        a.octRecords = 2u * a.octB;
-        a.nNodes = RT_GOCT_END_WORD ? rtk::kEndWalk : goct_word(k->n_nodes, RT_GOCT_GROUP);  // the END word
-    }
-    // (octant walk: refill at 32 free lanes under the pixel-major order, 16 before: -0.5 %,
-    // profiles/r05/goct_bursts_weights.txt)
-    a.refillMin = lds ? k->refill_min : k->refill_min_g ? k->refill_min_g : goct ? 32u : 8u;
-    a.shadeMin = lds ? k->shade_min : k->shade_min_g ? k->shade_min_g : 48u;
-    if (!lds) {
-        // scenes in HBM/L2: a node step's loads cost more against a triangle step's than in LDS
-        // (octant walk under the pixel-major order: 65 / 55 -- 35: +1.0 %, 45: +0.4 %, 80-130 the same;
-        // profiles/r05/goct_bursts_weights.txt)
-        a.stepWeightNode = k->w_node_g ? k->w_node_g : goct ? 65u : k->w_node;
-        a.stepWeightLeaf = k->w_leaf_g ? k->w_leaf_g : k->w_leaf;
-    }
-    if (wf) a.nTop = std::min(a.nTop, k->wf_top_limit);
-    const size_t smem =
-        wf ? (lds ? ((size_t)a.octRecords + 3 * (size_t)k->n_tris) * 16 : (size_t)a.nTop * 64) +
-                 (rtk::kWfExtendThreads / 64) * rtk::kWfRingBytes
-           : (lds ? scene_bytes : (size_t)a.nTop * 64) +
-                 (si == RT_SCHED_STEP && !fused ? 4 * rtk::kFinishWaveBytes : 0) +
-                 (si == RT_SCHED_STEP && lds ? 4 * (fused ? rtk::kRingWaveBytes : rtk::kRingWaveBytesPf) : 0) +
-                 (si == RT_SCHED_STEP ? rtk::kStealBytes : 0);
-    k->last_lds = lds;
-    // the step schedule's ray ring (LDS scenes) writes each tile's frame flags as one word at ring
-    // fill; the other fused renders write a byte per path at its end
-    a.flagTiles = fused && !wf && si == RT_SCHED_STEP && lds ? 1u : fused && !wf && si == RT_SCHED_STEP && goct ? 2u : 0u;
-
-    const int mi = k->math;
-    const bool bofs = lds && a.octB == rtk::kOctB;
-    const int var = (bofs || goct ? 1 : 0) + (a.radBuf ? 2 : 0);  // occupancy cache: the variant slot
-    int& occ = k->occ_cache[si][mi][lds][k->stats][var];
-    if (occ == 0 || k->occ_smem[si][mi][lds][k->stats][var] != smem) {
-        occ = wf ? rtk::occupancy_wf_extend(k->math, lds, k->stats, bofs, smem, goct)
-                 : rtk::occupancy_kernel_entry(si, k->math, lds, k->stats, bofs, smem, goct, a.radBuf != nullptr);
-        k->occ_smem[si][mi][lds][k->stats][var] = smem;
-    }
-    uint64_t grid = (uint64_t)(k->max_blocks ? std::min(occ, k->max_blocks) : occ) * (uint64_t)ctx->num_cus;
-    // tiles: one workgroup per 16x16 tile at most; persistent schedules: one 8x8 tile per wave
-    // (wavefront extend: 8 waves per workgroup)
-    grid = std::min<uint64_t>(grid, si == RT_SCHED_TILES ? n_tiles
-                                    : wf                 ? (n_tiles * n_frames + 7) / 8
-                                                         : (n_tiles * n_frames + 3) / 4);
-    if (grid == 0) grid = 1;
-    {
-        // bulk chunks only when every resident wave gets at least two of them; a small frame
-        // (512x512: ~40 pixels per wave) is handed out 64 pixels at a time
-        const uint64_t tot = (uint64_t)a.nTiles * 64u * n_frames, waves = grid * 4u;
-        // fused work order (step_body) on the HBM/L2 scene path: pixel-major when F is a power of two
-        // -- a pixel's frames side by side in a wave, so a step's lanes read fewer records: bunny
-        // proxy 1.352 -> 1.282 ms/frame, emulated N = 8 rank 1.637 -> 1.535 ms
-        // (profiles/r05/pixel_major_ab.txt); else tile-major for large launches (a tile's frames back
-        // to back: -1.4 %, profiles/r01/work_order_ab.txt) and frame-major for small ones (tile-major
-        // bunches a costly tile's frames into the tail); LDS scenes frame-major (the ray ring)
-        // (the pixel-major order is the step schedule's: the wavefront extend launches keep the
-        // big / frame-major rule their order was measured with, profiles/r02/wavefront/)
-        const bool pow2 = (n_frames == 2 || n_frames == 4 || n_frames == 8) && si == RT_SCHED_STEP;
-        const bool big = !lds && tot >= 4096u * waves;
-        a.tileMajor = n_frames < 2 ? 0u
-                      : k->tile_major == 2 ? (!lds && pow2 ? 2u : 1u)
-                      : k->tile_major == 1 ? 1u
-                      : k->tile_major == 0 ? 0u
-                      : !lds && pow2       ? 2u
-                      : big                ? 1u
-                                           : 0u;
-        // the bulk share stops where the tail would hold less than two bulk chunks per wave: a
-        // bulk chunk (512 pixel-frames, ~0.25 ms of a wave's time at 4K) taken just before the
-        // split otherwise outlasts the tail that should even the waves out -- small launches
-        // (multi-GPU ranks: N = 8 renders 1/8 of the frame) get a larger tail (bulk 80 % -> ~37 %:
-        // emulated N = 8 rank step, Cornell 1.112 -> 1.047 ms, bunny proxy 1.694 -> 1.629 ms;
-        // profiles/r02/multigpu/n8_chunk_sweep_*.txt); full 4K launches keep 80 %
-        // bulk chunks of 512 work items, 1024 in the pixel-major order (two whole tiles x 8 frames per
-        // fetch: bunny proxy -0.8 %, profiles/r05/goct_bursts_weights.txt)
-        const uint32_t chunk = k->chunk_pixels ? k->chunk_pixels : a.tileMajor == 2u ? 1024u : 512u;
-        a.chunkPixels = chunk;
-        uint64_t bulk = tot * k->bulk_percent / 100;
-        const uint64_t reserve = 2u * waves * chunk;
-        bulk = std::min<uint64_t>(bulk, tot > reserve ? tot - reserve : 0u);
-        a.chunkSplit = tot >= 2u * waves * chunk ? (uint32_t)(bulk / chunk * chunk) : 0u;
-        // tail chunks: the largest power-of-two multiple of 64 pixels, up to tail_chunk, that still
-        // gives every wave >= 2.5 of them -- few atomics on the tail counter for large launches,
-        // fine-grained balance for small ones (4K fused 256, 4K per-frame / 1080p / 512^2 fused 128,
-        // 512^2 per-frame 64: profiles/r02/chunk_sweep.txt)
-        // (with counter partitions -- per-frame launches without a bulk region, below -- the grabs no
-        // longer queue on one address, and the finer per-wave rule balances better)
-        const bool parts = RT_COUNTER_PARTS > 1 && RT_STATIC_FIRST && RT_PF_COUNTER_SLOTS && !fused &&
-                           si == RT_SCHED_STEP && !wf && a.chunkSplit == 0u && grid >= RT_COUNTER_PARTS &&
-                           tot >= 256u * waves;  // (512^2 frames, ~50 work items per wave: +5 % with them)
-        const uint64_t share = (tot - a.chunkSplit) * (parts ? 1u : RT_TAIL_SHARE_WAVES) / waves;
-        uint32_t tail = 64;
-        while (tail * 2u <= k->tail_chunk && (uint64_t)tail * 2u * 5u <= share * 2u) tail *= 2u;
-        a.tailChunk = tail;
-        // RT_STATIC_FIRST: a per-frame launch without a bulk region starts every wave on its own tail chunk,
-        // with no atomic (step_body), and the tail counter hands out from past those chunks.  (The
-        // same for the bulk region of large launches was 3-5 % slower: the waves then stay in step
-        // and meet again at the counter.)
-        a.tailBase = a.chunkSplit;
-        if (RT_STATIC_FIRST && !fused && si == RT_SCHED_STEP && !wf && a.chunkSplit == 0u) {
-            a.staticFirst = 1u;
-            a.tailBase = (uint32_t)std::min<uint64_t>(waves * tail, tot);
-            // RT_COUNTER_PARTS: the tail counter split over that many partitions (with the per-frame
-            // counter slots, whose layout holds them)
-            if (parts) {
-                a.nParts = RT_COUNTER_PARTS;
-                a.partLen = (uint32_t)((tot / 64u + RT_COUNTER_PARTS - 1) / RT_COUNTER_PARTS * 64u);
-            }
-            // such launches (a 1080p frame: ~400 work items per wave) refill at 16 free lanes, not 6:
-            // 1080p 2-bounce frames -2.8 % (4K fused launches lose 5 % at 16,
-            // profiles/r06/work_handout_ab.txt)
-            if (lds && !k->refill_min_set) a.refillMin = 16u;
-        }
-    }
-
-    // per-frame sky shortcut (step_body): its key costs each wave one gamma step at launch
-    // start, which pays off from ~256 pixels per wave (1080p -2.7 %, 4K) and not on small frames
-    // (512^2; round 6: the threshold was 1k pixels per wave before the small-launch hand-out,
-    // profiles/r06/work_handout_ab.txt)
-    if (!fused && si == RT_SCHED_STEP &&
-        (k->pf_sky == 2 || (k->pf_sky == 1 && g1 - g0 >= 256u * 4u * grid))) {
-        a.pfKeyIn = k->accum_key + 4 + k->pf_parity;
-        a.pfKeyOut = k->accum_key + 4 + (k->pf_parity ^ 1);
-    }
+    // 7. wavefront: the ray queues
     rtk::WfArgs wa{};
     float4* wq[2] = {};
     uint32_t* wcnt[2] = {};
-    unsigned grid_s = 0;
     if (wf) {
-        // queues for every (frame slot, work-item) of the launch, streams of 64-entry blocks
-        const uint64_t blocks = n_tiles * n_frames;
-        const size_t cap = (size_t)blocks * 64;
-        // streams: by default one per shade workgroup the GPU holds at once, so the shade
-        // launch is a single round of workgroups (no second, partly empty round)
-        int& occ_s = k->wf_shade_occ[mi][k->stats];
-        if (occ_s == 0) occ_s = rtk::occupancy_wf_shade(k->math, k->stats);
-        const uint64_t per_cu = k->wf_streams_per_cu ? k->wf_streams_per_cu : (uint64_t)occ_s;
-        const uint32_t G = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)ctx->num_cus * per_cu));
-        if (k->wf_cap < cap) {
-            // earlier renders on this stream may still read them
-            hipError_t me = hipStreamSynchronize(rstr);
-            for (float4*& q : k->wf_q) {
-                if (q) (void)hipFree(q);
-                q = nullptr;
-            }
-            if (k->wf_hits) (void)hipFree(k->wf_hits);
-            k->wf_hits = nullptr;
-            k->wf_cap = 0;
-            for (float4*& q : k->wf_q)
-                if (me == hipSuccess) me = hipMalloc(&q, cap * 4 * sizeof(float4));
-            if (me == hipSuccess) me = hipMalloc(&k->wf_hits, cap * sizeof(float2));
-            if (me != hipSuccess) return map_hip(me);
-            k->wf_cap = cap;
-        }
-        if (k->wf_cnt_cap < 2 * ((size_t)G + 1)) {
-            hipError_t me = hipStreamSynchronize(rstr);
-            if (k->wf_cnt) (void)hipFree(k->wf_cnt);
-            k->wf_cnt = nullptr;
-            k->wf_cnt_cap = 0;
-            if (me == hipSuccess) me = hipMalloc(&k->wf_cnt, 2 * ((size_t)G + 1) * sizeof(uint32_t));
-            if (me != hipSuccess) return map_hip(me);
-            k->wf_cnt_cap = 2 * ((size_t)G + 1);
-        }
-        wq[0] = k->wf_q[0];
-        wq[1] = k->wf_q[1];
-        wcnt[0] = k->wf_cnt;
-        wcnt[1] = k->wf_cnt + G + 1;
+        rc = ensure_wavefront_queues(k, (size_t)p.cap, p.G, rstr);
+        if (rc) return rc;
+        wq[0] = k->wf_q[0], wq[1] = k->wf_q[1];
+        wcnt[0] = k->wf_cnt, wcnt[1] = k->wf_cnt + p.G + 1;
         wa.hits = k->wf_hits;
-        wa.cap = (uint32_t)cap;
-        wa.G = G;
-        wa.nBlocks = (uint32_t)blocks;
-        wa.refillMin = k->wf_refill_min;
-        grid_s = G;  // one workgroup per stream
+        wa.cap = p.cap, wa.G = p.G, wa.nBlocks = p.nBlocks, wa.refillMin = p.wfRefillMin;
     }
-    // the chunk counters start at zero: per-frame launches clear theirs here; a fused render's
-    // (its radiance set's) were cleared by the accumulation that followed the set's previous render
-    // (accum_key_body), which this render already waits for -- no clearing launch in front of it
-#ifdef RT_DIAG_NO_ACCUM
-    const bool clear_here = true;  // (diagnostic builds without the accumulation launch)
-#else
-    const bool clear_here = !fused;
-#endif
-    // RT_PF_COUNTER_SLOTS: a per-frame step launch takes one of two counter slots in turn and zeroes
-    // the other for the next one (step_body), so no clearing launch sits between consecutive renders
-    // (1080p: a 4-us fill and two ~6-us dispatch gaps in a ~0.28-ms frame)
-    const bool pf_slots = RT_PF_COUNTER_SLOTS && !fused && si == RT_SCHED_STEP && !wf;
-    if (pf_slots) {
+
+    // 8. the counter slot or clear, the timing events, the launch
+    if (p.pf_slots) {
         a.workCounter = k->work_counter + 4 * RT_RAD_SETS + k->pf_ctr * rtk::kMaxParts * rtk::kPartStride;
         a.workCounterClear = k->work_counter + 4 * RT_RAD_SETS + (k->pf_ctr ^ 1) * rtk::kMaxParts * rtk::kPartStride;
-    } else if (si != RT_SCHED_TILES && !wf && clear_here) {
+    } else if (p.clear_counter_here) {
         hipError_t me = hipMemsetAsync(a.workCounter, 0, 16, rstr);
         if (me != hipSuccess) return map_hip(me);
     }
@@ -1314,64 +1005,24 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
         if (!ev0 || !ev1) return RT_OUT_OF_RESOURCES;
         (void)hipEventRecord(ev0, rstr);
     }
-    hipError_t e = wf ? rtk::launch_wavefront(a, wa, wq, wcnt, k->math, lds, k->stats, bofs, (unsigned)grid, smem,
-                                              grid_s, rstr, goct)
-                      : rtk::launch_kernel_entry(a, si, k->math, lds, k->stats, (unsigned)grid, smem, rstr, goct);
+    hipError_t e = wf ? rtk::launch_wavefront(a, wa, wq, wcnt, k->math, p.lds, k->stats, p.bofs, (unsigned)p.grid,
+                                              p.smem, p.grid_s, rstr, p.goct)
+                      : rtk::launch_kernel_entry(a, si, k->math, p.lds, k->stats, (unsigned)p.grid, p.smem, rstr,
+                                                 p.goct);
     if (e != hipSuccess) return map_hip(e);
     if (k->timing) {
         (void)hipEventRecord(ev1, rstr);
         k->pending_events.emplace_back(ev0, ev1);
     }
     if (a.pfKeyIn) k->pf_parity ^= 1;
-    if (pf_slots) k->pf_ctr ^= 1;
+    if (p.pf_slots) k->pf_ctr ^= 1;  // flips only when the launch call reported success
+
+    // 9. fused: the accumulation launch
     if (fused) {
-        // fused frames: the gamma accumulation of every frame, in order, per pixel -- on the
-        // accumulation stream after this render, overlapping whatever the main stream runs next
-        // (the next fused render uses the other radiance set); qs() joins it back
-        hipStream_t as = ctx->stream;
-        if (!ctx->overlap) ctx->mdirty = true;
-        // The render left its chunk counters for this accumulation to clear (accum_key_body); if
-        // the accumulation cannot be enqueued, clear them behind the render (same stream as the
-        // set's next render), so that render does not start with spent counters and skip tiles.
-        auto fail = [&](int rc) {
-            (void)hipMemsetAsync(a.workCounter, 0, 16, rstr);
-            return rc;
-        };
-        if (ctx->overlap) {
-            as = ctx->astream;
-            e = hipEventRecord(k->render_done, rstr);
-            if (e == hipSuccess) e = hipStreamWaitEvent(as, k->render_done, 0);
-            if (e != hipSuccess) return fail(map_hip(e));
-        }
-        hipEvent_t ea = nullptr, eb = nullptr;
-        if (k->timing) {
-            ea = take_event(k);
-            eb = take_event(k);
-            if (!ea || !eb) return fail(RT_OUT_OF_RESOURCES);
-            (void)hipEventRecord(ea, as);
-        }
-        // (a root's gather copies of the previous image read `out`: the accumulation that rewrites
-        // it comes after them)
-        e = rti::out_read_wait(ctx, as);
-        if (e != hipSuccess) return fail(map_hip(e));
-#ifndef RT_DIAG_NO_ACCUM  // diagnostic A/B builds only (wrong images): the render without its accumulation
-        e = rtk::launch_accum_frames(a, k->math, k->accum_key, as);
-        if (e != hipSuccess) return fail(map_hip(e));
-#endif
-        if (k->timing) {
-            (void)hipEventRecord(eb, as);
-            k->pending_accum.emplace_back(ea, eb);
-        }
-        if (ctx->overlap) {
-            const int rs = k->rad_set;
-            e = hipEventRecord(k->rad_free[rs], as);
-            if (e == hipSuccess) e = hipEventRecord(ctx->atail, as);
-            if (e != hipSuccess) return map_hip(e);
-            k->rad_busy[rs] = true;
-            k->rad_set = (k->rad_set + 1) % RT_RAD_SETS;
-            ctx->apending = true;
-        }
+        rc = enqueue_accum(ctx, k, a, rstr);
+        if (rc) return rc;
     }
+    // 10. bookkeeping
     if (k->pending_events.size() + k->pending_accum.size() > 4096) {
         rc = drain_events(k);
         if (rc) return rc;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/rt_cl_types.h"
+#include "rt_layout.hpp"
 
 namespace rtk {
 
@@ -67,39 +68,6 @@ struct KernelArgs {
     uint32_t nParts, partLen;
 };
 
-constexpr int kSchedTiles = 0;  // one pixel per lane per 16x16 tile, all bounces in place
-// (1: path regeneration and 3: a per-wave LDS path pool were measured slower than the step
-// schedule and retired in round 3; DESIGN.md section 5 keeps their numbers)
-constexpr int kSchedStep = 2;   // per-wave state machine: node / triangle steps, batched shading
-constexpr int kSchedWavefront = 4;  // extend / shade launches per bounce over HBM ray queues
-constexpr int kNumSched = 5;
-// frames per fused launch (rtEnqueueKernelFrames splits longer runs)
-constexpr uint32_t kMaxFusedFrames = 8;
-// step schedule LDS per wave: the finish queue, 64 x {radiance, gid}
-constexpr uint32_t kFinishWaveBytes = 64u * 16u;
-// step schedule, LDS scenes: per-wave ring of camera rays generated a whole 8x8 tile at a time
-// ({dir, seed}, {invDir, sign} (fused launches) + work-item id per slot)
-constexpr uint32_t kRingSlots = 64;
-constexpr uint32_t kRingWaveBytes = kRingSlots * 32u + kRingSlots * 4u;
-constexpr uint32_t kRingWaveBytesPf = kRingSlots * 16u + kRingSlots * 4u;  // per-frame: no invDir
-// step schedule: per workgroup, each wave's remaining chunk {next, end} (64-bit word per wave),
-// from which its siblings take single tiles once the work counter is dry
-constexpr uint32_t kStealBytes = 4u * 8u + 32u;  // (padded to whole float4s)
-// END as a walk word that is neither a node (< 2^24) nor a leaf code (count << 24 | first, count
-// 1..127): the step schedule's byte-address LDS walk and its octant walk over HBM/L2 (step_body)
-constexpr uint32_t kEndWalk = 0xff000000u;
-#ifndef RT_GOCT_END_WORD
-#define RT_GOCT_END_WORD 1  // the HBM/L2 octant walk's END as kEndWalk (0: its sentinel's word, visited)
-#endif
-
-// LDS node records of trees with at most kOctBMaxStride records per plane keep their B planes at
-// the fixed float4 offset kOctB, so a node step reads B with an immediate offset from A's address
-constexpr uint32_t kOctBMaxStride = 64;
-// counter partitions: words between two partitions' counters (1 KB), and the most partitions
-constexpr uint32_t kPartStride = 256;
-constexpr uint32_t kMaxParts = 8;
-constexpr uint32_t kOctB = 8 * kOctBMaxStride;
-
 using KernelFn = void (*)(KernelArgs);
 
 // ---- wavefront schedule (rt_wavefront.hpp) ----------------------------------------------------
@@ -122,10 +90,6 @@ using WfKernelFn = void (*)(KernelArgs, WfArgs);
 struct WfKernels {
     WfKernelFn extend, shade;
 };
-constexpr unsigned kWfExtendThreads = 512;  // extend workgroup: 8 waves (LDS scene staged once per 8)
-constexpr unsigned kWfShadeThreads = 256;   // shade workgroup: one stream, 256 paths per round
-constexpr int kWfMaxBounces = 64;            // longer bounce loops run the step schedule
-constexpr uint32_t kWfRingBytes = 64u * 32u;  // extend: per-wave ray ring ({o, position}, {d, -})
 // the launches of one wavefront render: for b < lightBounces, extend(b) then shade(b); queues and
 // counts alternate between q[0]/q[1] and cnt[0]/cnt[1]
 hipError_t launch_wavefront(const KernelArgs& a, WfArgs w, float4* const q[2], uint32_t* const cnt[2], int math,

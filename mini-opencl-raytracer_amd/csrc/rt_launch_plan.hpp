@@ -1,0 +1,89 @@
+// rt_launch_plan.hpp -- how one KernelEntry launch hands its work out, as a pure function of plain
+// values (rt_launch_plan.cpp): no HIP, no allocation, no globals.  enqueue (rt_capi.cpp) fills a
+// PlanIn, calls plan_shape, looks the kernel's occupancy up for the LDS size that gives, calls
+// plan_handout, and turns the LaunchPlan into rtk::KernelArgs, resources and launches.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+namespace rtp {
+
+struct PlanIn {
+    uint32_t W, H;                          // image size (both > 0)
+    uint64_t gws;                           // global work size of the launch
+    uint64_t range_first, range_last;       // rtKernelSetWorkRange (last 0: to the end)
+    uint32_t n_frames;                      // frames of this launch (>= 1)
+    int32_t light_bounces;
+    int sched, math;                        // as requested (RT_SCHED_*, RT_MATH_*)
+    bool stats, hit_bound;                  // rt_stats counters on; primary-hit buffers bound
+    bool fused;                             // radiance slots + accumulation launch (enqueue decides)
+    bool overlap;                           // the context's accumulation overlap
+    uint32_t band_period, band_phase;       // 8-row band interleave
+    uint32_t n_nodes, n_tris, n_mats, n_top;  // the packed scene
+    bool oct_ok;                            // every leaf fits the octant records
+    bool goct_available;                    // regrouped octant records exist ...
+    uint32_t goct_b;                        // ... and their B planes' float4 offset
+    bool force_global;
+    int global_oct;
+    // tuning (rt_kernel_s; rtKernelSetTuning)
+    uint32_t refill_min, shade_min;
+    bool refill_min_set;
+    uint32_t refill_min_g, shade_min_g;
+    uint32_t w_node, w_leaf, w_node_g, w_leaf_g;
+    uint32_t chunk_pixels, tail_chunk, bulk_percent;
+    int tile_major, pf_sky, max_blocks;
+    uint32_t wf_top_limit, wf_streams_per_cu, wf_refill_min;
+    int num_cus;
+};
+
+struct LaunchPlan {
+    bool nothing;                           // no work item in range / no band row: RT_SUCCESS, no launch
+    // ---- plan_shape ----
+    int si;                                 // the schedule the launch runs (rtk::kSched*)
+    bool wf, lds, goct, bofs;
+    int var;                                // occupancy cache: the variant slot
+    size_t smem;                            // dynamic LDS bytes
+    // rtk::KernelArgs scalars
+    uint64_t gidBegin, gidEnd;
+    uint32_t rowBegin, rowCount, tilesX, nTiles, bandPeriod, bandPhase;
+    uint32_t nTop;
+    bool regrouped;                         // walk the regrouped octant records (goct_nodes)
+    uint32_t octStride, octB, octRecords, nNodes;
+    uint32_t refillMin, shadeMin, stepWeightNode, stepWeightLeaf;
+    uint32_t flagTiles, nFrames, radStride;
+    size_t need, fneed;                     // fused: radiance slots (float4) and frame-flag bytes of the set
+    bool own_stream;                        // fused: the render goes to a render stream of its own
+    bool pf_slots;                          // per-frame step launch: takes a counter slot, zeroes the other
+    bool clear_counter_here;                // the launch's counters are cleared in front of it
+    // ---- plan_handout ----
+    uint64_t grid;
+    uint32_t tileMajor, chunkPixels, tailChunk, chunkSplit, tailBase, staticFirst, nParts, partLen;
+    bool use_pf_sky;                        // per-frame sky shortcut keys
+    // wavefront queues
+    uint32_t cap, G, nBlocks, wfRefillMin;
+    unsigned grid_s;
+};
+
+// RT_COUNTER_PARTS of this build (LaunchPlan::nParts is 0 or this)
+uint32_t counter_parts();
+
+// the schedule a launch runs: the wavefront one needs a bounded bounce loop (two launches per
+// bounce), else the step schedule renders it (same bits)
+int resolve_schedule(int sched, int32_t light_bounces);
+
+// Everything up to the LDS size: returns RT_SUCCESS (out->nothing set when there is no launch to
+// make), RT_INVALID_GLOBAL_WORK_SIZE or RT_INVALID_OPERATION.
+int plan_shape(const PlanIn& in, LaunchPlan* out);
+// The grid and the work hand-out, from the occupancy (workgroups per CU) of the kernel plan_shape
+// chose at out->smem; occ_shade: the wavefront shade kernel's (read only when out->wf).
+void plan_handout(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out);
+
+// both steps (occupancies known beforehand: tests)
+inline int plan_launch(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out) {
+    const int rc = plan_shape(in, out);
+    if (rc == 0 && !out->nothing) plan_handout(in, occ, occ_shade, out);
+    return rc;
+}
+
+}  // namespace rtp

@@ -1,0 +1,232 @@
+// rt_scene_pack.cpp -- validation of the flattened BVH and the node records packed from it.
+// Pure host code (no HIP): prepare_scene (rt_capi.cpp) owns the device buffers and the copies.
+#include "rt_scene_pack.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <limits>
+
+#include "../../include/rt_status.h"
+
+namespace rtp {
+
+// Validate the flattened BVH (CLBVHnode.cpp:161-183 contract) and return its depth and its
+// node count.  The tree is the prefix [0, end) of the array: in the depth-first layout (first
+// child = parent + 1, second child after the first child's subtree) the root's subtree ends
+// after the leaf its chain of second children reaches.  Nodes past `end` are never read -- by
+// the reference's walk from node 0 either -- so a buffer may be larger than the tree it holds
+// (rtBuildBVH writes `count` nodes into a buffer of 2n-1).  Within the tree every node is
+// checked and each one but the root must have exactly one parent; since a parent's index is
+// smaller than its children's, that makes every node reachable from node 0 and the
+// skip-pointer walk a finite depth-first order (a child shared by two parents would make it
+// loop).
+int check_nodes(const rt_cl_bvh_node* nd, uint32_t n, uint32_t n_tris, int* depth_out, uint32_t* n_used) {
+    if (n == 0) return RT_INVALID_MEM_OBJECT;
+    uint32_t last = 0;  // the root's chain of second children (offsets strictly increase)
+    while (nd[last].nPrimitives == 0) {
+        if (nd[last].offset <= last || nd[last].offset >= n) return RT_INVALID_MEM_OBJECT;
+        last = nd[last].offset;
+    }
+    n = last + 1;
+    std::vector<int> depth(n, -1);
+    std::vector<uint8_t> parents(n, 0);
+    depth[0] = 0;
+    int max_depth = 0;
+    // children have larger indices than their parent, so one forward sweep sets depths
+    for (uint32_t i = 0; i < n; ++i) {
+        const rt_cl_bvh_node& x = nd[i];
+        if (i > 0 && parents[i] != 1) return RT_INVALID_MEM_OBJECT;  // orphan: unreachable
+        if (x.nPrimitives > 0) {
+            if ((uint64_t)x.offset + x.nPrimitives > n_tris) return RT_INVALID_MEM_OBJECT;
+            max_depth = std::max(max_depth, depth[i]);
+        } else {
+            if (x.axis > 2) return RT_INVALID_MEM_OBJECT;
+            const uint64_t a = (uint64_t)i + 1, b = x.offset;
+            if (a >= n || b >= n || b <= a) return RT_INVALID_MEM_OBJECT;
+            if (parents[a]++ != 0 || parents[b]++ != 0) return RT_INVALID_MEM_OBJECT;  // shared child
+            depth[a] = depth[i] + 1;
+            depth[b] = depth[i] + 1;
+        }
+    }
+    *depth_out = max_depth;
+    *n_used = n;
+    // The reference's 64-entry stack (kernel_bvh.cl:181) would overflow past depth 64; the
+    // stackless walk here has no such limit, so deeper trees are rendered, not rejected.
+    return RT_SUCCESS;
+}
+
+// Per-octant skip pointers (see rt_kernels.hip, intersect): for octant o (bit i = the ray
+// direction's sign on axis i) the reference visits an interior node's second child first
+// when bit axis(n) is set (kernel_bvh.cl:200-207).  skip[n][o] is the node the reference
+// pops after finishing n's subtree: near child -> far child, far child -> skip of parent.
+// Children have larger indices than their parent, so one forward sweep fills the table.
+void build_skips(const rt_cl_bvh_node* nd, uint32_t n, std::vector<uint32_t>& skips) {
+    skips.assign((size_t)n * 8, 0xffffffffu);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (nd[i].nPrimitives > 0) continue;
+        const uint32_t first = i + 1, second = nd[i].offset;
+        for (uint32_t o = 0; o < 8; ++o) {
+            const bool swap = (o >> nd[i].axis) & 1u;
+            const uint32_t nearc = swap ? second : first, farc = swap ? first : second;
+            skips[(size_t)nearc * 8 + o] = farc;
+            skips[(size_t)farc * 8 + o] = skips[(size_t)i * 8 + o];
+        }
+    }
+}
+
+// Octant-resolved node records for LDS-resident scenes (stored as 16 planes of float4:
+// A[octant][node], then B[octant][node], each plane n + 1 records): for node i and ray
+// octant o,
+//   A = {near.x, near.y, near.z, far.x}, B = {far.y, far.z, hit_next, miss_next}
+// where near/far are the slab planes kernel_bvh.cl:156-169 selects by the ray's signs
+// (bit-exact copies of pmin/pmax), miss_next = skip[i][o] and hit_next is the near child
+// (interior, < 2^24) or the leaf code count << 24 | first (count 1..127).  The reference's
+// "stack empty" is record n, a sentinel every ray misses (its near planes are +inf along the
+// octant's direction, so t0 = +inf) whose successors are n itself: a finished walk parks
+// there, and the kernel needs no end test per step.  A node step is two b128 reads, the slab
+// arithmetic and two selects.  Returns false when a leaf does not fit (> 127 primitives or
+// first + count > 2^24): such a scene is rendered from the global layout instead (LDS scenes
+// are small, so this takes an unusual hand-made BVH).
+bool build_oct_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
+                     std::vector<uint32_t>& out) {
+    const uint32_t stride = oct_stride(n), bofs = oct_b(n);
+    out.assign((size_t)oct_records(n) * 4, 0u);
+    bool ok = n < kLeafMin;
+    auto bits = [](float f) {
+        uint32_t u;
+        std::memcpy(&u, &f, 4);
+        return u;
+    };
+    const float inf = std::numeric_limits<float>::infinity();
+    for (uint32_t i = 0; i <= n; ++i) {
+        uint32_t leaf = 0;
+        float lo[3], hi[3];
+        if (i < n) {
+            const rt_cl_bvh_node& x = nd[i];
+            if (x.nPrimitives > 0) {
+                if (x.nPrimitives <= 127 && (uint64_t)x.offset + x.nPrimitives <= kLeafMin)
+                    leaf = ((uint32_t)x.nPrimitives << 24) | x.offset;
+                else
+                    ok = false;
+            }
+            lo[0] = x.bounds.pmin.x, lo[1] = x.bounds.pmin.y, lo[2] = x.bounds.pmin.z;
+            hi[0] = x.bounds.pmax.x, hi[1] = x.bounds.pmax.y, hi[2] = x.bounds.pmax.z;
+        } else {
+            // END sentinel: near plane +inf (octant bit clear: near = pmin) or -inf (set: near =
+            // pmax), i.e. lo = +inf, hi = -inf -- (near - o) * invDir = +inf on every axis
+            for (int ax = 0; ax < 3; ++ax) lo[ax] = inf, hi[ax] = -inf;
+        }
+        for (uint32_t o = 0; o < 8; ++o) {
+            // octant-major planes A[o][node], B[o][node] (16 B each): lanes visiting different
+            // nodes in the same octant hit different LDS banks
+            uint32_t* ra = &out[((size_t)o * stride + i) * 4];
+            uint32_t* rb = &out[((size_t)bofs + (size_t)o * stride + i) * 4];
+            float nr[3], fr[3];
+            for (int ax = 0; ax < 3; ++ax) {
+                const bool neg = (o >> ax) & 1u;
+                nr[ax] = neg ? hi[ax] : lo[ax];
+                fr[ax] = neg ? lo[ax] : hi[ax];
+            }
+            ra[0] = bits(nr[0]);
+            ra[1] = bits(nr[1]);
+            ra[2] = bits(nr[2]);
+            ra[3] = bits(fr[0]);
+            rb[0] = bits(fr[1]);
+            rb[1] = bits(fr[2]);
+            if (i == n) {
+                rb[2] = rb[3] = n;
+                continue;
+            }
+            const uint32_t skip = skips[(size_t)i * 8 + o];
+            rb[2] = nd[i].nPrimitives > 0 ? leaf : (((o >> nd[i].axis) & 1u) ? nd[i].offset : i + 1);
+            rb[3] = skip == 0xffffffffu ? n : skip;
+        }
+    }
+    return ok;
+}
+
+// The same octant records regrouped for the walk over HBM/L2 (RT_GOCT_GROUP = G > 0): blocks of G
+// consecutive nodes, each block laid out octant-major ([block][octant][G nodes], A planes then B
+// planes), so G = 1 puts the eight octants' records of a node in one 128-B line (lanes of different
+// octants at the same node -- every traversal starts at the root -- read one line, not eight) and
+// larger G keeps neighbouring nodes of one octant together as the octant-major layout does.  Links
+// are stored as walk words (block * 8G + node in block), so the kernel's index (octant x octStride
+// + word) holds with octStride = G; END = rtk::kEndWalk, a word that is neither a node nor a leaf (a
+// walk that reaches it leaves the node and triangle steps at once: no sentinel loads).
+void build_oct_nodes_grouped(const std::vector<uint32_t>& oct, uint32_t n, uint32_t G, std::vector<uint32_t>& out,
+                             uint32_t* b_ofs) {
+    const uint32_t stride = oct_stride(n), bofs = oct_b(n);
+    const uint32_t na = ((n + 1 + G - 1) / G) * 8u * G;  // A records, sentinel included, whole blocks
+    *b_ofs = na;
+    out.assign((size_t)2 * na * 4, 0u);
+    for (uint32_t i = 0; i <= n; ++i)
+        for (uint32_t o = 0; o < 8; ++o) {
+            const uint32_t* ra = &oct[((size_t)o * stride + i) * 4];
+            const uint32_t* rb = &oct[((size_t)bofs + (size_t)o * stride + i) * 4];
+            const size_t at = (size_t)goct_word(i, G) + (size_t)o * G;
+            uint32_t* wa = &out[at * 4];
+            uint32_t* wb = &out[((size_t)na + at) * 4];
+            for (int c = 0; c < 4; ++c) wa[c] = ra[c];
+            wb[0] = rb[0];
+            wb[1] = rb[1];
+            wb[2] = rb[2] >= kLeafMin ? rb[2] : goct_word(rb[2], G);  // leaf code as it is, else the near child
+            wb[3] = rb[3] >= n && RT_GOCT_END_WORD ? rtk::kEndWalk : goct_word(rb[3], G);  // END: the non-walk word
+        }
+}
+
+// Node records for scenes read from HBM/L2 (64 B = half a cache line, so one visit touches
+// one line): q0 = {bmin.xyz, bmax.x}, q1 = {bmax.yz, c0, c1}, q2/q3 = skip[8].  Interior:
+// c0 = first child, c1 = second child | axis << 30; leaf: c0 = first triangle,
+// c1 = count | 3 << 30.  Children and skips are explicit, so the nodes can be renumbered:
+// the first `top` nodes in breadth-first order (the top of the tree, visited by nearly every
+// ray) come first and are staged in LDS; the rest keep their depth-first order.  The walk is
+// the same tree and skip table, so visits, tests and results are unchanged.
+void build_global_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
+                        uint32_t top, std::vector<uint32_t>& out, uint32_t* n_top) {
+    std::vector<uint32_t> order, newid(n, 0xffffffffu);
+    order.reserve(n);
+    std::vector<uint32_t> q = {0};
+    for (size_t h = 0; h < q.size() && order.size() < top; ++h) {
+        const uint32_t i = q[h];
+        newid[i] = (uint32_t)order.size();
+        order.push_back(i);
+        if (nd[i].nPrimitives == 0) {
+            q.push_back(i + 1);
+            q.push_back(nd[i].offset);
+        }
+    }
+    *n_top = (uint32_t)order.size();
+    for (uint32_t i = 0; i < n; ++i)
+        if (newid[i] == 0xffffffffu) {
+            newid[i] = (uint32_t)order.size();
+            order.push_back(i);
+        }
+    auto map = [&](uint32_t x) { return x == 0xffffffffu ? x : newid[x]; };
+    auto bits = [](float f) {
+        uint32_t u;
+        std::memcpy(&u, &f, 4);
+        return u;
+    };
+    out.assign((size_t)n * 16, 0u);
+    for (uint32_t p = 0; p < n; ++p) {
+        const uint32_t i = order[p];
+        const rt_cl_bvh_node& x = nd[i];
+        uint32_t* r = &out[(size_t)p * 16];
+        r[0] = bits(x.bounds.pmin.x);
+        r[1] = bits(x.bounds.pmin.y);
+        r[2] = bits(x.bounds.pmin.z);
+        r[3] = bits(x.bounds.pmax.x);
+        r[4] = bits(x.bounds.pmax.y);
+        r[5] = bits(x.bounds.pmax.z);
+        if (x.nPrimitives > 0) {
+            r[6] = x.offset;
+            r[7] = (uint32_t)x.nPrimitives | (3u << 30);
+        } else {
+            r[6] = map(i + 1);
+            r[7] = map(x.offset) | ((uint32_t)x.axis << 30);
+        }
+        for (int o = 0; o < 8; ++o) r[8 + o] = map(skips[(size_t)i * 8 + o]);
+    }
+}
+
+}  // namespace rtp

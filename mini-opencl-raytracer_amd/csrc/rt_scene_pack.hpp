@@ -1,0 +1,45 @@
+// rt_scene_pack.hpp -- host-side scene validation and record packing (rt_scene_pack.cpp): what
+// turns a malformed scene into an error code, never a wild GPU walk.  No HIP here.
+#pragma once
+
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/rt_cl_types.h"
+#include "rt_layout.hpp"
+
+namespace rtp {
+
+// leaf codes (count << 24 | first, count 1..127) start here; node indices stay below
+constexpr uint32_t kLeafMin = 1u << 24;
+
+// records per octant plane: the n nodes, the END sentinel, and one pad record when that count is
+// even -- an odd plane stride (x 16 B) staggers the eight planes over the LDS banks, so lanes of
+// different octants at the same node do not collide (an even stride of 40 put planes o and o+2
+// on the same banks: +40 % bank-conflict cycles)
+inline uint32_t oct_stride(uint32_t n) { return (n + 1) | 1u; }
+// float4 offset of the B planes: rtk::kOctB for trees of at most kOctBMaxStride records per plane
+// (a node step then reads B at an immediate offset from A), else right after the A planes
+inline uint32_t oct_b(uint32_t n) {
+    return oct_stride(n) <= rtk::kOctBMaxStride ? rtk::kOctB : 8u * oct_stride(n);
+}
+inline uint32_t oct_records(uint32_t n) { return oct_b(n) + 8u * oct_stride(n); }
+
+#ifndef RT_GOCT_GROUP
+#define RT_GOCT_GROUP 1  // node-major: bunny proxy fused 1.405 -> 1.393 ms/frame (profiles/r03/goct_layout_ab.txt)
+#endif
+// walk word of node i in the regrouped records (build_oct_nodes_grouped)
+inline uint32_t goct_word(uint32_t i, uint32_t G) { return (i / G) * 8u * G + i % G; }
+
+// (see rt_scene_pack.cpp for each one's contract)
+int check_nodes(const rt_cl_bvh_node* nd, uint32_t n, uint32_t n_tris, int* depth_out, uint32_t* n_used);
+void build_skips(const rt_cl_bvh_node* nd, uint32_t n, std::vector<uint32_t>& skips);
+bool build_oct_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
+                     std::vector<uint32_t>& out);
+void build_oct_nodes_grouped(const std::vector<uint32_t>& oct, uint32_t n, uint32_t G, std::vector<uint32_t>& out,
+                             uint32_t* b_ofs);
+void build_global_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
+                        uint32_t top, std::vector<uint32_t>& out, uint32_t* n_top);
+
+}  // namespace rtp

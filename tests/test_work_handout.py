@@ -1,5 +1,5 @@
 """GPU: the persistent schedules' work hand-out hands every work item out exactly once, whatever
-path a launch takes (rt_capi.cpp chunk rule, step_body take_tile / next_chunk): per-frame launches
+path a launch takes (rt_launch_plan.cpp chunk rule, step_body take_tile / next_chunk): per-frame launches
 with counter partitions (>= 256 work items per wave: 1080p and up), with a static first chunk and
 one tail counter (smaller frames), with a bulk region (4K), odd sizes whose last tiles are partial,
 and small tail chunks.  Consecutive per-frame launches also alternate between the two counter slots
