@@ -433,8 +433,10 @@ __device__ __forceinline__ void tri_accept(const TriEval& e, int32_t idx, Traver
     // The reference's early returns (det < 1e-8, u < 0, u > 1, v < 0, u + v > 1; then t <
     // isect.t) in VALU arithmetic rather than a chain of mask operations: for operands that are
     // not NaN, x < y <=> x - y < 0 exactly (an IEEE difference of distinct floats is never
-    // rounded to zero or across it; denormals are kept), and minNum skips NaN operands, which
-    // the early returns let through as well ((det < 1e-8 || -det > 1e-8) == det < 1e-8).
+    // rounded to zero or across it; denormals are kept).  NaN operands (a zero-area triangle's
+    // 0 * inf, an overflowing or non-finite vertex): minNum skips them as the early returns let
+    // them through -- exercised against the oracle and the live reference by
+    // tests/test_stress_gpu.py (test_soups_pinned_equals_oracle, test_nonfinite_soup).
     // Rejected when any test fails; otherwise accepted iff t < isect.t.
     const float rej = __builtin_fminf(__builtin_fminf(__builtin_fminf(e.det - kHitEps, e.u),
                                                       __builtin_fminf(1.0f - e.u, e.v)),
