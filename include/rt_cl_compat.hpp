@@ -92,6 +92,10 @@ public:
         check(rtEnqueueReadBuffer(ctx_, buffer.get(), 0, 0, size, ptr), "Failed to read buffer");
     }
     inline void ExecuteKernel(std::shared_ptr<CLKernel> kernel, size_t workSize) const;
+    // extensions: batched ray queries over caller rays (rtEnqueueIntersectRays, rtEnqueueCameraRays)
+    inline void IntersectRays(std::shared_ptr<CLKernel> kernel, const Buffer& rays, const Buffer& hits, size_t nRays,
+                              int mode = RT_QUERY_CLOSEST, size_t firstRay = 0) const;
+    inline void CameraRays(std::shared_ptr<CLKernel> kernel, size_t workSize, const Buffer& rays) const;
     void Finish() const { check(rtFinish(ctx_), "Failed to finish queue"); }
     rt_context GetContext() const { return ctx_; }
 
@@ -129,6 +133,14 @@ private:
 
 inline void CLContext::ExecuteKernel(std::shared_ptr<CLKernel> kernel, size_t workSize) const {
     check(rtEnqueueKernel(ctx_, kernel->GetKernel(), workSize), "Failed to enqueue kernel");
+}
+inline void CLContext::IntersectRays(std::shared_ptr<CLKernel> kernel, const Buffer& rays, const Buffer& hits,
+                                     size_t nRays, int mode, size_t firstRay) const {
+    check(rtEnqueueIntersectRays(ctx_, kernel->GetKernel(), rays.get(), firstRay, nRays, mode, hits.get()),
+          "Failed to enqueue ray query");
+}
+inline void CLContext::CameraRays(std::shared_ptr<CLKernel> kernel, size_t workSize, const Buffer& rays) const {
+    check(rtEnqueueCameraRays(ctx_, kernel->GetKernel(), workSize, rays.get()), "Failed to enqueue camera rays");
 }
 
 }  // namespace rtcl

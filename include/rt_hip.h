@@ -189,7 +189,8 @@ int rtKernelSetHitBuffers(rt_kernel k, rt_mem hit_ids, rt_mem hit_t);
 typedef struct rt_stats {
     uint64_t rays, node_visits, tri_tests, hits;
     uint64_t launches;
-    double kernel_ms;  /* sum of KernelEntry durations (HIP events) when timing is on */
+    double kernel_ms;  /* sum of KernelEntry durations (HIP events) when timing is on; ray queries
+                        * (rtEnqueueIntersectRays) add theirs, and count in `launches` */
     /* diagnostic (step schedule, stats on): shader-clock cycles summed over waves spent
      * refilling/finishing pixels, traversing, shading, and in total */
     uint64_t cycles_refill, cycles_traverse, cycles_shade, cycles_total;
@@ -209,6 +210,63 @@ int rtKernelSetStats(rt_kernel k, int enable);
 int rtKernelSetTiming(rt_kernel k, int enable);
 int rtKernelGetStats(rt_kernel k, rt_stats* out);
 int rtKernelResetStats(rt_kernel k);
+
+/* ---- batched ray queries over caller rays ------------------------------------------------
+ * The scene is the one bound to `k` (BUFFER_SCENE, BUFFER_NODE), packed and validated exactly as
+ * a render launch does (rtValidateBVH first: RT_INVALID_MEM_OBJECT on a bad tree).  A query runs
+ * in k's math mode and honours rtKernelForceGlobalScene; BUFFER_OUT and BUFFER_MATERIAL need not
+ * be bound (a bound material buffer is validated as for a render).
+ *
+ * rtEnqueueIntersectRays answers rays [first_ray, first_ray + n_rays) of `rays` (rt_ray records)
+ * into the same slots of `hits` (rt_ray_hit records); the other slots are not touched.  Per ray it
+ * is the reference's InitRay(origin, dir) followed by Intersect (kernel_bvh.cl:42-55, 171-219) in
+ * the reference's node and triangle order -- `dir` is normalised by the kernel and need not be
+ * unit length -- with two generalisations: isect.t starts at `tmax` instead of MAX_RENDER_DIST, and
+ * a triangle the reference would accept is accepted only if also t >= tmin.  With tmin = -INFINITY
+ * and tmax = 100000.0f the result is Intersect's bit for bit, its negative-t hits and one-sided
+ * (det >= 1e-8) culling included; tmin > tmax always misses.
+ *   RT_QUERY_CLOSEST  the full walk: the closest accepted triangle.
+ *   RT_QUERY_ANY      the same walk stopped at its first accepted triangle (deterministic: the
+ *                     closest-hit walk's first acceptance); hits exactly when closest-hit does.
+ * A hit writes prim = the index into the BVH-ordered triangle array (as rtKernelSetHitBuffers), t,
+ * and the triangle's barycentrics u, v (the hit point is v1 + u (v2 - v1) + v (v3 - v1)); a miss
+ * writes {-1, tmax, 0, 0}.
+ * Errors (nothing is launched): a mode other than the two RT_INVALID_VALUE; n_rays == 0 RT_SUCCESS
+ * with no launch; a missing scene or node buffer RT_INVALID_KERNEL_ARGS; first_ray + n_rays > 2^31
+ * RT_INVALID_VALUE; `rays` and `hits` the same buffer RT_INVALID_MEM_OBJECT; first_ray + n_rays
+ * beyond either buffer's size RT_INVALID_BUFFER_SIZE; a BVH leaf of more than 127 triangles
+ * RT_INVALID_OPERATION (queries walk the octant records, which hold leaves up to that size).
+ *
+ * rtEnqueueCameraRays writes, for every work-item gid in [0, global_work_size), the primary ray
+ * KernelEntry would trace for it with k's current WIDTH, HEIGHT, FRAME_COUNT and camera slots, in
+ * k's math mode (seed gid + frame_hash(frameCount)): origin = camPos, tmin = -INFINITY, tmax =
+ * 100000.0f, dir = the direction CreateRay hands to InitRay (its normalize(dir), before InitRay
+ * normalises again), so feeding the record to rtEnqueueIntersectRays reproduces the primary ray
+ * exactly.  rtKernelSetWorkRange and rtKernelSetRowInterleave are ignored: every gid is written.
+ * Errors: those slots unset or WIDTH / HEIGHT zero RT_INVALID_KERNEL_ARGS; global_work_size 0 or
+ * above 2^32 - 1 RT_INVALID_GLOBAL_WORK_SIZE; `rays` smaller than 32 B per work-item
+ * RT_INVALID_BUFFER_SIZE.
+ *
+ * Both are asynchronous on the context's in-order queue like every other call: coalesced per-frame
+ * launches (PERFRAME_BATCH) are launched first, pending fused-frame accumulations are ordered
+ * before them, they count as "another call touching the context" for the deferral rules above, and
+ * later reads of `hits` / `rays` see the results.  With rtKernelSetStats on, a query adds its rays,
+ * node visits, triangle tests and hits to rt_stats (an any-hit query counts only what it walked). */
+typedef struct rt_ray {
+    float origin[3];
+    float tmin;
+    float dir[3];
+    float tmax;
+} rt_ray; /* 32 B */
+typedef struct rt_ray_hit {
+    int32_t prim;
+    float t, u, v;
+} rt_ray_hit; /* 16 B */
+#define RT_QUERY_CLOSEST 0
+#define RT_QUERY_ANY 1
+int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t first_ray, size_t n_rays, int mode,
+                           rt_mem hits);
+int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem rays);
 
 /* Where the scene lives: 1 = staged in LDS (when it fits), 0 = read from HBM/L2. */
 int rtKernelGetSceneInLDS(rt_kernel k, int* in_lds);
@@ -319,7 +377,9 @@ int rtValidateBVH(const void* nodes, size_t n_nodes, size_t n_tris, int* depth);
  *                                     or a device pointer of one of its buffers
  *                                     (rtBufferGetDevicePointer) has been handed out, the host may
  *                                     synchronise outside the library, so from then on every
- *                                     rtEnqueueKernel launches at once. */
+ *                                     rtEnqueueKernel launches at once.
+ *   QUERY_REFILL_MIN                  ray queries (rtEnqueueIntersectRays): take rays from the ring
+ *                                     once this many lanes are free (1-64, default 32) */
 enum rt_tuning {
     RT_TUNE_REFILL_MIN = 0,
     RT_TUNE_SHADE_MIN = 1,
@@ -344,7 +404,8 @@ enum rt_tuning {
     /* 22: the retired speculative walk's switch (RT_INVALID_VALUE) */
     RT_TUNE_PERFRAME_BATCH = 23,
     RT_TUNE_STEP_WEIGHT_NODE_GLOBAL = 24,
-    RT_TUNE_STEP_WEIGHT_LEAF_GLOBAL = 25
+    RT_TUNE_STEP_WEIGHT_LEAF_GLOBAL = 25,
+    RT_TUNE_QUERY_REFILL_MIN = 26
 };
 int rtKernelSetTuning(rt_kernel k, int param, int value);
 int rtKernelGetTuning(rt_kernel k, int param, int* value);

@@ -61,6 +61,12 @@ MATERIAL_DTYPE = np.dtype([("diffuse", FLOAT3), ("specular", FLOAT3), ("emission
                            ("padding", np.int32)])
 assert VERTEX_DTYPE.itemsize == 80 and TRIANGLE_DTYPE.itemsize == 256
 assert NODE_DTYPE.itemsize == 48 and MATERIAL_DTYPE.itemsize == 64
+# rt_ray / rt_ray_hit (rt_hip.h): the records of rtEnqueueIntersectRays and rtEnqueueCameraRays
+RAY_DTYPE = np.dtype([("origin", np.float32, (3,)), ("tmin", np.float32), ("dir", np.float32, (3,)),
+                      ("tmax", np.float32)])
+RAY_HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32)])
+assert RAY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 16
+QUERY_CLOSEST, QUERY_ANY = 0, 1
 
 # RenderKernelArgument_t (CLutils.h:11-27)
 BUFFER_OUT, BUFFER_SCENE, BUFFER_NODE, BUFFER_MATERIAL = 0, 1, 2, 3
@@ -79,7 +85,7 @@ TUNING = {"refill_min": 0, "shade_min": 1, "refill_min_global": 2, "shade_min_gl
           "tile_major": 13, "perframe_sky": 14, "wf_refill_min": 15, "wf_streams_per_cu": 16,
           "wf_top_nodes": 17, "global_oct": 18, "perframe_defer": 19, "max_blocks": 20,
           "perframe_defer_min": 21, "perframe_batch": 23, "step_weight_node_global": 24,
-          "step_weight_leaf_global": 25}
+          "step_weight_leaf_global": 25, "query_refill_min": 26}
 
 
 class Stats(ctypes.Structure):
@@ -129,6 +135,8 @@ _HIP_PROTOS = {
     "rtSetKernelArg": (ctypes.c_int, [_vp, ctypes.c_uint, ctypes.c_size_t, _vp]),
     "rtEnqueueKernel": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
     "rtEnqueueKernelFrames": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint]),
+    "rtEnqueueIntersectRays": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, _vp]),
+    "rtEnqueueCameraRays": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp]),
     "rtEnqueueReadBuffer": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtEnqueueWriteBuffer": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtFinish": (ctypes.c_int, [_vp]),

@@ -79,6 +79,19 @@ class CLContext:
         check(self._lib.rtEnqueueKernelFrames(self.handle, kernel.handle, int(work_size), int(n_frames)),
               "Failed to enqueue kernel frames")
 
+    def IntersectRays(self, kernel: "CLKernel", rays: "Buffer", hits: "Buffer", n_rays: int,
+                      mode: int = N.QUERY_CLOSEST, first: int = 0) -> None:
+        """rtEnqueueIntersectRays: rays [first, first + n_rays) of `rays` (N.RAY_DTYPE records) against the
+        scene bound to `kernel`, answered into the same slots of `hits` (N.RAY_HIT_DTYPE)."""
+        check(self._lib.rtEnqueueIntersectRays(self.handle, kernel.handle, rays.handle, int(first), int(n_rays),
+                                               int(mode), hits.handle), "Failed to enqueue ray query")
+
+    def CameraRays(self, kernel: "CLKernel", work_size: int, rays: "Buffer") -> None:
+        """rtEnqueueCameraRays: the primary ray KernelEntry would trace for each work-item, as N.RAY_DTYPE
+        records (work range and row interleave ignored)."""
+        check(self._lib.rtEnqueueCameraRays(self.handle, kernel.handle, int(work_size), rays.handle),
+              "Failed to enqueue camera rays")
+
     def Finish(self) -> None:
         check(self._lib.rtFinish(self.handle), "Failed to finish queue")
 

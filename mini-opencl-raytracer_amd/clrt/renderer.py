@@ -45,6 +45,7 @@ class Raytracer:
         self.output: Buffer | None = None
         self.pixels = np.zeros((self.height * self.width, 4), np.float32)
         self._scene_bufs: list = []
+        self._cast_bufs: tuple | None = None  # (capacity in rays, ray buffer, hit buffer) of cast()
 
     # CLRaytracer::Init (CLRaytracer.cpp:104-120)
     def Init(self) -> None:
@@ -95,6 +96,34 @@ class Raytracer:
         self.ctx.Finish()
         self.frame_count += 1
 
+    def cast(self, origins, dirs, tmin=-np.inf, tmax=100000.0, any_hit: bool = False) -> np.ndarray:
+        """Intersect caller rays with the uploaded scene (rtEnqueueIntersectRays): `origins` and `dirs`
+        are (n, 3) arrays (directions need not be unit length), `tmin` / `tmax` scalars or (n,) arrays.
+        Returns n N.RAY_HIT_DTYPE records {prim, t, u, v}; a miss is {-1, tmax, 0, 0}.  `any_hit` stops
+        each walk at its first accepted triangle.  The device buffers are kept and reused."""
+        origins = np.asarray(origins, np.float32).reshape(-1, 3)
+        dirs = np.asarray(dirs, np.float32).reshape(-1, 3)
+        n = len(origins)
+        if len(dirs) != n:
+            raise ValueError("origins and dirs differ in length")
+        rays = np.empty(n, N.RAY_DTYPE)
+        rays["origin"], rays["dir"] = origins, dirs
+        rays["tmin"], rays["tmax"] = tmin, tmax
+        hits = np.empty(n, N.RAY_HIT_DTYPE)
+        if n == 0:
+            return hits
+        if self._cast_bufs is None or self._cast_bufs[0] < n:
+            if self._cast_bufs:
+                self._cast_bufs[1].release()
+                self._cast_bufs[2].release()
+            self._cast_bufs = (n, self.ctx.create_buffer(N.MEM_READ_WRITE, n * N.RAY_DTYPE.itemsize),
+                               self.ctx.create_buffer(N.MEM_READ_WRITE, n * N.RAY_HIT_DTYPE.itemsize))
+        _, rb, hb = self._cast_bufs
+        self.ctx.WriteBuffer(rb, rays)
+        self.ctx.IntersectRays(self.kernel, rb, hb, n, N.QUERY_ANY if any_hit else N.QUERY_CLOSEST)
+        self.ctx.ReadBuffer(hb, hits, blocking=True)
+        return hits
+
     def image(self) -> np.ndarray:
         """Last read-back frame as (H, W, 3); row 0 is the bottom row (GL order)."""
         return self.pixels.reshape(self.height, self.width, 4)[:, :, :3]
@@ -129,6 +158,10 @@ class Raytracer:
         for b in self._scene_bufs:
             b.release()
         self._scene_bufs = []
+        if self._cast_bufs:
+            self._cast_bufs[1].release()
+            self._cast_bufs[2].release()
+            self._cast_bufs = None
         if self.output:
             self.output.release()
         if self.kernel:

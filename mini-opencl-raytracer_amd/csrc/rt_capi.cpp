@@ -30,6 +30,7 @@
 #include "rt_internal.hpp"
 #include "rt_kernels.hpp"
 #include "rt_launch_plan.hpp"
+#include "rt_query_plan.hpp"
 #include "rt_scene_pack.hpp"
 
 namespace {
@@ -97,6 +98,10 @@ struct rt_kernel_s {
     // wavefront schedule: ray queues (two sets of 4 float4 planes), hit records, stream counts
     // (refill at 32 free lanes: bunny proxy 2.62 -> 2.45 ms/frame, profiles/r02/wavefront/sweep_bunny.txt)
     uint32_t wf_refill_min = 32, wf_streams_per_cu = 0, wf_top_limit = 256;  // streams 0: auto
+    uint32_t query_refill_min = 32;    // ray queries: RT_TUNE_QUERY_REFILL_MIN
+    // ray queries: [math][lds][stats][bofs][any] -> workgroups per CU (0 = unknown) at query_occ_smem
+    int query_occ[3][2][2][2][2] = {};
+    size_t query_occ_smem[3][2][2][2][2] = {};
     int wf_shade_occ[3][2] = {};       // [math][stats] -> shade workgroups per CU (0 = unknown)
     float4* wf_q[2] = {};
     float2* wf_hits = nullptr;
@@ -213,18 +218,21 @@ int ensure_dev(T*& p, size_t& cap, size_t count) {
     return RT_SUCCESS;
 }
 
-int prepare_scene(rt_kernel k) {
+// need_mats false (ray queries): the material buffer may be unbound -- then no material is packed
+// and no material index checked, and the next render packs and checks again (checked_mats reset)
+int prepare_scene(rt_kernel k, bool need_mats = true) {
     rt_mem tm = k->bufs[RT_ARG_BUFFER_SCENE], nm = k->bufs[RT_ARG_BUFFER_NODE],
            mm = k->bufs[RT_ARG_BUFFER_MATERIAL];
+    if (need_mats && !mm) return RT_INVALID_KERNEL_ARGS;
     if (tm->size < sizeof(rt_cl_triangle) || nm->size < sizeof(rt_cl_bvh_node) ||
-        mm->size < sizeof(rt_cl_material))
+        (mm && mm->size < sizeof(rt_cl_material)))
         return RT_INVALID_MEM_OBJECT;
     const uint32_t nt = (uint32_t)(tm->size / sizeof(rt_cl_triangle));
     const uint32_t n_buf = (uint32_t)(nm->size / sizeof(rt_cl_bvh_node));
-    const uint32_t nmat = (uint32_t)(mm->size / sizeof(rt_cl_material));
+    const uint32_t nmat = mm ? (uint32_t)(mm->size / sizeof(rt_cl_material)) : 0u;
     const bool tris_stale = k->packed_for_tris != tm || k->packed_tris_gen != tm->generation;
     const bool nodes_stale = k->packed_for_nodes != nm || k->packed_nodes_gen != nm->generation;
-    const bool mats_stale = k->checked_mats != mm || k->checked_mats_gen != mm->generation;
+    const bool mats_stale = mm && (k->checked_mats != mm || k->checked_mats_gen != mm->generation);
     if (!tris_stale && !nodes_stale && !mats_stale) return RT_SUCCESS;
 
     std::vector<uint8_t> tmp_t, tmp_n;
@@ -238,7 +246,7 @@ int prepare_scene(rt_kernel k) {
     rc = check_nodes(reinterpret_cast<const rt_cl_bvh_node*>(nb), n_buf, nt, &depth, &nn);
     if (rc) return rc;
     const rt_cl_triangle* tr = reinterpret_cast<const rt_cl_triangle*>(tb);
-    for (uint32_t i = 0; i < nt; ++i)
+    for (uint32_t i = 0; mm && i < nt; ++i)
         if (tr[i].mtlIndex >= nmat) return RT_INVALID_MEM_OBJECT;
     std::vector<uint32_t> skips;
     build_skips(reinterpret_cast<const rt_cl_bvh_node*>(nb), nn, skips);
@@ -283,7 +291,7 @@ int prepare_scene(rt_kernel k) {
     rc = ensure_dev(k->shade_mats, k->shade_mats_cap, (size_t)nmat * 8);
     if (rc) return rc;
     hipError_t e = rtk::launch_pack(static_cast<const rt_cl_triangle*>(tm->dptr), nt, k->packed_tris,
-                                    k->shade_tris, static_cast<const rt_cl_material*>(mm->dptr), nmat,
+                                    k->shade_tris, mm ? static_cast<const rt_cl_material*>(mm->dptr) : nullptr, nmat,
                                     k->shade_mats, qs(k->ctx));
     if (e != hipSuccess) return map_hip(e);
     k->n_nodes = nn;
@@ -297,7 +305,7 @@ int prepare_scene(rt_kernel k) {
     k->packed_for_nodes = nm;
     k->packed_nodes_gen = nm->generation;
     k->checked_mats = mm;
-    k->checked_mats_gen = mm->generation;
+    k->checked_mats_gen = mm ? mm->generation : ~0ull;
     return RT_SUCCESS;
 }
 
@@ -1031,6 +1039,132 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     return RT_SUCCESS;
 }
 
+// ---- batched ray queries (rt_query.hpp; the plan: rt_query_plan.cpp) ----------------------------
+
+// the query plan's inputs: the range, the two buffers, the kernel's settings and its packed scene
+// (packed false: before the scene is packed -- the range and argument checks only)
+static rtp::QueryIn query_inputs(rt_context ctx, rt_kernel k, rt_mem rays, size_t first_ray, size_t n_rays, int mode,
+                                 rt_mem hits, bool packed) {
+    rtp::QueryIn in{};
+    in.first_ray = first_ray, in.n_rays = n_rays;
+    in.rays_bytes = rays->size, in.hits_bytes = hits->size;
+    in.same_buffer = rays == hits;
+    in.mode = mode;
+    in.oct_ok = true;
+    if (packed) {
+        in.n_nodes = k->n_nodes, in.n_tris = k->n_tris;
+        in.oct_ok = k->oct_ok;
+        in.goct_available = k->goct_nodes != nullptr, in.goct_b = k->goct_b;
+    }
+    in.force_global = k->force_global;
+    in.refill_min = k->query_refill_min;
+    in.w_node = k->w_node, in.w_leaf = k->w_leaf, in.w_node_g = k->w_node_g, in.w_leaf_g = k->w_leaf_g;
+    in.max_blocks = k->max_blocks;
+    in.num_cus = ctx->num_cus;
+    return in;
+}
+
+int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t first_ray, size_t n_rays, int mode,
+                           rt_mem hits) {
+    // 1. the handles and the range: no scene is packed and nothing launched on an error
+    int rc = ensure_device(ctx);
+    if (rc) return rc;
+    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
+    if (!rays || !hits || rays->ctx != ctx || hits->ctx != ctx) return RT_INVALID_MEM_OBJECT;
+    if (ctx->pend_k) {  // another call touches the context: the coalesced frames launch first
+        rc = rti::flush_frames(ctx);
+        if (rc) return pending_error(ctx, rc);
+    }
+    rtp::QueryPlan p;
+    rc = rtp::query_shape(query_inputs(ctx, k, rays, first_ray, n_rays, mode, hits, false), &p);
+    if (rc || p.nothing) return pending_error(ctx, rc);
+    if (!k->set[RT_ARG_BUFFER_SCENE] || !k->set[RT_ARG_BUFFER_NODE]) return RT_INVALID_KERNEL_ARGS;
+    // 2. the scene, packed and validated as a render launch does (materials only when bound)
+    rc = prepare_scene(k, false);
+    if (rc) return rc;
+    // 3. the plan, with the kernel's occupancy at the LDS size it chose
+    const rtp::QueryIn in = query_inputs(ctx, k, rays, first_ray, n_rays, mode, hits, true);
+    rc = rtp::query_shape(in, &p);
+    if (rc || p.nothing) return rc;
+    int& occ = k->query_occ[k->math][p.lds][k->stats][p.bofs][p.any];
+    size_t& at = k->query_occ_smem[k->math][p.lds][k->stats][p.bofs][p.any];
+    if (occ == 0 || at != p.smem) {
+        occ = rtk::occupancy_query(k->math, p.lds, k->stats, p.bofs, p.any, p.smem);
+        at = p.smem;
+    }
+    rtp::query_grid(in, occ, &p);
+    // 4. the arguments
+    rtk::KernelArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.packedTris = k->packed_tris;
+    a.octNodes = p.regrouped ? k->goct_nodes : k->oct_nodes;
+    a.nTris = k->n_tris;
+    a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords;
+    a.stepWeightNode = p.stepWeightNode, a.stepWeightLeaf = p.stepWeightLeaf;
+    a.stats = k->dstats;
+    rtk::QueryArgs q{};
+    q.rays = static_cast<const float4*>(rays->dptr);
+    q.hits = static_cast<float4*>(hits->dptr);
+    q.first = p.first, q.count = p.count, q.nUnits = p.nUnits, q.refillMin = p.refillMin;
+    // 5. the launch, on the context's stream after the pending accumulations and gathers
+    hipStream_t st = qs(ctx);
+    k->last_lds = p.lds;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (k->timing) {
+        ev0 = take_event(k);
+        ev1 = take_event(k);
+        if (!ev0 || !ev1) return RT_OUT_OF_RESOURCES;
+        (void)hipEventRecord(ev0, st);
+    }
+    const hipError_t e = rtk::launch_query(a, q, k->math, p.lds, k->stats, p.bofs, p.any, p.grid, p.smem, st);
+    if (e != hipSuccess) return map_hip(e);
+    if (k->timing) {
+        (void)hipEventRecord(ev1, st);
+        k->pending_events.emplace_back(ev0, ev1);
+    }
+    hits->shadow_valid = false;  // device contents changed
+    ++hits->generation;
+    if (k->pending_events.size() + k->pending_accum.size() > 4096) {
+        rc = drain_events(k);
+        if (rc) return rc;
+    }
+    ++k->launches;
+    return pending_error(ctx, RT_SUCCESS);
+}
+
+int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem rays) {
+    int rc = ensure_device(ctx);
+    if (rc) return rc;
+    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
+    if (!rays || rays->ctx != ctx) return RT_INVALID_MEM_OBJECT;
+    if (ctx->pend_k) {  // another call touches the context: the coalesced frames launch first
+        rc = rti::flush_frames(ctx);
+        if (rc) return pending_error(ctx, rc);
+    }
+    for (int i : {RT_ARG_WIDTH, RT_ARG_HEIGHT, RT_ARG_FRAME_COUNT, RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT,
+                  RT_ARG_CAMERA_UP})
+        if (!k->set[i]) return RT_INVALID_KERNEL_ARGS;
+    if (global_work_size == 0 || global_work_size > 0xffffffffull) return RT_INVALID_GLOBAL_WORK_SIZE;
+    rtk::KernelArgs a;
+    std::memset(&a, 0, sizeof(a));
+    std::memcpy(&a.width, &k->u32[RT_ARG_WIDTH], 4);
+    std::memcpy(&a.height, &k->u32[RT_ARG_HEIGHT], 4);
+    std::memcpy(&a.frameCount, &k->u32[RT_ARG_FRAME_COUNT], 4);
+    if (a.width == 0 || a.height == 0) return RT_INVALID_KERNEL_ARGS;
+    if (rays->size / sizeof(rt_ray) < global_work_size) return RT_INVALID_BUFFER_SIZE;
+    for (int i = 0; i < 3; ++i) {
+        a.camPos[i] = k->f3[0][i];
+        a.camFront[i] = k->f3[1][i];
+        a.camUp[i] = k->f3[2][i];
+    }
+    const hipError_t e =
+        rtk::launch_camera_rays(a, static_cast<float4*>(rays->dptr), (uint32_t)global_work_size, k->math, qs(ctx));
+    if (e != hipSuccess) return map_hip(e);
+    rays->shadow_valid = false;  // device contents changed
+    ++rays->generation;
+    return pending_error(ctx, RT_SUCCESS);
+}
+
 int rtBuildBVH(rt_context ctx, rt_mem tris, size_t n_tris, unsigned max_prims_in_node, rt_mem nodes,
                size_t* n_nodes) {
     return rtBuildBVHEx(ctx, tris, n_tris, max_prims_in_node, RT_BVH_PLOC, nodes, n_nodes);
@@ -1391,6 +1525,7 @@ int rtKernelSetTuning(rt_kernel k, int param, int value) {
         case RT_TUNE_PERFRAME_BATCH: if (!in(1, (int)rtk::kMaxFusedFrames)) return RT_INVALID_VALUE; k->pf_batch = (uint32_t)value; break;
         case RT_TUNE_STEP_WEIGHT_NODE_GLOBAL: if (!in(0, 1000)) return RT_INVALID_VALUE; k->w_node_g = (uint32_t)value; break;
         case RT_TUNE_STEP_WEIGHT_LEAF_GLOBAL: if (!in(0, 1000)) return RT_INVALID_VALUE; k->w_leaf_g = (uint32_t)value; break;
+        case RT_TUNE_QUERY_REFILL_MIN: if (!in(1, 64)) return RT_INVALID_VALUE; k->query_refill_min = (uint32_t)value; break;
         default: return RT_INVALID_VALUE;
     }
     return RT_SUCCESS;
@@ -1422,6 +1557,7 @@ int rtKernelGetTuning(rt_kernel k, int param, int* value) {
         case RT_TUNE_PERFRAME_BATCH: *value = (int)k->pf_batch; break;
         case RT_TUNE_STEP_WEIGHT_NODE_GLOBAL: *value = (int)k->w_node_g; break;
         case RT_TUNE_STEP_WEIGHT_LEAF_GLOBAL: *value = (int)k->w_leaf_g; break;
+        case RT_TUNE_QUERY_REFILL_MIN: *value = (int)k->query_refill_min; break;
         default: return RT_INVALID_VALUE;
     }
     return RT_SUCCESS;

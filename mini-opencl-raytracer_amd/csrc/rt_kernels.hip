@@ -182,6 +182,37 @@ int occupancy_wf_shade(int math, bool stats) {
     return blocks > 0 ? blocks : 1;
 }
 
+// ---- ray queries (rt_query.hpp) ------------------------------------------------------------------
+static QueryKernelFn pick_query(int math, bool lds, bool stats, bool bofs, bool any) {
+    if (math == MathShipped::kId) return pick_query_shipped(lds, stats, bofs, any);
+    if (math == MathDeviceLib::kId) return query_pick<MathDeviceLib>(lds, stats, bofs, any);
+    return query_pick<MathPinned>(lds, stats, bofs, any);
+}
+
+hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, int math, bool lds, bool stats, bool bofs, bool any,
+                        unsigned grid, size_t smem, hipStream_t st) {
+    hipLaunchKernelGGL(pick_query(math, lds, stats, lds && bofs, any), dim3(grid), dim3(kQueryThreads), smem, st, a, q);
+    return hipGetLastError();
+}
+
+int occupancy_query(int math, bool lds, bool stats, bool bofs, bool any, size_t smem) {
+    int blocks = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, pick_query(math, lds, stats, lds && bofs, any),
+                                                     kQueryThreads, smem) != hipSuccess)
+        return 1;
+    return blocks > 0 ? blocks : 1;
+}
+
+hipError_t launch_camera_rays(const KernelArgs& a, float4* rays, uint32_t n, int math, hipStream_t st) {
+    if (math == MathShipped::kId) return launch_camera_rays_shipped(a, rays, n, st);
+    const dim3 grid((unsigned)(((uint64_t)n + 255u) / 256u));
+    if (math == MathDeviceLib::kId)
+        hipLaunchKernelGGL(camera_rays<MathDeviceLib>, grid, dim3(256), 0, st, a, rays, n);
+    else
+        hipLaunchKernelGGL(camera_rays<MathPinned>, grid, dim3(256), 0, st, a, rays, n);
+    return hipGetLastError();
+}
+
 // rtDiagPinnedMath: the pinned policy's builtins, element-wise (tests)
 __global__ void pinned_math_kernel(int op, const float* __restrict__ a, const float* __restrict__ b,
                                    float* __restrict__ out, size_t n) {

@@ -99,6 +99,26 @@ int occupancy_wf_extend(int math, bool lds, bool stats, bool bofs, size_t smem, 
 int occupancy_wf_shade(int math, bool stats);
 WfKernels pick_wf_shipped(bool lds, bool stats, bool bofs, bool goct);
 
+// ---- ray queries (rt_query.hpp) ------------------------------------------------------------------
+// rtEnqueueIntersectRays: KernelArgs carries the packed scene (packedTris, octNodes, nNodes, nTris,
+// octStride, octB, octRecords), the step weights and the stats pointer; the rest is unused.
+struct QueryArgs {
+    const float4* rays;       // rt_ray records as 2 x float4: {origin, tmin}, {dir, tmax}
+    float4* hits;             // rt_ray_hit records: {prim bits, t, u, v}
+    uint32_t first, count;    // the range [first, first + count) of both arrays
+    uint32_t nUnits;          // 64-ray units of the range (the last one may be partial)
+    uint32_t refillMin;       // take new rays once this many lanes are free
+};
+using QueryKernelFn = void (*)(KernelArgs, QueryArgs);
+// lds: scene staged in LDS (bofs: B planes at kOctB), else octant records and triangles in HBM/L2
+hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, int math, bool lds, bool stats, bool bofs, bool any,
+                        unsigned grid, size_t smem, hipStream_t st);
+int occupancy_query(int math, bool lds, bool stats, bool bofs, bool any, size_t smem);
+QueryKernelFn pick_query_shipped(bool lds, bool stats, bool bofs, bool any);
+// rtEnqueueCameraRays: width, height, frameCount and the camera slots of `a`; one rt_ray per work-item
+hipError_t launch_camera_rays(const KernelArgs& a, float4* rays, uint32_t n, int math, hipStream_t st);
+hipError_t launch_camera_rays_shipped(const KernelArgs& a, float4* rays, uint32_t n, hipStream_t st);
+
 // goct (step schedule, scene not in LDS): walk the octant records in HBM/L2 instead of the
 // 64-B global node records
 hipError_t launch_kernel_entry(const KernelArgs& a, int sched, int math, bool lds, bool stats, unsigned grid,

@@ -97,9 +97,10 @@ __device__ __forceinline__ Ray init_ray(F3 o, F3 d) {
 
 // kernel_bvh.cl:386-403
 // (px, py) = (gid % W, gid / W), passed in by the callers that already know them.
+// camera_dir: the direction CreateRay hands to InitRay (its normalize(dir)); create_ray: the ray.
 template <class M>
-__device__ __forceinline__ Ray create_ray(uint32_t px, uint32_t py, uint32_t W, uint32_t H, F3 pos, F3 front,
-                                          F3 up, float angle, uint32_t& seed) {
+__device__ __forceinline__ F3 camera_dir(uint32_t px, uint32_t py, uint32_t W, uint32_t H, F3 front, F3 up,
+                                         float angle, uint32_t& seed) {
     const float invW = M::rcp((float)W);
     const float invH = M::rcp((float)H);
     const float aspect = M::div((float)W, (float)H);
@@ -109,7 +110,12 @@ __device__ __forceinline__ Ray create_ray(uint32_t px, uint32_t py, uint32_t W, 
     y = -(1.0f - 2.0f * ((y + 0.5f) * invH)) * angle;
     // (2*A - 1 and 1 - 2*B contract to the same bits: 2*A is exact)
     F3 dir = madd<M>(M::cross(front, up), x, up * y) + front;
-    return init_ray<M>(pos, normalize<M>(dir));
+    return normalize<M>(dir);
+}
+template <class M>
+__device__ __forceinline__ Ray create_ray(uint32_t px, uint32_t py, uint32_t W, uint32_t H, F3 pos, F3 front,
+                                          F3 up, float angle, uint32_t& seed) {
+    return init_ray<M>(pos, camera_dir<M>(px, py, W, H, front, up, angle, seed));
 }
 
 // ---- scene access ------------------------------------------------------------------------
@@ -1828,3 +1834,4 @@ __device__ __forceinline__ void material_record(const rt_cl_material& m, float4*
 }  // namespace rtk
 
 #include "rt_wavefront.hpp"
+#include "rt_query.hpp"

@@ -79,6 +79,16 @@ WfKernels pick_wf_shipped(bool lds, bool stats, bool bofs, bool goct) {
     return wf_pick<MathShipped>(lds, stats, bofs, goct);
 }
 
+QueryKernelFn pick_query_shipped(bool lds, bool stats, bool bofs, bool any) {
+    return query_pick<MathShipped>(lds, stats, bofs, any);
+}
+
+hipError_t launch_camera_rays_shipped(const KernelArgs& a, float4* rays, uint32_t n, hipStream_t st) {
+    hipLaunchKernelGGL(camera_rays<MathShipped>, dim3((unsigned)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, st, a,
+                       rays, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_pack_mats_shipped(const rt_cl_material* mats, uint32_t n_mats, float4* pm, hipStream_t st) {
     hipLaunchKernelGGL(pack_mats_shipped, dim3((n_mats + 255) / 256), dim3(256), 0, st, mats, pm, n_mats);
     return hipGetLastError();

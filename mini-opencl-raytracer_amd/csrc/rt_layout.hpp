@@ -45,4 +45,8 @@ constexpr unsigned kWfShadeThreads = 256;   // shade workgroup: one stream, 256 
 constexpr int kWfMaxBounces = 64;            // longer bounce loops run the step schedule
 constexpr uint32_t kWfRingBytes = 64u * 32u;  // extend: per-wave ray ring ({o, position}, {d, -})
 
+// ---- ray queries (rt_query.hpp) ----
+constexpr unsigned kQueryThreads = 512;          // query workgroup: 8 waves (LDS scene staged once per 8)
+constexpr uint32_t kQueryRingBytes = 64u * 32u;  // per-wave ring of 64 rt_ray records
+
 }  // namespace rtk

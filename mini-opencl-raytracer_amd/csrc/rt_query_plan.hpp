@@ -1,0 +1,60 @@
+// rt_query_plan.hpp -- how one ray query (rtEnqueueIntersectRays) is launched, as a pure function
+// of plain values (rt_query_plan.cpp): no HIP, no allocation, no globals.  The C ABI fills a
+// QueryIn, calls query_shape, looks the kernel's occupancy up for the LDS size that gives, and
+// calls query_grid.  The render's plan (rt_launch_plan.hpp) is separate and untouched.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+namespace rtp {
+
+constexpr int kQueryClosest = 0, kQueryAny = 1;      // RT_QUERY_CLOSEST, RT_QUERY_ANY
+constexpr uint64_t kQueryMaxRays = 1ull << 31;       // first + n_rays at most (ray indices are 32-bit)
+constexpr size_t kQueryLdsBudget = 64 * 1024;        // per-workgroup LDS of the LDS scene path, rings included
+
+struct QueryIn {
+    uint64_t first_ray, n_rays;          // the range [first_ray, first_ray + n_rays)
+    uint64_t rays_bytes, hits_bytes;     // sizes of the two buffers
+    bool same_buffer;                    // rays and hits are one buffer
+    int mode;                            // RT_QUERY_*
+    uint32_t n_nodes, n_tris;            // the packed scene
+    bool oct_ok;                         // every leaf fits the octant records
+    bool goct_available;                 // regrouped octant records exist ...
+    uint32_t goct_b;                     // ... and their B planes' float4 offset
+    bool force_global;
+    uint32_t refill_min;                 // RT_TUNE_QUERY_REFILL_MIN
+    uint32_t w_node, w_leaf, w_node_g, w_leaf_g;  // step weights (the render's tuning)
+    int max_blocks;                      // RT_TUNE_MAX_BLOCKS
+    int num_cus;
+};
+
+struct QueryPlan {
+    bool nothing;                        // n_rays == 0: RT_SUCCESS, no launch
+    // ---- query_shape ----
+    bool lds, bofs, any;                 // scene staged in LDS (B planes at kOctB); any-hit
+    bool regrouped;                      // HBM/L2 path: walk the regrouped octant records
+    size_t smem;                         // dynamic LDS bytes
+    uint32_t first, count;               // the range, 32-bit
+    uint32_t nUnits;                     // 64-ray units: unit j = rays first + 64 j .. (the last one may be partial)
+    uint32_t octStride, octB, octRecords, nNodes;
+    uint32_t refillMin, stepWeightNode, stepWeightLeaf;
+    // ---- query_grid ----
+    uint32_t grid;                       // workgroups of kQueryThreads; unit j goes to wave j % (8 grid)
+};
+
+// Everything up to the LDS size.  RT_SUCCESS (out->nothing set when n_rays == 0 and the mode is
+// valid), or, in this order: RT_INVALID_VALUE (mode; first_ray + n_rays > 2^31), RT_INVALID_MEM_OBJECT (one buffer for
+// rays and hits), RT_INVALID_BUFFER_SIZE (the range ends beyond either buffer),
+// RT_INVALID_OPERATION (a leaf of more than 127 triangles: no octant records to walk).
+int query_shape(const QueryIn& in, QueryPlan* out);
+// The grid, from the occupancy (workgroups per CU) of the kernel query_shape chose at out->smem.
+void query_grid(const QueryIn& in, int occ, QueryPlan* out);
+
+inline int query_plan(const QueryIn& in, int occ, QueryPlan* out) {
+    const int rc = query_shape(in, out);
+    if (rc == 0 && !out->nothing) query_grid(in, occ, out);
+    return rc;
+}
+
+}  // namespace rtp
