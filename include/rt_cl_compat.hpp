@@ -96,6 +96,14 @@ public:
     inline void IntersectRays(std::shared_ptr<CLKernel> kernel, const Buffer& rays, const Buffer& hits, size_t nRays,
                               int mode = RT_QUERY_CLOSEST, size_t firstRay = 0) const;
     inline void CameraRays(std::shared_ptr<CLKernel> kernel, size_t workSize, const Buffer& rays) const;
+    // extensions: moving geometry (rtEnqueueUpdateVertices, rtRefitBVH); normals may be null
+    void UpdateVertices(const Buffer& tris, size_t firstTri, size_t nTris, const Buffer& positions,
+                        const Buffer* normals = nullptr) const {
+        check(rtEnqueueUpdateVertices(ctx_, tris.get(), firstTri, nTris, positions.get(),
+                                      normals ? normals->get() : nullptr),
+              "Failed to update vertices");
+    }
+    inline void RefitBVH(std::shared_ptr<CLKernel> kernel) const;
     void Finish() const { check(rtFinish(ctx_), "Failed to finish queue"); }
     rt_context GetContext() const { return ctx_; }
 
@@ -141,6 +149,9 @@ inline void CLContext::IntersectRays(std::shared_ptr<CLKernel> kernel, const Buf
 }
 inline void CLContext::CameraRays(std::shared_ptr<CLKernel> kernel, size_t workSize, const Buffer& rays) const {
     check(rtEnqueueCameraRays(ctx_, kernel->GetKernel(), workSize, rays.get()), "Failed to enqueue camera rays");
+}
+inline void CLContext::RefitBVH(std::shared_ptr<CLKernel> kernel) const {
+    check(rtRefitBVH(ctx_, kernel->GetKernel()), "Failed to refit BVH");
 }
 
 }  // namespace rtcl

@@ -24,6 +24,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rt_cl_types.h"
 #include "rt_status.h"
 
 #ifdef __cplusplus
@@ -267,6 +268,50 @@ typedef struct rt_ray_hit {
 int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t first_ray, size_t n_rays, int mode,
                            rt_mem hits);
 int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem rays);
+
+/* ---- moving geometry: vertex update + device-side BVH refit (extension) ----
+ * For a mesh whose triangles move while the tree's shape stays put.  Both enqueue calls are
+ * asynchronous on the context's in-order queue and never wait on the host: they launch the
+ * coalesced per-frame launches first, run after every render, accumulation and query enqueued so
+ * far, and later launches and queries see the new geometry.
+ *
+ * rtEnqueueUpdateVertices overwrites v1/v2/v3.position.xyz (and, when `normals` is non-NULL,
+ * v*.normal.xyz) of triangles [first_tri, first_tri + n_tris) of `tris` from records [0, n_tris)
+ * of `positions` / `normals` (rt_tri_points, 48 B; the w slots are ignored).  Indices are the
+ * triangle buffer's own (BVH leaf order).  Nothing else in a record is touched.
+ *
+ * rtRefitBVH recomputes the bounds of the tree bound to k (BUFFER_NODE) from the triangles bound
+ * to k (BUFFER_SCENE), writes them into the node buffer's CLLinearBVHNode records and into every
+ * derived record k holds, and repacks k's triangle / shading records.  Topology, axis flags, leaf
+ * ranges, the records past the tree's end and every non-bounds byte of a node record (the w slots
+ * of pmin / pmax included) stay as they are.
+ *   Bounds rule: a leaf's box is the fminf / fmaxf fold (from +inf / -inf) over the nine position
+ * coordinates of each of its triangles, read from the 256-B records; an interior box is the fminf /
+ * fmaxf of its two children's.  So a NaN coordinate is ignored and an infinity kept.  The sign of
+ * a zero bound is unspecified: the slab test cannot tell, since 0 * inf is NaN for either sign and
+ * every other comparison treats +0 and -0 alike.  rtsRefitBounds (rt_scene.h) is the same rule on
+ * host arrays.
+ *   Safety: a refit never validates, so it may only follow changes that cannot alter topology or
+ * material indices.  Every buffer keeps a second, "structural" generation that every writer but
+ * these two calls bumps (rtEnqueueWriteBuffer, rtBuildBVH, rect copies, ray / hit outputs).  When
+ * k was never prepared, or the structural generation of its triangle or node buffer is not the one
+ * k packed, rtRefitBVH first runs the ordinary host-side preparation of a launch (read-back,
+ * rtValidateBVH, packing: RT_INVALID_MEM_OBJECT on a malformed tree), then refits; otherwise
+ * nothing leaves the device and the next launch finds k's packed scene current.  Other kernels
+ * bound to the same buffers see a changed generation and prepare in full at their next launch.
+ * The material buffer is checked and packed when bound and not required (a kernel used for
+ * queries only refits without one).
+ *   Errors (nothing is launched): scene or node slot unbound RT_INVALID_KERNEL_ARGS; a buffer of
+ * another context or NULL (`normals` excepted) RT_INVALID_MEM_OBJECT; `positions` or `normals` the
+ * same buffer as `tris` RT_INVALID_MEM_OBJECT; first_tri + n_tris beyond `tris`, or `positions` /
+ * `normals` smaller than 48 * n_tris, RT_INVALID_BUFFER_SIZE.  n_tris == 0: RT_SUCCESS, no launch.
+ * The caller restarts a progressive accumulation, as after a camera move. */
+typedef struct rt_tri_points { rt_float3 p1, p2, p3; } rt_tri_points; /* 48 B, w ignored */
+int rtEnqueueUpdateVertices(rt_context ctx, rt_mem tris, size_t first_tri, size_t n_tris, rt_mem positions,
+                            rt_mem normals /* may be NULL */);
+int rtRefitBVH(rt_context ctx, rt_kernel k);
+/* counts since kernel creation: full host-side scene preparations, device refits */
+int rtDiagScenePrepares(rt_kernel k, uint64_t* full, uint64_t* refits);
 
 /* Where the scene lives: 1 = staged in LDS (when it fits), 0 = read from HBM/L2. */
 int rtKernelGetSceneInLDS(rt_kernel k, int* in_lds);

@@ -53,6 +53,17 @@ int rtsGetTreeStats(const rt_scene* s, unsigned* max_depth, unsigned* n_leaves,
 int rtsFromArrays(const rt_cl_triangle* tris, size_t n_tris, const rt_cl_bvh_node* nodes, size_t n_nodes,
                   const rt_cl_material* mats, size_t n_mats, unsigned max_prims_in_node, rt_scene** out);
 
+/* Refit on host arrays, for geometry that moved under an unchanged tree: rewrites pmin/pmax.xyz of
+ * the tree's nodes in place by the bounds rule of rtRefitBVH (rt_hip.h) -- a leaf's box is the
+ * fminf / fmaxf fold, from +inf / -inf, over the nine position coordinates of each of its triangles
+ * (a NaN coordinate is ignored, an infinity kept), an interior box the fminf / fmaxf of its two
+ * children's; the sign of a zero bound is unspecified.  The tree is validated first as rtValidateBVH
+ * validates it (the prefix of `nodes` that node 0's chain of second children ends; children i + 1 and
+ * offset > i + 1 inside it, leaf ranges inside the n_tris triangles, one parent per node):
+ * RT_INVALID_VALUE and nothing written otherwise.  Records past the tree's end, the w slots and every
+ * non-bounds byte stay as they are. */
+int rtsRefitBounds(const rt_cl_triangle* tris, size_t n_tris, rt_cl_bvh_node* nodes, size_t n_nodes);
+
 /* Binary scene cache: the three device arrays exactly as built, so a large
  * OBJ is parsed and its BVH built once.  Format: "RTSCENE1", u32 version, u32
  * maxPrimitivesInNode, u64 triangle / node / material counts, the raw arrays, u64 FNV-1a of

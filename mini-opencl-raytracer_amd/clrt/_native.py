@@ -67,6 +67,9 @@ RAY_DTYPE = np.dtype([("origin", np.float32, (3,)), ("tmin", np.float32), ("dir"
 RAY_HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32)])
 assert RAY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 16
 QUERY_CLOSEST, QUERY_ANY = 0, 1
+# rt_tri_points (rt_hip.h): the records of rtEnqueueUpdateVertices, three float3 slots (w ignored)
+TRI_POINTS_DTYPE = np.dtype([("p1", FLOAT3), ("p2", FLOAT3), ("p3", FLOAT3)])
+assert TRI_POINTS_DTYPE.itemsize == 48
 
 # RenderKernelArgument_t (CLutils.h:11-27)
 BUFFER_OUT, BUFFER_SCENE, BUFFER_NODE, BUFFER_MATERIAL = 0, 1, 2, 3
@@ -137,6 +140,9 @@ _HIP_PROTOS = {
     "rtEnqueueKernelFrames": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint]),
     "rtEnqueueIntersectRays": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, _vp]),
     "rtEnqueueCameraRays": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp]),
+    "rtEnqueueUpdateVertices": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
+    "rtRefitBVH": (ctypes.c_int, [_vp, _vp]),
+    "rtDiagScenePrepares": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "rtEnqueueReadBuffer": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtEnqueueWriteBuffer": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtFinish": (ctypes.c_int, [_vp]),
@@ -205,6 +211,7 @@ _SCENE_PROTOS = {
                                        ctypes.POINTER(ctypes.c_uint)]),
     "rtsFromArrays": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
                                      ctypes.c_uint, ctypes.POINTER(_vp)]),
+    "rtsRefitBounds": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t]),
     "rtsSaveScene": (ctypes.c_int, [_vp, ctypes.c_char_p]),
     "rtsLoadScene": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_vp)]),
     "rtsRelease": (None, [_vp]),

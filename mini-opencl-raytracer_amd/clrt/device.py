@@ -92,6 +92,19 @@ class CLContext:
         check(self._lib.rtEnqueueCameraRays(self.handle, kernel.handle, int(work_size), rays.handle),
               "Failed to enqueue camera rays")
 
+    def UpdateVertices(self, tris: "Buffer", first: int, n: int, positions: "Buffer",
+                       normals: "Buffer | None" = None) -> None:
+        """rtEnqueueUpdateVertices: the position (and normal) xyz of triangles [first, first + n) of `tris`
+        from records [0, n) of `positions` / `normals` (N.TRI_POINTS_DTYPE); asynchronous."""
+        check(self._lib.rtEnqueueUpdateVertices(self.handle, tris.handle, int(first), int(n), positions.handle,
+                                                normals.handle if normals is not None else None),
+              "Failed to update vertices")
+
+    def RefitBVH(self, kernel: "CLKernel") -> None:
+        """rtRefitBVH: the bounds of the tree bound to `kernel` from its triangles, on the device, into the
+        node buffer and every record the kernel packed; asynchronous.  Topology stays."""
+        check(self._lib.rtRefitBVH(self.handle, kernel.handle), "Failed to refit BVH")
+
     def Finish(self) -> None:
         check(self._lib.rtFinish(self.handle), "Failed to finish queue")
 
@@ -238,6 +251,13 @@ class CLKernel:
                 "sched": dict(zip(("node_steps", "node_lanes", "tri_steps", "tri_lanes", "shade_rounds",
                                    "shade_lanes", "refill_rounds", "refill_lanes", "other_lanes",
                                    "shade_wait", "free_wait", "reserved"), list(s.sched)))}
+
+    def scene_prepares(self) -> tuple:
+        """rtDiagScenePrepares: (full host-side scene preparations, device refits) since creation."""
+        full, refits = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.rtDiagScenePrepares(self.handle, ctypes.byref(full), ctypes.byref(refits)),
+              "scene prepares")
+        return int(full.value), int(refits.value)
 
     def reset_stats(self) -> None:
         check(self._lib.rtKernelResetStats(self.handle), "reset stats")

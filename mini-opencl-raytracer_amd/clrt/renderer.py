@@ -46,6 +46,8 @@ class Raytracer:
         self.pixels = np.zeros((self.height * self.width, 4), np.float32)
         self._scene_bufs: list = []
         self._cast_bufs: tuple | None = None  # (capacity in rays, ray buffer, hit buffer) of cast()
+        self._move_bufs: tuple | None = None  # (capacity in triangles, positions, normals) of move_vertices()
+        self._move_keep: list = []            # host arrays of uploads still in the queue
 
     # CLRaytracer::Init (CLRaytracer.cpp:104-120)
     def Init(self) -> None:
@@ -64,8 +66,10 @@ class Raytracer:
     # CLBVHScene::SetupBuffers (CLBVHnode.cpp:209-236)
     def upload_scene(self, scene: Scene) -> None:
         flags = N.MEM_READ_ONLY | N.MEM_COPY_HOST_PTR
-        tb = self.ctx.create_buffer(flags, scene.triangles.nbytes, scene.triangles)
-        nb = self.ctx.create_buffer(flags, scene.nodes.nbytes, scene.nodes)
+        # (triangles and nodes read-write: move_vertices updates and refits them on the device)
+        rw = N.MEM_READ_WRITE | N.MEM_COPY_HOST_PTR
+        tb = self.ctx.create_buffer(rw, scene.triangles.nbytes, scene.triangles)
+        nb = self.ctx.create_buffer(rw, scene.nodes.nbytes, scene.nodes)
         mb = self.ctx.create_buffer(flags, scene.materials.nbytes, scene.materials)
         for old in self._scene_bufs:
             old.release()
@@ -94,6 +98,7 @@ class Raytracer:
         if self.read_back:
             self.ctx.ReadBuffer(self.output, self.pixels, 16 * work)
         self.ctx.Finish()
+        self._move_keep.clear()
         self.frame_count += 1
 
     def cast(self, origins, dirs, tmin=-np.inf, tmax=100000.0, any_hit: bool = False) -> np.ndarray:
@@ -123,6 +128,53 @@ class Raytracer:
         self.ctx.IntersectRays(self.kernel, rb, hb, n, N.QUERY_ANY if any_hit else N.QUERY_CLOSEST)
         self.ctx.ReadBuffer(hb, hits, blocking=True)
         return hits
+
+    def move_vertices(self, positions, normals=None, first: int = 0) -> None:
+        """Move triangles [first, first + n) of the uploaded scene and refit its BVH on the device
+        (rtEnqueueUpdateVertices + rtRefitBVH; nothing waits on the host).  `positions` -- and `normals`
+        when given -- are (n, 3, 3) arrays (triangle, vertex, xyz) or n N.TRI_POINTS_DTYPE records, in
+        the uploaded triangle order (BVH leaf order).  The tree's topology stays: a caller whose tree has
+        degraded after large deformations builds a new one.  The output buffer still holds the frames
+        accumulated from the old geometry: the caller restarts the progressive accumulation (frame_count
+        = 1), as the reference does on a camera move.  The device buffers are kept and reused."""
+        recs = [self._tri_points(positions)]
+        if normals is not None:
+            recs.append(self._tri_points(normals))
+            if len(recs[1]) != len(recs[0]):
+                raise ValueError("positions and normals differ in length")
+        n = len(recs[0])
+        if n == 0:
+            return
+        if self._move_bufs is None or self._move_bufs[0] < n:
+            if self._move_bufs:
+                self._move_bufs[1].release()
+                self._move_bufs[2].release()
+            size = n * N.TRI_POINTS_DTYPE.itemsize
+            self._move_bufs = (n, self.ctx.create_buffer(N.MEM_READ_WRITE, size),
+                               self.ctx.create_buffer(N.MEM_READ_WRITE, size))
+        _, pb, nb = self._move_bufs
+        self.ctx.WriteBuffer(pb, recs[0], blocking=False)
+        if normals is not None:
+            self.ctx.WriteBuffer(nb, recs[1], blocking=False)
+        self.ctx.UpdateVertices(self._scene_bufs[0], first, n, pb, nb if normals is not None else None)
+        self.ctx.RefitBVH(self.kernel)
+        # the staging arrays must outlive the asynchronous uploads: kept until the queue is next
+        # known to be drained (RenderFrame's Finish; after a few moves without one, a Finish here)
+        self._move_keep.extend(recs)
+        if len(self._move_keep) > 8:
+            self.ctx.Finish()
+            self._move_keep.clear()
+
+    @staticmethod
+    def _tri_points(a) -> np.ndarray:
+        a = np.asarray(a)
+        if a.dtype == N.TRI_POINTS_DTYPE:
+            return np.ascontiguousarray(a)
+        a = np.asarray(a, np.float32).reshape(-1, 3, 3)
+        out = np.zeros(len(a), N.TRI_POINTS_DTYPE)
+        for i, f in enumerate(("p1", "p2", "p3")):
+            out[f][:, :3] = a[:, i]
+        return out
 
     def image(self) -> np.ndarray:
         """Last read-back frame as (H, W, 3); row 0 is the bottom row (GL order)."""
@@ -162,6 +214,11 @@ class Raytracer:
             self._cast_bufs[1].release()
             self._cast_bufs[2].release()
             self._cast_bufs = None
+        if self._move_bufs:
+            self._move_bufs[1].release()
+            self._move_bufs[2].release()
+            self._move_bufs = None
+        self._move_keep = []
         if self.output:
             self.output.release()
         if self.kernel:

@@ -116,6 +116,18 @@ def build_bvh_device(triangles: np.ndarray, materials: np.ndarray, max_prims_in_
     return Scene(out_t, out_n, np.ascontiguousarray(materials, dtype=MATERIAL_DTYPE), max_prims_in_node)
 
 
+def refit(scene: Scene) -> Scene:
+    """rtsRefitBounds: a Scene with the same triangles, materials and tree whose node bounds are
+    recomputed from the triangles (leaves fold their vertices with fminf / fmaxf, interior nodes their
+    two children) -- for geometry that moved under an unchanged topology.  The input is not modified;
+    RTError(CL_INVALID_VALUE) on a malformed tree."""
+    lib = scene_lib()
+    t = np.ascontiguousarray(scene.triangles, dtype=TRIANGLE_DTYPE)
+    n = np.array(scene.nodes, dtype=NODE_DTYPE, order="C", copy=True)
+    check(lib.rtsRefitBounds(t.ctypes.data, t.shape[0], n.ctypes.data, n.shape[0]), "rtsRefitBounds")
+    return Scene(scene.triangles, n, scene.materials, scene.max_prims_in_node)
+
+
 def save_scene(scene: Scene, path: str) -> None:
     """Binary scene cache (rtsSaveScene): the three arrays exactly as built."""
     lib = scene_lib()

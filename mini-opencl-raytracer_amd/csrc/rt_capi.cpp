@@ -31,6 +31,7 @@
 #include "rt_kernels.hpp"
 #include "rt_launch_plan.hpp"
 #include "rt_query_plan.hpp"
+#include "rt_refit.hpp"
 #include "rt_scene_pack.hpp"
 
 namespace {
@@ -136,6 +137,15 @@ struct rt_kernel_s {
     // derived packed scene
     rt_mem packed_for_tris = nullptr, packed_for_nodes = nullptr, checked_mats = nullptr;
     uint64_t packed_tris_gen = ~0ull, packed_nodes_gen = ~0ull, checked_mats_gen = ~0ull;
+    // the buffers' structural generations at the last full preparation (rtRefitBVH)
+    uint64_t packed_tris_struct = ~0ull, packed_nodes_struct = ~0ull;
+    // device refit (rt_refit.hip): node -> parent, then node -> g_nodes record (n_nodes words each),
+    // uploaded by the full preparation; the climb's arrival counters
+    uint32_t* refit_links = nullptr;
+    uint32_t* refit_arrivals = nullptr;
+    size_t refit_links_cap = 0, refit_arrivals_cap = 0;
+    bool goct_built = false;           // goct_nodes holds this scene's records
+    uint64_t full_prepares = 0, refits = 0;  // rtDiagScenePrepares
     float4* packed_tris = nullptr;
     float4* oct_nodes = nullptr;       // [node][octant] 2 x float4 (LDS-resident scenes)
     float4* goct_nodes = nullptr;      // regrouped octant records for the HBM/L2 walk (RT_GOCT_GROUP)
@@ -254,12 +264,23 @@ int prepare_scene(rt_kernel k, bool need_mats = true) {
     if (nn >= (1u << 30)) return RT_INVALID_MEM_OBJECT;  // node indices share a word with the axis
     std::vector<uint32_t> gn;
     uint32_t n_top = 0;
-    build_global_nodes(reinterpret_cast<const rt_cl_bvh_node*>(nb), nn, skips, k->top_limit, gn, &n_top);
+    // (links: what the device refit needs beside the node buffer -- parent links, then each node's
+    // renumbered record in g_nodes)
+    std::vector<uint32_t> slot_of, links;
+    build_global_nodes(reinterpret_cast<const rt_cl_bvh_node*>(nb), nn, skips, k->top_limit, gn, &n_top, &slot_of);
+    rtp::build_refit_links(reinterpret_cast<const rt_cl_bvh_node*>(nb), nn, slot_of, links);
     rc = ensure_dev(k->g_nodes, k->g_nodes_cap, (size_t)nn * 4);
+    if (rc) return rc;
+    rc = ensure_dev(k->refit_links, k->refit_links_cap, (size_t)nn * 2);
+    if (rc) return rc;
+    rc = ensure_dev(k->refit_arrivals, k->refit_arrivals_cap, (size_t)nn);
     if (rc) return rc;
     {
         hipError_t e = hipMemcpyAsync(k->g_nodes, gn.data(), gn.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                                       qs(k->ctx));
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(k->refit_links, links.data(), links.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               qs(k->ctx));
         if (e != hipSuccess) return map_hip(e);
     }
     std::vector<uint32_t> oct;
@@ -273,6 +294,7 @@ int prepare_scene(rt_kernel k, bool need_mats = true) {
         if (e != hipSuccess) return map_hip(e);
     }
     k->goct_b = 0;
+    k->goct_built = false;
     if (RT_GOCT_GROUP && oct_ok && (uint64_t)(nn + RT_GOCT_GROUP) * 8u < kLeafMin) {
         std::vector<uint32_t> nm;
         build_oct_nodes_grouped(oct, nn, RT_GOCT_GROUP, nm, &k->goct_b);
@@ -282,6 +304,7 @@ int prepare_scene(rt_kernel k, bool need_mats = true) {
                                       qs(k->ctx));
         if (e == hipSuccess) e = hipStreamSynchronize(qs(k->ctx));
         if (e != hipSuccess) return map_hip(e);
+        k->goct_built = true;
     }
     rc = ensure_dev(k->packed_tris, k->packed_tris_cap, (size_t)nt * 3);
     if (rc) return rc;
@@ -304,8 +327,11 @@ int prepare_scene(rt_kernel k, bool need_mats = true) {
     k->packed_tris_gen = tm->generation;
     k->packed_for_nodes = nm;
     k->packed_nodes_gen = nm->generation;
+    k->packed_tris_struct = tm->structural;
+    k->packed_nodes_struct = nm->structural;
     k->checked_mats = mm;
     k->checked_mats_gen = mm ? mm->generation : ~0ull;
+    ++k->full_prepares;
     return RT_SUCCESS;
 }
 
@@ -537,6 +563,8 @@ int rtReleaseKernel(rt_kernel k) {
     if (k->oct_nodes) (void)hipFree(k->oct_nodes);
     if (k->goct_nodes) (void)hipFree(k->goct_nodes);
     if (k->g_nodes) (void)hipFree(k->g_nodes);
+    if (k->refit_links) (void)hipFree(k->refit_links);
+    if (k->refit_arrivals) (void)hipFree(k->refit_arrivals);
     if (k->shade_tris) (void)hipFree(k->shade_tris);
     if (k->shade_mats) (void)hipFree(k->shade_mats);
     if (k->dstats) (void)hipFree(k->dstats);
@@ -1124,6 +1152,7 @@ int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t firs
     }
     hits->shadow_valid = false;  // device contents changed
     ++hits->generation;
+    ++hits->structural;
     if (k->pending_events.size() + k->pending_accum.size() > 4096) {
         rc = drain_events(k);
         if (rc) return rc;
@@ -1162,6 +1191,7 @@ int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt
     if (e != hipSuccess) return map_hip(e);
     rays->shadow_valid = false;  // device contents changed
     ++rays->generation;
+    ++rays->structural;
     return pending_error(ctx, RT_SUCCESS);
 }
 
@@ -1195,8 +1225,99 @@ int rtBuildBVHEx(rt_context ctx, rt_mem tris, size_t n_tris, unsigned max_prims_
     for (rt_mem m : {tris, nodes}) {  // device contents changed: host shadows are stale
         m->shadow_valid = false;
         ++m->generation;
+        ++m->structural;
     }
     *n_nodes = count;
+    return RT_SUCCESS;
+}
+
+// ---- moving geometry (rt_refit.hip) --------------------------------------------------------------
+
+int rtEnqueueUpdateVertices(rt_context ctx, rt_mem tris, size_t first_tri, size_t n_tris, rt_mem positions,
+                            rt_mem normals) {
+    int rc = ensure_device(ctx);
+    if (rc) return rc;
+    if (!tris || !positions || tris->ctx != ctx || positions->ctx != ctx || (normals && normals->ctx != ctx))
+        return RT_INVALID_MEM_OBJECT;
+    if (positions == tris || normals == tris) return RT_INVALID_MEM_OBJECT;
+    const size_t nt = tris->size / sizeof(rt_cl_triangle);
+    if (first_tri > nt || n_tris > nt - first_tri || nt > 0x40000000ull) return RT_INVALID_BUFFER_SIZE;
+    if (positions->size / sizeof(rt_tri_points) < n_tris || (normals && normals->size / sizeof(rt_tri_points) < n_tris))
+        return RT_INVALID_BUFFER_SIZE;
+    if (n_tris == 0) return RT_SUCCESS;
+    // coalesced frames launch first, reading (and packing) the scene as it was
+    if (ctx->pend_k) {
+        rc = rti::flush_frames(ctx);
+        if (rc) return pending_error(ctx, rc);
+    }
+    const hipError_t e = rtr::launch_update_vertices(
+        static_cast<rt_cl_triangle*>(tris->dptr), (uint32_t)first_tri, (uint32_t)n_tris,
+        static_cast<const float4*>(positions->dptr), normals ? static_cast<const float4*>(normals->dptr) : nullptr,
+        qs(ctx));
+    if (e != hipSuccess) return map_hip(e);
+    // device contents changed; positions and normals only, so the structural generation stays
+    tris->shadow_valid = false;
+    ++tris->generation;
+    return pending_error(ctx, RT_SUCCESS);
+}
+
+int rtRefitBVH(rt_context ctx, rt_kernel k) {
+    int rc = ensure_device(ctx);
+    if (rc) return rc;
+    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
+    if (!k->set[RT_ARG_BUFFER_SCENE] || !k->set[RT_ARG_BUFFER_NODE]) return RT_INVALID_KERNEL_ARGS;
+    if (ctx->pend_k) {  // coalesced frames launch first, on the scene as it was
+        rc = rti::flush_frames(ctx);
+        if (rc) return pending_error(ctx, rc);
+    }
+    rt_mem tm = k->bufs[RT_ARG_BUFFER_SCENE], nm = k->bufs[RT_ARG_BUFFER_NODE];
+    // A refit validates nothing: k's packed scene must come from these buffers, and nothing may
+    // have touched their topology or material indices since (top_limit changes reset the node
+    // generation: the global records are then renumbered by the full preparation).  Otherwise the
+    // full preparation of a launch runs first -- and validates, as a launch would.
+    const bool current = k->packed_for_tris == tm && k->packed_for_nodes == nm && k->packed_tris_gen != ~0ull &&
+                         k->packed_nodes_gen != ~0ull && k->packed_tris_struct == tm->structural &&
+                         k->packed_nodes_struct == nm->structural;
+    if (!current) {
+        k->packed_nodes_gen = ~0ull;  // (a changed generation alone would do; be explicit)
+        rc = prepare_scene(k, false);
+        if (rc) return rc;
+    }
+    rtr::RefitArgs a{};
+    a.tris = static_cast<const rt_cl_triangle*>(tm->dptr);
+    a.n_tris = k->n_tris;
+    a.nodes = static_cast<rt_cl_bvh_node*>(nm->dptr);
+    a.n_nodes = k->n_nodes;
+    a.parent = k->refit_links;
+    a.slot = k->refit_links + k->n_nodes;
+    a.arrivals = k->refit_arrivals;
+    a.oct = k->oct_nodes;
+    a.oct_stride = rtp::oct_stride(k->n_nodes), a.oct_b = rtp::oct_b(k->n_nodes);
+    a.goct = k->goct_built ? k->goct_nodes : nullptr;
+    a.goct_b = k->goct_b, a.goct_group = RT_GOCT_GROUP ? RT_GOCT_GROUP : 1;
+    a.g_nodes = k->g_nodes;
+    hipStream_t st = qs(ctx);
+    hipError_t e = rtr::launch_refit(a, st);
+    // the triangle and shading records from the moved vertices; materials stay as packed
+    if (e == hipSuccess)
+        e = rtk::launch_pack(a.tris, k->n_tris, k->packed_tris, k->shade_tris, nullptr, 0, k->shade_mats, st);
+    // the node buffer changed on the device (bounds only: its structural generation stays)
+    nm->shadow_valid = false;
+    ++nm->generation;
+    if (e != hipSuccess) {
+        k->packed_nodes_gen = ~0ull;  // whatever was enqueued, the next launch prepares in full
+        return map_hip(e);
+    }
+    k->packed_tris_gen = tm->generation;
+    k->packed_nodes_gen = nm->generation;
+    ++k->refits;
+    return pending_error(ctx, RT_SUCCESS);
+}
+
+int rtDiagScenePrepares(rt_kernel k, uint64_t* full, uint64_t* refits) {
+    if (!k) return RT_INVALID_KERNEL;
+    if (full) *full = k->full_prepares;
+    if (refits) *refits = k->refits;
     return RT_SUCCESS;
 }
 
@@ -1227,6 +1348,7 @@ int rtEnqueueWriteBuffer(rt_context ctx, rt_mem m, int blocking, size_t offset, 
     if (ctx->pend_k) (void)rti::flush_frames(ctx);
     if (m->shadow_valid) std::memcpy(m->shadow.data() + offset, src, size);
     ++m->generation;
+    ++m->structural;
     hipError_t e = hipMemcpyAsync(static_cast<uint8_t*>(m->dptr) + offset, src, size,
                                   hipMemcpyHostToDevice, qs(ctx));
     if (e == hipSuccess && blocking) e = host_wait(ctx);
@@ -1350,6 +1472,7 @@ int rtEnqueueCopyPointerRectToBuffer(rt_context ctx, const void* src, size_t src
     if (dst_offset + (rows - 1) * dst_pitch + width_bytes > dst->size) return RT_INVALID_VALUE;
     dst->shadow_valid = false;  // device contents change: a scene buffer is re-read and repacked
     ++dst->generation;
+    ++dst->structural;
     return map_hip(hipMemcpy2DAsync(static_cast<uint8_t*>(dst->dptr) + dst_offset, dst_pitch, src, src_pitch,
                                     width_bytes, rows, hipMemcpyDeviceToDevice, qs(ctx)));
 }

@@ -90,6 +90,11 @@ struct rt_mem_s {
     std::vector<uint8_t> shadow;  // host copy of the bytes (valid when shadow_valid)
     bool shadow_valid = false;
     uint64_t generation = 0;      // bumped on every host write
+    // "structural" generation: bumped by every writer that may change topology or material indices
+    // -- all of them but rtEnqueueUpdateVertices and rtRefitBVH, which touch positions, normals and
+    // bounds only.  A kernel whose packed scene has the buffers' structural generations may refit on
+    // the device without validating again (rt_capi.cpp: rtRefitBVH)
+    uint64_t structural = 0;
     // a copy-engine gather plan writes into this buffer (the root's destination, rt_comm.cpp):
     // rtReleaseBuffer then only marks it, and the plan frees it when it lets go (rti::unpin)
     int pins = 0;

@@ -182,7 +182,7 @@ void build_oct_nodes_grouped(const std::vector<uint32_t>& oct, uint32_t n, uint3
 // ray) come first and are staged in LDS; the rest keep their depth-first order.  The walk is
 // the same tree and skip table, so visits, tests and results are unchanged.
 void build_global_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
-                        uint32_t top, std::vector<uint32_t>& out, uint32_t* n_top) {
+                        uint32_t top, std::vector<uint32_t>& out, uint32_t* n_top, std::vector<uint32_t>* slot_of) {
     std::vector<uint32_t> order, newid(n, 0xffffffffu);
     order.reserve(n);
     std::vector<uint32_t> q = {0};
@@ -226,6 +226,23 @@ void build_global_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<
             r[7] = map(x.offset) | ((uint32_t)x.axis << 30);
         }
         for (int o = 0; o < 8; ++o) r[8 + o] = map(skips[(size_t)i * 8 + o]);
+    }
+    if (slot_of) slot_of->swap(newid);  // node -> its record (the device refit writes planes there)
+}
+
+// What the device refit (rt_refit.hip) needs beside the validated node buffer, 2n words: node ->
+// parent (interior i is the parent of i + 1 and offset; the root: 0xffffffff), then node -> record
+// of the global layout (build_global_nodes' renumbering).  A parent's index is smaller than its
+// children's, so a climb through these links ends at the root.
+void build_refit_links(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& slot_of,
+                       std::vector<uint32_t>& out) {
+    out.assign((size_t)n * 2, 0xffffffffu);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (nd[i].nPrimitives == 0) {
+            out[i + 1] = i;
+            out[nd[i].offset] = i;
+        }
+        out[(size_t)n + i] = slot_of[i];
     }
 }
 

@@ -40,6 +40,9 @@ bool build_oct_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uin
 void build_oct_nodes_grouped(const std::vector<uint32_t>& oct, uint32_t n, uint32_t G, std::vector<uint32_t>& out,
                              uint32_t* b_ofs);
 void build_global_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
-                        uint32_t top, std::vector<uint32_t>& out, uint32_t* n_top);
+                        uint32_t top, std::vector<uint32_t>& out, uint32_t* n_top,
+                        std::vector<uint32_t>* slot_of = nullptr);
+void build_refit_links(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& slot_of,
+                       std::vector<uint32_t>& out);
 
 }  // namespace rtp

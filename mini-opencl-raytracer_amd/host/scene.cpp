@@ -22,6 +22,7 @@
 // Arithmetic is plain fp32 with no contraction (built with -ffp-contract=off), in the
 // order of the reference's float3/CLBounds3 operators (CLmathlib.hpp:18-204).
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -523,6 +524,56 @@ int rtsFromArrays(const rt_cl_triangle* tris, size_t n_tris, const rt_cl_bvh_nod
     int rc = check_arrays(s->nodes, s->tris.size());
     if (rc) return rc;
     *out = s.release();
+    return RT_SUCCESS;
+}
+
+int rtsRefitBounds(const rt_cl_triangle* tris, size_t n_tris, rt_cl_bvh_node* nodes, size_t n_nodes) {
+    if (!nodes || n_nodes == 0 || (!tris && n_tris)) return RT_INVALID_VALUE;
+    // the tree: the prefix the root's chain of second children ends (depth-first layout)
+    size_t last = 0;
+    while (nodes[last].nPrimitives == 0) {
+        const size_t second = nodes[last].offset;
+        if (second <= last + 1 || second >= n_nodes) return RT_INVALID_VALUE;
+        last = second;
+    }
+    const size_t n = last + 1;
+    std::vector<uint8_t> parents(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const rt_cl_bvh_node& x = nodes[i];
+        if (i > 0 && parents[i] != 1) return RT_INVALID_VALUE;  // orphan
+        if (x.nPrimitives > 0) {
+            if ((uint64_t)x.offset + x.nPrimitives > n_tris) return RT_INVALID_VALUE;
+        } else {
+            const size_t a = i + 1, b = x.offset;
+            if (a >= n || b >= n || b <= a) return RT_INVALID_VALUE;
+            if (parents[a]++ != 0 || parents[b]++ != 0) return RT_INVALID_VALUE;  // shared child
+        }
+    }
+    // children have larger indices than their parent: one backward sweep
+    const float inf = std::numeric_limits<float>::infinity();
+    for (size_t i = n; i-- > 0;) {
+        rt_cl_bvh_node& x = nodes[i];
+        float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+        auto grow = [&](const rt_float3& p) {
+            lo[0] = std::fmin(lo[0], p.x), lo[1] = std::fmin(lo[1], p.y), lo[2] = std::fmin(lo[2], p.z);
+            hi[0] = std::fmax(hi[0], p.x), hi[1] = std::fmax(hi[1], p.y), hi[2] = std::fmax(hi[2], p.z);
+        };
+        if (x.nPrimitives > 0) {
+            for (size_t j = x.offset; j < (size_t)x.offset + x.nPrimitives; ++j) {
+                grow(tris[j].v1.position);
+                grow(tris[j].v2.position);
+                grow(tris[j].v3.position);
+            }
+        } else {
+            const rt_cl_bounds &b1 = nodes[i + 1].bounds, &b2 = nodes[x.offset].bounds;
+            lo[0] = std::fmin(b1.pmin.x, b2.pmin.x), lo[1] = std::fmin(b1.pmin.y, b2.pmin.y);
+            lo[2] = std::fmin(b1.pmin.z, b2.pmin.z);
+            hi[0] = std::fmax(b1.pmax.x, b2.pmax.x), hi[1] = std::fmax(b1.pmax.y, b2.pmax.y);
+            hi[2] = std::fmax(b1.pmax.z, b2.pmax.z);
+        }
+        x.bounds.pmin.x = lo[0], x.bounds.pmin.y = lo[1], x.bounds.pmin.z = lo[2];
+        x.bounds.pmax.x = hi[0], x.bounds.pmax.y = hi[1], x.bounds.pmax.z = hi[2];
+    }
     return RT_SUCCESS;
 }
 
