@@ -13,7 +13,8 @@
 // triangle array, material indices in range, depth <= 64), so a malformed scene is an
 // error code, never an out-of-bounds or non-terminating GPU walk.
 // That validation and the record packing live in rt_scene_pack.cpp, and how a launch hands its
-// work out in rt_launch_plan.cpp (both pure host code); this file keeps resources, streams, launches.
+// work out in rt_launch_plan.cpp (both pure host code); the packed scene and the rule that keeps it
+// current in rt_device_scene.cpp; this file keeps the other resources, the streams and the launches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +28,7 @@
 #include "../../include/rt_cl_types.h"
 #include "../../include/rt_hip.h"
 #include "rt_bvh.hpp"
+#include "rt_device_scene.hpp"
 #include "rt_internal.hpp"
 #include "rt_kernels.hpp"
 #include "rt_launch_plan.hpp"
@@ -49,14 +51,8 @@ constexpr size_t kHitPad = RT_TIMELINE ? 192 : 0;
 }  // namespace
 
 using rti::map_hip;
+using rti::mark_device_write;
 using rti::qs;
-using rtp::build_global_nodes;
-using rtp::build_oct_nodes;
-using rtp::build_oct_nodes_grouped;
-using rtp::build_skips;
-using rtp::check_nodes;
-using rtp::kLeafMin;
-using rtp::oct_records;
 
 struct rt_kernel_s {
     rt_context ctx = nullptr;
@@ -134,33 +130,7 @@ struct rt_kernel_s {
     int rad_set = 0;
     hipEvent_t render_done = nullptr;  // recorded on the main stream after a fused render
     uint64_t pf_waits = ~0ull;         // ctx->host_waits at the previous per-frame step launch
-    // derived packed scene
-    rt_mem packed_for_tris = nullptr, packed_for_nodes = nullptr, checked_mats = nullptr;
-    uint64_t packed_tris_gen = ~0ull, packed_nodes_gen = ~0ull, checked_mats_gen = ~0ull;
-    // the buffers' structural generations at the last full preparation (rtRefitBVH)
-    uint64_t packed_tris_struct = ~0ull, packed_nodes_struct = ~0ull;
-    // device refit (rt_refit.hip): node -> parent, then node -> g_nodes record (n_nodes words each),
-    // uploaded by the full preparation; the climb's arrival counters
-    uint32_t* refit_links = nullptr;
-    uint32_t* refit_arrivals = nullptr;
-    size_t refit_links_cap = 0, refit_arrivals_cap = 0;
-    bool goct_built = false;           // goct_nodes holds this scene's records
-    uint64_t full_prepares = 0, refits = 0;  // rtDiagScenePrepares
-    float4* packed_tris = nullptr;
-    float4* oct_nodes = nullptr;       // [node][octant] 2 x float4 (LDS-resident scenes)
-    float4* goct_nodes = nullptr;      // regrouped octant records for the HBM/L2 walk (RT_GOCT_GROUP)
-    size_t goct_nodes_cap = 0;
-    uint32_t goct_b = 0;               // their B planes' float4 offset
-    float4* shade_tris = nullptr;      // compact shading records (normals + mtlIndex)
-    float4* shade_mats = nullptr;      // compact materials
-    size_t shade_tris_cap = 0, shade_mats_cap = 0;
-    bool oct_ok = false;               // every leaf fits the records' inline {first, count}
-    float4* g_nodes = nullptr;         // global-scene node records (64 B, top of the tree first)
-    size_t g_nodes_cap = 0;
-    uint32_t n_top = 0, top_limit = 384;  // nodes of g_nodes staged in LDS (global path; swept, profiles/r01/bunny_top_nodes_sweep_2.txt)
-    size_t packed_tris_cap = 0, oct_nodes_cap = 0;  // float4s
-    uint32_t n_nodes = 0, n_tris = 0, n_mats = 0;
-    int depth = 0;
+    rti::DeviceScene scene;  // the derived packed scene (rt_device_scene.hpp)
     bool last_lds = false;
     // [sched][math][lds][stats][bofs or goct, + 2 for fused launches] -> blocks per CU (0 = unknown)
     int occ_cache[rtk::kNumSched][3][2][2][4] = {};
@@ -190,6 +160,14 @@ void flush_kernel(rt_kernel k) {
     if (k && k->ctx && k->ctx->pend_k == k) (void)rti::flush_frames(k->ctx);
 }
 
+// another call touches the context: its coalesced frames launch first, and an error of theirs is
+// that call's status
+int flush_first(rt_context ctx) {
+    if (!ctx || !ctx->pend_k) return RT_SUCCESS;
+    const int rc = rti::flush_frames(ctx);
+    return rc ? pending_error(ctx, rc) : RT_SUCCESS;
+}
+
 // the arguments a coalesced launch compares (FRAME_COUNT continues the run; FRAME_SEED is never
 // read by KernelEntry, kernel_bvh.cl:415-456)
 bool same_args(const rt_context ctx, const rt_kernel k) {
@@ -202,137 +180,10 @@ bool same_args(const rt_context ctx, const rt_kernel k) {
 }
 
 
-// Host view of a buffer's bytes (shadow, or a device read-back).
-int host_bytes(rt_mem m, std::vector<uint8_t>& tmp, const uint8_t** out) {
-    if (m->shadow_valid) {
-        *out = m->shadow.data();
-        return RT_SUCCESS;
-    }
-    tmp.resize(m->size);
-    hipError_t e = hipMemcpyAsync(tmp.data(), m->dptr, m->size, hipMemcpyDeviceToHost, qs(m->ctx));
-    if (e == hipSuccess) e = hipStreamSynchronize(qs(m->ctx));
-    if (e != hipSuccess) return map_hip(e);
-    *out = tmp.data();
-    return RT_SUCCESS;
-}
-
-template <class T>
-int ensure_dev(T*& p, size_t& cap, size_t count) {
-    if (cap >= count) return RT_SUCCESS;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, count * sizeof(T));
-    if (e != hipSuccess) return map_hip(e);
-    cap = count;
-    return RT_SUCCESS;
-}
-
-// need_mats false (ray queries): the material buffer may be unbound -- then no material is packed
-// and no material index checked, and the next render packs and checks again (checked_mats reset)
-int prepare_scene(rt_kernel k, bool need_mats = true) {
-    rt_mem tm = k->bufs[RT_ARG_BUFFER_SCENE], nm = k->bufs[RT_ARG_BUFFER_NODE],
-           mm = k->bufs[RT_ARG_BUFFER_MATERIAL];
-    if (need_mats && !mm) return RT_INVALID_KERNEL_ARGS;
-    if (tm->size < sizeof(rt_cl_triangle) || nm->size < sizeof(rt_cl_bvh_node) ||
-        (mm && mm->size < sizeof(rt_cl_material)))
-        return RT_INVALID_MEM_OBJECT;
-    const uint32_t nt = (uint32_t)(tm->size / sizeof(rt_cl_triangle));
-    const uint32_t n_buf = (uint32_t)(nm->size / sizeof(rt_cl_bvh_node));
-    const uint32_t nmat = mm ? (uint32_t)(mm->size / sizeof(rt_cl_material)) : 0u;
-    const bool tris_stale = k->packed_for_tris != tm || k->packed_tris_gen != tm->generation;
-    const bool nodes_stale = k->packed_for_nodes != nm || k->packed_nodes_gen != nm->generation;
-    const bool mats_stale = mm && (k->checked_mats != mm || k->checked_mats_gen != mm->generation);
-    if (!tris_stale && !nodes_stale && !mats_stale) return RT_SUCCESS;
-
-    std::vector<uint8_t> tmp_t, tmp_n;
-    const uint8_t *tb = nullptr, *nb = nullptr;
-    int rc = host_bytes(tm, tmp_t, &tb);
-    if (rc) return rc;
-    rc = host_bytes(nm, tmp_n, &nb);
-    if (rc) return rc;
-    int depth = 0;
-    uint32_t nn = 0;  // the tree's nodes: a prefix of the buffer
-    rc = check_nodes(reinterpret_cast<const rt_cl_bvh_node*>(nb), n_buf, nt, &depth, &nn);
-    if (rc) return rc;
-    const rt_cl_triangle* tr = reinterpret_cast<const rt_cl_triangle*>(tb);
-    for (uint32_t i = 0; mm && i < nt; ++i)
-        if (tr[i].mtlIndex >= nmat) return RT_INVALID_MEM_OBJECT;
-    std::vector<uint32_t> skips;
-    build_skips(reinterpret_cast<const rt_cl_bvh_node*>(nb), nn, skips);
-
-    if (nn >= (1u << 30)) return RT_INVALID_MEM_OBJECT;  // node indices share a word with the axis
-    std::vector<uint32_t> gn;
-    uint32_t n_top = 0;
-    // (links: what the device refit needs beside the node buffer -- parent links, then each node's
-    // renumbered record in g_nodes)
-    std::vector<uint32_t> slot_of, links;
-    build_global_nodes(reinterpret_cast<const rt_cl_bvh_node*>(nb), nn, skips, k->top_limit, gn, &n_top, &slot_of);
-    rtp::build_refit_links(reinterpret_cast<const rt_cl_bvh_node*>(nb), nn, slot_of, links);
-    rc = ensure_dev(k->g_nodes, k->g_nodes_cap, (size_t)nn * 4);
-    if (rc) return rc;
-    rc = ensure_dev(k->refit_links, k->refit_links_cap, (size_t)nn * 2);
-    if (rc) return rc;
-    rc = ensure_dev(k->refit_arrivals, k->refit_arrivals_cap, (size_t)nn);
-    if (rc) return rc;
-    {
-        hipError_t e = hipMemcpyAsync(k->g_nodes, gn.data(), gn.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                      qs(k->ctx));
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(k->refit_links, links.data(), links.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
-                               qs(k->ctx));
-        if (e != hipSuccess) return map_hip(e);
-    }
-    std::vector<uint32_t> oct;
-    const bool oct_ok = build_oct_nodes(reinterpret_cast<const rt_cl_bvh_node*>(nb), nn, skips, oct);
-    rc = ensure_dev(k->oct_nodes, k->oct_nodes_cap, (size_t)oct_records(nn));
-    if (rc) return rc;
-    {
-        hipError_t e = hipMemcpyAsync(k->oct_nodes, oct.data(), oct.size() * sizeof(uint32_t),
-                                      hipMemcpyHostToDevice, qs(k->ctx));
-        if (e == hipSuccess) e = hipStreamSynchronize(qs(k->ctx));
-        if (e != hipSuccess) return map_hip(e);
-    }
-    k->goct_b = 0;
-    k->goct_built = false;
-    if (RT_GOCT_GROUP && oct_ok && (uint64_t)(nn + RT_GOCT_GROUP) * 8u < kLeafMin) {
-        std::vector<uint32_t> nm;
-        build_oct_nodes_grouped(oct, nn, RT_GOCT_GROUP, nm, &k->goct_b);
-        rc = ensure_dev(k->goct_nodes, k->goct_nodes_cap, nm.size() / 4);
-        if (rc) return rc;
-        hipError_t e = hipMemcpyAsync(k->goct_nodes, nm.data(), nm.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                      qs(k->ctx));
-        if (e == hipSuccess) e = hipStreamSynchronize(qs(k->ctx));
-        if (e != hipSuccess) return map_hip(e);
-        k->goct_built = true;
-    }
-    rc = ensure_dev(k->packed_tris, k->packed_tris_cap, (size_t)nt * 3);
-    if (rc) return rc;
-    rc = ensure_dev(k->shade_tris, k->shade_tris_cap, (size_t)nt * 3);
-    if (rc) return rc;
-    // two material tables: IEEE divisions (pinned, devicelib), then the shipped policy's
-    rc = ensure_dev(k->shade_mats, k->shade_mats_cap, (size_t)nmat * 8);
-    if (rc) return rc;
-    hipError_t e = rtk::launch_pack(static_cast<const rt_cl_triangle*>(tm->dptr), nt, k->packed_tris,
-                                    k->shade_tris, mm ? static_cast<const rt_cl_material*>(mm->dptr) : nullptr, nmat,
-                                    k->shade_mats, qs(k->ctx));
-    if (e != hipSuccess) return map_hip(e);
-    k->n_nodes = nn;
-    k->n_tris = nt;
-    k->n_mats = nmat;
-    k->depth = depth;
-    k->oct_ok = oct_ok;
-    k->n_top = n_top;
-    k->packed_for_tris = tm;
-    k->packed_tris_gen = tm->generation;
-    k->packed_for_nodes = nm;
-    k->packed_nodes_gen = nm->generation;
-    k->packed_tris_struct = tm->structural;
-    k->packed_nodes_struct = nm->structural;
-    k->checked_mats = mm;
-    k->checked_mats_gen = mm ? mm->generation : ~0ull;
-    ++k->full_prepares;
-    return RT_SUCCESS;
+// k's packed scene is that of its bound buffers (a malformed scene is refused here, before any launch)
+int prepare_scene(rt_kernel k) {
+    return k->scene.prepare(k->ctx, k->bufs[RT_ARG_BUFFER_SCENE], k->bufs[RT_ARG_BUFFER_NODE],
+                            k->bufs[RT_ARG_BUFFER_MATERIAL]);
 }
 
 hipEvent_t take_event(rt_kernel k) {
@@ -345,6 +196,31 @@ hipEvent_t take_event(rt_kernel k) {
     if (hipEventCreate(&e) != hipSuccess) return nullptr;
     return e;
 }
+
+using EventList = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
+
+// The timing bracket of one launch on `st` (rtKernelSetTiming; nothing without it): an event before
+// the launch and one after, kept in `list` until drain_events reads them.
+struct TimedLaunch {
+    rt_kernel k;
+    hipStream_t st;
+    EventList& list;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+
+    bool begin() {  // false: no events to be had
+        if (!k->timing) return true;
+        ev0 = take_event(k);
+        ev1 = take_event(k);
+        if (!ev0 || !ev1) return false;
+        (void)hipEventRecord(ev0, st);
+        return true;
+    }
+    void end() {
+        if (!k->timing) return;
+        (void)hipEventRecord(ev1, st);
+        list.emplace_back(ev0, ev1);
+    }
+};
 
 static int drain_list(rt_kernel k, std::vector<std::pair<hipEvent_t, hipEvent_t>>& list, double& total,
                       bool renders) {
@@ -380,6 +256,12 @@ int drain_events(rt_kernel k) {
     int rc = drain_list(k, k->pending_events, k->kernel_ms, true);
     if (rc) return rc;
     return drain_list(k, k->pending_accum, k->accum_ms, false);
+}
+
+// after a launch: the brackets nobody has read yet stay bounded
+int drain_if_many(rt_kernel k) {
+    if (k->pending_events.size() + k->pending_accum.size() <= 4096) return RT_SUCCESS;
+    return drain_events(k);
 }
 
 void reset_period(rt_kernel k) {
@@ -559,14 +441,7 @@ int rtReleaseKernel(rt_kernel k) {
         if (q) (void)hipFree(q);
     if (k->wf_hits) (void)hipFree(k->wf_hits);
     if (k->wf_cnt) (void)hipFree(k->wf_cnt);
-    if (k->packed_tris) (void)hipFree(k->packed_tris);
-    if (k->oct_nodes) (void)hipFree(k->oct_nodes);
-    if (k->goct_nodes) (void)hipFree(k->goct_nodes);
-    if (k->g_nodes) (void)hipFree(k->g_nodes);
-    if (k->refit_links) (void)hipFree(k->refit_links);
-    if (k->refit_arrivals) (void)hipFree(k->refit_arrivals);
-    if (k->shade_tris) (void)hipFree(k->shade_tris);
-    if (k->shade_mats) (void)hipFree(k->shade_mats);
+    k->scene.release();
     if (k->dstats) (void)hipFree(k->dstats);
     if (k->work_counter) (void)hipFree(k->work_counter);
     if (k->accum_key) (void)hipFree(k->accum_key);
@@ -642,11 +517,8 @@ int rtEnqueueKernel(rt_context ctx, rt_kernel k, size_t global_work_size) {
     const bool coalesce = ctx && k && k->ctx == ctx && k->pf_batch > 1 && k->sched == RT_SCHED_STEP && !k->stats &&
                           !k->timing && !ctx->mexposed && !ctx->dexposed;
     if (!coalesce) {
-        if (ctx && ctx->pend_k) {
-            const int rc = rti::flush_frames(ctx);
-            if (rc) return pending_error(ctx, rc);
-        }
-        return enqueue(ctx, k, global_work_size, 1);
+        const int rc = flush_first(ctx);
+        return rc ? rc : enqueue(ctx, k, global_work_size, 1);
     }
     int rc = ensure_device(ctx);
     if (rc) return rc;
@@ -669,10 +541,8 @@ int rtEnqueueKernel(rt_context ctx, rt_kernel k, size_t global_work_size) {
         ++ctx->pend_n;  // the next frame of the run
         return RT_SUCCESS;
     }
-    if (ctx->pend_k) {
-        rc = rti::flush_frames(ctx);
-        if (rc) return pending_error(ctx, rc);
-    }
+    rc = flush_first(ctx);
+    if (rc) return rc;
     rc = prepare_scene(k);  // (a malformed scene is refused now, not at the launch)
     if (rc) return rc;
     ctx->pend_k = k;
@@ -687,10 +557,7 @@ int rtEnqueueKernel(rt_context ctx, rt_kernel k, size_t global_work_size) {
 
 int rtEnqueueKernelFrames(rt_context ctx, rt_kernel k, size_t global_work_size, unsigned n_frames) {
     if (n_frames == 0) return RT_INVALID_VALUE;
-    if (ctx && ctx->pend_k) {
-        const int rc = rti::flush_frames(ctx);
-        if (rc) return pending_error(ctx, rc);
-    }
+    if (const int rc = flush_first(ctx)) return rc;
     if (n_frames == 1 || !k || (k->sched != RT_SCHED_STEP && k->sched != RT_SCHED_WAVEFRONT)) {
         // one launch per frame (the other schedules have no fused form): same results
         if (!k) return RT_INVALID_KERNEL;
@@ -735,9 +602,10 @@ static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, size_t global_work_s
     in.stats = k->stats, in.hit_bound = k->hit_ids != nullptr;
     in.fused = fused, in.overlap = ctx->overlap;
     in.band_period = k->band_period, in.band_phase = k->band_phase;
-    in.n_nodes = k->n_nodes, in.n_tris = k->n_tris, in.n_mats = k->n_mats, in.n_top = k->n_top;
-    in.oct_ok = k->oct_ok;
-    in.goct_available = k->goct_nodes != nullptr, in.goct_b = k->goct_b;
+    const rti::DeviceScene& sc = k->scene;
+    in.n_nodes = sc.n_nodes(), in.n_tris = sc.n_tris(), in.n_mats = sc.n_mats(), in.n_top = sc.n_top();
+    in.oct_ok = sc.oct_ok();
+    in.goct_available = sc.goct() != nullptr, in.goct_b = sc.goct_b();
     in.force_global = k->force_global, in.global_oct = k->global_oct;
     in.refill_min = k->refill_min, in.shade_min = k->shade_min, in.refill_min_set = k->refill_min_set;
     in.refill_min_g = k->refill_min_g, in.shade_min_g = k->shade_min_g;
@@ -770,12 +638,13 @@ static void fill_args(rt_kernel k, const rtp::LaunchPlan& p, rtk::KernelArgs* ar
     a.result = static_cast<float4*>(k->bufs[RT_ARG_BUFFER_OUT]->dptr);
     a.trisFull = static_cast<const rt_cl_triangle*>(k->bufs[RT_ARG_BUFFER_SCENE]->dptr);
     a.materials = static_cast<const rt_cl_material*>(k->bufs[RT_ARG_BUFFER_MATERIAL]->dptr);
-    a.packedTris = k->packed_tris;
-    a.octNodes = p.regrouped ? k->goct_nodes : k->oct_nodes;
-    a.gNodes = k->g_nodes;
-    a.shadeTris = k->shade_tris;
-    a.shadeMats = k->shade_mats + (k->math == RT_MATH_SHIPPED ? 4 * (size_t)k->n_mats : 0);
-    a.nMats = k->n_mats, a.nTris = k->n_tris;
+    const rti::DeviceScene& sc = k->scene;
+    a.packedTris = sc.packed_tris();
+    a.octNodes = p.regrouped ? sc.goct() : sc.oct_nodes();
+    a.gNodes = sc.g_nodes();
+    a.shadeTris = sc.shade_tris();
+    a.shadeMats = sc.shade_mats() + (k->math == RT_MATH_SHIPPED ? 4 * (size_t)sc.n_mats() : 0);
+    a.nMats = sc.n_mats(), a.nTris = sc.n_tris();
     a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords, a.nTop = p.nTop;
     std::memcpy(&a.width, &k->u32[RT_ARG_WIDTH], 4);
     std::memcpy(&a.height, &k->u32[RT_ARG_HEIGHT], 4);
@@ -903,13 +772,8 @@ static int enqueue_accum(rt_context ctx, rt_kernel k, const rtk::KernelArgs& a, 
         if (e == hipSuccess) e = hipStreamWaitEvent(as, k->render_done, 0);
         if (e != hipSuccess) return fail(map_hip(e));
     }
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (k->timing) {
-        ea = take_event(k);
-        eb = take_event(k);
-        if (!ea || !eb) return fail(RT_OUT_OF_RESOURCES);
-        (void)hipEventRecord(ea, as);
-    }
+    TimedLaunch timed{k, as, k->pending_accum};
+    if (!timed.begin()) return fail(RT_OUT_OF_RESOURCES);
     // (a root's gather copies of the previous image read `out`: the accumulation that rewrites
     // it comes after them)
     e = rti::out_read_wait(ctx, as);
@@ -918,10 +782,7 @@ static int enqueue_accum(rt_context ctx, rt_kernel k, const rtk::KernelArgs& a, 
     e = rtk::launch_accum_frames(a, k->math, k->accum_key, as);
     if (e != hipSuccess) return fail(map_hip(e));
 #endif
-    if (k->timing) {
-        (void)hipEventRecord(eb, as);
-        k->pending_accum.emplace_back(ea, eb);
-    }
+    timed.end();
     if (ctx->overlap) {
         const int rs = k->rad_set;
         e = hipEventRecord(k->rad_free[rs], as);
@@ -1034,22 +895,14 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
         hipError_t me = hipMemsetAsync(a.workCounter, 0, 16, rstr);
         if (me != hipSuccess) return map_hip(me);
     }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (k->timing) {
-        ev0 = take_event(k);
-        ev1 = take_event(k);
-        if (!ev0 || !ev1) return RT_OUT_OF_RESOURCES;
-        (void)hipEventRecord(ev0, rstr);
-    }
+    TimedLaunch timed{k, rstr, k->pending_events};
+    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
     hipError_t e = wf ? rtk::launch_wavefront(a, wa, wq, wcnt, k->math, p.lds, k->stats, p.bofs, (unsigned)p.grid,
                                               p.smem, p.grid_s, rstr, p.goct)
                       : rtk::launch_kernel_entry(a, si, k->math, p.lds, k->stats, (unsigned)p.grid, p.smem, rstr,
                                                  p.goct);
     if (e != hipSuccess) return map_hip(e);
-    if (k->timing) {
-        (void)hipEventRecord(ev1, rstr);
-        k->pending_events.emplace_back(ev0, ev1);
-    }
+    timed.end();
     if (a.pfKeyIn) k->pf_parity ^= 1;
     if (p.pf_slots) k->pf_ctr ^= 1;  // flips only when the launch call reported success
 
@@ -1059,10 +912,8 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
         if (rc) return rc;
     }
     // 10. bookkeeping
-    if (k->pending_events.size() + k->pending_accum.size() > 4096) {
-        rc = drain_events(k);
-        if (rc) return rc;
-    }
+    rc = drain_if_many(k);
+    if (rc) return rc;
     ++k->launches;
     return RT_SUCCESS;
 }
@@ -1080,9 +931,10 @@ static rtp::QueryIn query_inputs(rt_context ctx, rt_kernel k, rt_mem rays, size_
     in.mode = mode;
     in.oct_ok = true;
     if (packed) {
-        in.n_nodes = k->n_nodes, in.n_tris = k->n_tris;
-        in.oct_ok = k->oct_ok;
-        in.goct_available = k->goct_nodes != nullptr, in.goct_b = k->goct_b;
+        const rti::DeviceScene& sc = k->scene;
+        in.n_nodes = sc.n_nodes(), in.n_tris = sc.n_tris();
+        in.oct_ok = sc.oct_ok();
+        in.goct_available = sc.goct() != nullptr, in.goct_b = sc.goct_b();
     }
     in.force_global = k->force_global;
     in.refill_min = k->query_refill_min;
@@ -1099,16 +951,14 @@ int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t firs
     if (rc) return rc;
     if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
     if (!rays || !hits || rays->ctx != ctx || hits->ctx != ctx) return RT_INVALID_MEM_OBJECT;
-    if (ctx->pend_k) {  // another call touches the context: the coalesced frames launch first
-        rc = rti::flush_frames(ctx);
-        if (rc) return pending_error(ctx, rc);
-    }
+    rc = flush_first(ctx);
+    if (rc) return rc;
     rtp::QueryPlan p;
     rc = rtp::query_shape(query_inputs(ctx, k, rays, first_ray, n_rays, mode, hits, false), &p);
     if (rc || p.nothing) return pending_error(ctx, rc);
     if (!k->set[RT_ARG_BUFFER_SCENE] || !k->set[RT_ARG_BUFFER_NODE]) return RT_INVALID_KERNEL_ARGS;
     // 2. the scene, packed and validated as a render launch does (materials only when bound)
-    rc = prepare_scene(k, false);
+    rc = prepare_scene(k);
     if (rc) return rc;
     // 3. the plan, with the kernel's occupancy at the LDS size it chose
     const rtp::QueryIn in = query_inputs(ctx, k, rays, first_ray, n_rays, mode, hits, true);
@@ -1124,9 +974,9 @@ int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t firs
     // 4. the arguments
     rtk::KernelArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.packedTris = k->packed_tris;
-    a.octNodes = p.regrouped ? k->goct_nodes : k->oct_nodes;
-    a.nTris = k->n_tris;
+    a.packedTris = k->scene.packed_tris();
+    a.octNodes = p.regrouped ? k->scene.goct() : k->scene.oct_nodes();
+    a.nTris = k->scene.n_tris();
     a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords;
     a.stepWeightNode = p.stepWeightNode, a.stepWeightLeaf = p.stepWeightLeaf;
     a.stats = k->dstats;
@@ -1137,26 +987,14 @@ int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t firs
     // 5. the launch, on the context's stream after the pending accumulations and gathers
     hipStream_t st = qs(ctx);
     k->last_lds = p.lds;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (k->timing) {
-        ev0 = take_event(k);
-        ev1 = take_event(k);
-        if (!ev0 || !ev1) return RT_OUT_OF_RESOURCES;
-        (void)hipEventRecord(ev0, st);
-    }
+    TimedLaunch timed{k, st, k->pending_events};
+    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
     const hipError_t e = rtk::launch_query(a, q, k->math, p.lds, k->stats, p.bofs, p.any, p.grid, p.smem, st);
     if (e != hipSuccess) return map_hip(e);
-    if (k->timing) {
-        (void)hipEventRecord(ev1, st);
-        k->pending_events.emplace_back(ev0, ev1);
-    }
-    hits->shadow_valid = false;  // device contents changed
-    ++hits->generation;
-    ++hits->structural;
-    if (k->pending_events.size() + k->pending_accum.size() > 4096) {
-        rc = drain_events(k);
-        if (rc) return rc;
-    }
+    timed.end();
+    mark_device_write(hits, true);
+    rc = drain_if_many(k);
+    if (rc) return rc;
     ++k->launches;
     return pending_error(ctx, RT_SUCCESS);
 }
@@ -1166,10 +1004,8 @@ int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt
     if (rc) return rc;
     if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
     if (!rays || rays->ctx != ctx) return RT_INVALID_MEM_OBJECT;
-    if (ctx->pend_k) {  // another call touches the context: the coalesced frames launch first
-        rc = rti::flush_frames(ctx);
-        if (rc) return pending_error(ctx, rc);
-    }
+    rc = flush_first(ctx);
+    if (rc) return rc;
     for (int i : {RT_ARG_WIDTH, RT_ARG_HEIGHT, RT_ARG_FRAME_COUNT, RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT,
                   RT_ARG_CAMERA_UP})
         if (!k->set[i]) return RT_INVALID_KERNEL_ARGS;
@@ -1189,9 +1025,7 @@ int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt
     const hipError_t e =
         rtk::launch_camera_rays(a, static_cast<float4*>(rays->dptr), (uint32_t)global_work_size, k->math, qs(ctx));
     if (e != hipSuccess) return map_hip(e);
-    rays->shadow_valid = false;  // device contents changed
-    ++rays->generation;
-    ++rays->structural;
+    mark_device_write(rays, true);
     return pending_error(ctx, RT_SUCCESS);
 }
 
@@ -1222,11 +1056,7 @@ int rtBuildBVHEx(rt_context ctx, rt_mem tris, size_t n_tris, unsigned max_prims_
     if (e == hipSuccess) e = hipStreamSynchronize(qs(ctx));
     (void)hipFree(scratch);
     if (e != hipSuccess) return map_hip(e);
-    for (rt_mem m : {tris, nodes}) {  // device contents changed: host shadows are stale
-        m->shadow_valid = false;
-        ++m->generation;
-        ++m->structural;
-    }
+    for (rt_mem m : {tris, nodes}) mark_device_write(m, true);
     *n_nodes = count;
     return RT_SUCCESS;
 }
@@ -1246,18 +1076,14 @@ int rtEnqueueUpdateVertices(rt_context ctx, rt_mem tris, size_t first_tri, size_
         return RT_INVALID_BUFFER_SIZE;
     if (n_tris == 0) return RT_SUCCESS;
     // coalesced frames launch first, reading (and packing) the scene as it was
-    if (ctx->pend_k) {
-        rc = rti::flush_frames(ctx);
-        if (rc) return pending_error(ctx, rc);
-    }
+    rc = flush_first(ctx);
+    if (rc) return rc;
     const hipError_t e = rtr::launch_update_vertices(
         static_cast<rt_cl_triangle*>(tris->dptr), (uint32_t)first_tri, (uint32_t)n_tris,
         static_cast<const float4*>(positions->dptr), normals ? static_cast<const float4*>(normals->dptr) : nullptr,
         qs(ctx));
     if (e != hipSuccess) return map_hip(e);
-    // device contents changed; positions and normals only, so the structural generation stays
-    tris->shadow_valid = false;
-    ++tris->generation;
+    mark_device_write(tris, false);  // positions and normals only
     return pending_error(ctx, RT_SUCCESS);
 }
 
@@ -1266,58 +1092,17 @@ int rtRefitBVH(rt_context ctx, rt_kernel k) {
     if (rc) return rc;
     if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
     if (!k->set[RT_ARG_BUFFER_SCENE] || !k->set[RT_ARG_BUFFER_NODE]) return RT_INVALID_KERNEL_ARGS;
-    if (ctx->pend_k) {  // coalesced frames launch first, on the scene as it was
-        rc = rti::flush_frames(ctx);
-        if (rc) return pending_error(ctx, rc);
-    }
-    rt_mem tm = k->bufs[RT_ARG_BUFFER_SCENE], nm = k->bufs[RT_ARG_BUFFER_NODE];
-    // A refit validates nothing: k's packed scene must come from these buffers, and nothing may
-    // have touched their topology or material indices since (top_limit changes reset the node
-    // generation: the global records are then renumbered by the full preparation).  Otherwise the
-    // full preparation of a launch runs first -- and validates, as a launch would.
-    const bool current = k->packed_for_tris == tm && k->packed_for_nodes == nm && k->packed_tris_gen != ~0ull &&
-                         k->packed_nodes_gen != ~0ull && k->packed_tris_struct == tm->structural &&
-                         k->packed_nodes_struct == nm->structural;
-    if (!current) {
-        k->packed_nodes_gen = ~0ull;  // (a changed generation alone would do; be explicit)
-        rc = prepare_scene(k, false);
-        if (rc) return rc;
-    }
-    rtr::RefitArgs a{};
-    a.tris = static_cast<const rt_cl_triangle*>(tm->dptr);
-    a.n_tris = k->n_tris;
-    a.nodes = static_cast<rt_cl_bvh_node*>(nm->dptr);
-    a.n_nodes = k->n_nodes;
-    a.parent = k->refit_links;
-    a.slot = k->refit_links + k->n_nodes;
-    a.arrivals = k->refit_arrivals;
-    a.oct = k->oct_nodes;
-    a.oct_stride = rtp::oct_stride(k->n_nodes), a.oct_b = rtp::oct_b(k->n_nodes);
-    a.goct = k->goct_built ? k->goct_nodes : nullptr;
-    a.goct_b = k->goct_b, a.goct_group = RT_GOCT_GROUP ? RT_GOCT_GROUP : 1;
-    a.g_nodes = k->g_nodes;
-    hipStream_t st = qs(ctx);
-    hipError_t e = rtr::launch_refit(a, st);
-    // the triangle and shading records from the moved vertices; materials stay as packed
-    if (e == hipSuccess)
-        e = rtk::launch_pack(a.tris, k->n_tris, k->packed_tris, k->shade_tris, nullptr, 0, k->shade_mats, st);
-    // the node buffer changed on the device (bounds only: its structural generation stays)
-    nm->shadow_valid = false;
-    ++nm->generation;
-    if (e != hipSuccess) {
-        k->packed_nodes_gen = ~0ull;  // whatever was enqueued, the next launch prepares in full
-        return map_hip(e);
-    }
-    k->packed_tris_gen = tm->generation;
-    k->packed_nodes_gen = nm->generation;
-    ++k->refits;
-    return pending_error(ctx, RT_SUCCESS);
+    rc = flush_first(ctx);  // coalesced frames launch first, on the scene as it was
+    if (rc) return rc;
+    rc = k->scene.refit(ctx, k->bufs[RT_ARG_BUFFER_SCENE], k->bufs[RT_ARG_BUFFER_NODE],
+                        k->bufs[RT_ARG_BUFFER_MATERIAL]);
+    return rc ? rc : pending_error(ctx, RT_SUCCESS);
 }
 
 int rtDiagScenePrepares(rt_kernel k, uint64_t* full, uint64_t* refits) {
     if (!k) return RT_INVALID_KERNEL;
-    if (full) *full = k->full_prepares;
-    if (refits) *refits = k->refits;
+    if (full) *full = k->scene.full_prepares();
+    if (refits) *refits = k->scene.refits();
     return RT_SUCCESS;
 }
 
@@ -1470,9 +1255,7 @@ int rtEnqueueCopyPointerRectToBuffer(rt_context ctx, const void* src, size_t src
     if (rows == 0 || width_bytes == 0) return RT_SUCCESS;
     if (width_bytes > src_pitch || width_bytes > dst_pitch) return RT_INVALID_VALUE;
     if (dst_offset + (rows - 1) * dst_pitch + width_bytes > dst->size) return RT_INVALID_VALUE;
-    dst->shadow_valid = false;  // device contents change: a scene buffer is re-read and repacked
-    ++dst->generation;
-    ++dst->structural;
+    mark_device_write(dst, true);  // a scene buffer is re-read and repacked
     return map_hip(hipMemcpy2DAsync(static_cast<uint8_t*>(dst->dptr) + dst_offset, dst_pitch, src, src_pitch,
                                     width_bytes, rows, hipMemcpyDeviceToDevice, qs(ctx)));
 }
@@ -1606,7 +1389,7 @@ int rtValidateBVH(const void* nodes, size_t n_nodes, size_t n_tris, int* depth) 
     if (!nodes || n_nodes == 0 || n_nodes >= (1u << 30) || n_tris >= (1ull << 32)) return RT_INVALID_VALUE;
     int d = 0;
     uint32_t used = 0;
-    int rc = check_nodes(static_cast<const rt_cl_bvh_node*>(nodes), (uint32_t)n_nodes, (uint32_t)n_tris, &d, &used);
+    int rc = rtp::check_nodes(static_cast<const rt_cl_bvh_node*>(nodes), (uint32_t)n_nodes, (uint32_t)n_tris, &d, &used);
     if (rc == RT_SUCCESS && depth) *depth = d;
     return rc;
 }
@@ -1635,7 +1418,7 @@ int rtKernelSetTuning(rt_kernel k, int param, int value) {
             k->tail_chunk = (uint32_t)value;
             break;
         case RT_TUNE_BULK_PERCENT: if (!in(0, 100)) return RT_INVALID_VALUE; k->bulk_percent = (uint32_t)value; break;
-        case RT_TUNE_TOP_NODES: if (!in(0, 1024)) return RT_INVALID_VALUE; k->top_limit = (uint32_t)value; k->packed_nodes_gen = ~0ull; break;
+        case RT_TUNE_TOP_NODES: if (!in(0, 1024)) return RT_INVALID_VALUE; k->scene.top_limit = (uint32_t)value; k->scene.invalidate(); break;
         case RT_TUNE_TILE_MAJOR: if (!in(-1, 2)) return RT_INVALID_VALUE; k->tile_major = value; break;
         case RT_TUNE_MAX_BLOCKS: if (!in(0, 64)) return RT_INVALID_VALUE; k->max_blocks = value; break;
         case RT_TUNE_PERFRAME_SKY: if (!in(0, 2)) return RT_INVALID_VALUE; k->pf_sky = value; break;
@@ -1667,7 +1450,7 @@ int rtKernelGetTuning(rt_kernel k, int param, int* value) {
         case RT_TUNE_CHUNK_PIXELS: *value = (int)k->chunk_pixels; break;
         case RT_TUNE_TAIL_CHUNK: *value = (int)k->tail_chunk; break;
         case RT_TUNE_BULK_PERCENT: *value = (int)k->bulk_percent; break;
-        case RT_TUNE_TOP_NODES: *value = (int)k->top_limit; break;
+        case RT_TUNE_TOP_NODES: *value = (int)k->scene.top_limit; break;
         case RT_TUNE_TILE_MAJOR: *value = k->tile_major; break;
         case RT_TUNE_MAX_BLOCKS: *value = k->max_blocks; break;
         case RT_TUNE_PERFRAME_SKY: *value = k->pf_sky; break;

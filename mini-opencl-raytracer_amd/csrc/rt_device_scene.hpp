@@ -1,0 +1,85 @@
+// rt_device_scene.hpp -- the packed scene a kernel's launches read: the device records derived from
+// the caller's triangle, node and material buffers, which buffers (and which of their generations)
+// they were derived from, and the one rule that decides when they are stale.  Nothing is launched on a
+// scene the host has not validated (rt_scene_pack.cpp): prepare() runs before every launch and every
+// query, and refit() skips the validation only while nothing structural was written since the last one.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rt_internal.hpp"
+
+namespace rti {
+
+class DeviceScene {
+public:
+    // nodes of the global records staged in LDS (RT_TUNE_TOP_NODES; swept,
+    // profiles/r01/bunny_top_nodes_sweep_2.txt).  A change renumbers the records: invalidate()
+    uint32_t top_limit = 384;
+
+    // The records are those of `tris`, `nodes` and `mats` as they are now: returns at once when they
+    // already are, else validates and packs on the host, uploads, and only then remembers the buffers.
+    // mats null (ray queries without a material buffer): no material is packed and no material index
+    // checked; a later call with materials packs and checks again.
+    int prepare(rt_context ctx, rt_mem tris, rt_mem nodes, rt_mem mats);
+    // Bounds from the moved triangles on the device, into `nodes` and every record (rt_refit.hip); a
+    // full prepare() first unless the scene is structurally current.  Materials stay as packed.
+    int refit(rt_context ctx, rt_mem tris, rt_mem nodes, rt_mem mats);
+    // the next prepare() or refit() prepares in full
+    void invalidate() { for_nodes_ = nullptr; }
+    void release();
+
+    uint32_t n_nodes() const { return n_nodes_; }
+    uint32_t n_tris() const { return n_tris_; }
+    uint32_t n_mats() const { return n_mats_; }
+    uint32_t n_top() const { return n_top_; }
+    bool oct_ok() const { return oct_ok_; }  // every leaf fits the octant records' inline {first, count}
+    uint32_t goct_b() const { return goct_b_; }  // the regrouped records' B planes (float4 offset)
+    const float4* packed_tris() const { return packed_tris_; }
+    const float4* shade_tris() const { return shade_tris_; }  // compact shading records (normals + mtlIndex)
+    // compact materials, two tables of n_mats: IEEE divisions (pinned, devicelib), then the shipped policy's
+    const float4* shade_mats() const { return shade_mats_; }
+    const float4* oct_nodes() const { return oct_nodes_; }    // [node][octant] 2 x float4 (LDS-resident scenes)
+    const float4* g_nodes() const { return g_nodes_; }        // 64-B node records, top of the tree first
+    // regrouped octant records for the HBM/L2 walk (RT_GOCT_GROUP), null when this scene has none
+    const float4* goct() const { return goct_b_ ? goct_nodes_ : nullptr; }
+    // rtDiagScenePrepares
+    uint64_t full_prepares() const { return full_prepares_; }
+    uint64_t refits() const { return refits_; }
+
+private:
+    // a bound buffer, or its contents, differ from what the records were packed from
+    bool stale(rt_mem tris, rt_mem nodes, rt_mem mats) const {
+        return for_tris_ != tris || tris_gen_ != tris->generation || for_nodes_ != nodes ||
+               nodes_gen_ != nodes->generation || (mats && (for_mats_ != mats || mats_gen_ != mats->generation));
+    }
+    // The stricter rule of the refit, which validates nothing: the records come from these buffers and
+    // no writer that may change topology or material indices has touched them since the last full
+    // preparation (rt_mem_s::structural).  Positions, normals and bounds may have moved.
+    bool structurally_current(rt_mem tris, rt_mem nodes) const {
+        return for_tris_ == tris && for_nodes_ == nodes && tris_struct_ == tris->structural &&
+               nodes_struct_ == nodes->structural;
+    }
+    int allocate(uint32_t n_nodes, uint32_t n_tris, uint32_t n_mats, size_t goct_words);
+
+    // provenance: the buffers packed from, their generations then, their structural generations at
+    // the last full preparation
+    rt_mem for_tris_ = nullptr, for_nodes_ = nullptr, for_mats_ = nullptr;
+    uint64_t tris_gen_ = 0, nodes_gen_ = 0, mats_gen_ = 0;
+    uint64_t tris_struct_ = 0, nodes_struct_ = 0;
+    uint32_t n_nodes_ = 0, n_tris_ = 0, n_mats_ = 0, n_top_ = 0, goct_b_ = 0;
+    bool oct_ok_ = false;
+    uint64_t full_prepares_ = 0, refits_ = 0;
+    // device records and their capacities (float4s)
+    float4 *packed_tris_ = nullptr, *shade_tris_ = nullptr, *shade_mats_ = nullptr;
+    float4 *oct_nodes_ = nullptr, *goct_nodes_ = nullptr, *g_nodes_ = nullptr;
+    size_t packed_tris_cap_ = 0, shade_tris_cap_ = 0, shade_mats_cap_ = 0;
+    size_t oct_nodes_cap_ = 0, goct_nodes_cap_ = 0, g_nodes_cap_ = 0;
+    // device refit: node -> parent, then node -> g_nodes record (n_nodes words each), uploaded by the
+    // full preparation; the climb's arrival counters
+    uint32_t *refit_links_ = nullptr, *refit_arrivals_ = nullptr;
+    size_t refit_links_cap_ = 0, refit_arrivals_cap_ = 0;
+};
+
+}  // namespace rti

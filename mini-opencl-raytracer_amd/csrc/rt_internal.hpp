@@ -93,7 +93,7 @@ struct rt_mem_s {
     // "structural" generation: bumped by every writer that may change topology or material indices
     // -- all of them but rtEnqueueUpdateVertices and rtRefitBVH, which touch positions, normals and
     // bounds only.  A kernel whose packed scene has the buffers' structural generations may refit on
-    // the device without validating again (rt_capi.cpp: rtRefitBVH)
+    // the device without validating again (rt_device_scene.hpp: DeviceScene::refit)
     uint64_t structural = 0;
     // a copy-engine gather plan writes into this buffer (the root's destination, rt_comm.cpp):
     // rtReleaseBuffer then only marks it, and the plan frees it when it lets go (rti::unpin)
@@ -112,6 +112,15 @@ inline int map_hip(hipError_t e) {
         case hipErrorLaunchOutOfResources: return RT_OUT_OF_RESOURCES;
         default: return RT_INVALID_OPERATION;
     }
+}
+
+// The device wrote (or is about to write) `m` behind the host's back: its shadow is stale and every
+// scene packed from it is too.  structural: the writer may have changed topology or material indices
+// -- everyone but rtEnqueueUpdateVertices and the refit (rt_mem_s::structural).
+inline void mark_device_write(rt_mem m, bool structural) {
+    m->shadow_valid = false;
+    ++m->generation;
+    if (structural) ++m->structural;
 }
 
 // Launch the coalesced per-frame launches of `ctx`, if any (rt_capi.cpp).  Returns their error,

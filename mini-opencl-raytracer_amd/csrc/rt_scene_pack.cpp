@@ -1,5 +1,5 @@
 // rt_scene_pack.cpp -- validation of the flattened BVH and the node records packed from it.
-// Pure host code (no HIP): prepare_scene (rt_capi.cpp) owns the device buffers and the copies.
+// Pure host code (no HIP): rti::DeviceScene (rt_device_scene.cpp) owns the device buffers and the copies.
 #include "rt_scene_pack.hpp"
 
 #include <algorithm>
@@ -244,6 +244,38 @@ void build_refit_links(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<u
         }
         out[(size_t)n + i] = slot_of[i];
     }
+}
+
+// The whole host half of a scene preparation, in the order a launch has always run it: buffer sizes,
+// the tree, the material indices (only against a bound material buffer), the node-index width; then
+// every packer.  The regrouped records exist for scenes whose octant records hold every leaf and whose
+// walk words stay below the leaf codes.
+int pack_scene_host(const SceneBytes& in, uint32_t top_limit, HostPack* out) {
+    if (in.tris_size < sizeof(rt_cl_triangle) || in.nodes_size < sizeof(rt_cl_bvh_node) ||
+        (in.mats && in.mats_size < sizeof(rt_cl_material)))
+        return RT_INVALID_MEM_OBJECT;
+    const rt_cl_triangle* tr = reinterpret_cast<const rt_cl_triangle*>(in.tris);
+    const rt_cl_bvh_node* nd = reinterpret_cast<const rt_cl_bvh_node*>(in.nodes);
+    HostPack& p = *out;
+    p = HostPack();
+    p.n_tris = (uint32_t)(in.tris_size / sizeof(rt_cl_triangle));
+    p.n_mats = in.mats ? (uint32_t)(in.mats_size / sizeof(rt_cl_material)) : 0u;
+    const uint32_t n_buf = (uint32_t)(in.nodes_size / sizeof(rt_cl_bvh_node));
+    // (n_nodes: the tree's nodes, a prefix of the buffer)
+    const int rc = check_nodes(nd, n_buf, p.n_tris, &p.depth, &p.n_nodes);
+    if (rc) return rc;
+    for (uint32_t i = 0; in.mats && i < p.n_tris; ++i)
+        if (tr[i].mtlIndex >= p.n_mats) return RT_INVALID_MEM_OBJECT;
+    const uint32_t nn = p.n_nodes;
+    if (nn >= (1u << 30)) return RT_INVALID_MEM_OBJECT;  // node indices share a word with the axis
+    std::vector<uint32_t> skips, slot_of;
+    build_skips(nd, nn, skips);
+    build_global_nodes(nd, nn, skips, top_limit, p.global_nodes, &p.n_top, &slot_of);
+    build_refit_links(nd, nn, slot_of, p.refit_links);
+    p.oct_ok = build_oct_nodes(nd, nn, skips, p.oct_nodes);
+    if (RT_GOCT_GROUP && p.oct_ok && (uint64_t)(nn + RT_GOCT_GROUP) * 8u < kLeafMin)
+        build_oct_nodes_grouped(p.oct_nodes, nn, RT_GOCT_GROUP, p.goct_nodes, &p.goct_b);
+    return RT_SUCCESS;
 }
 
 }  // namespace rtp

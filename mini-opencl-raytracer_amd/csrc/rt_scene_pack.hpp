@@ -2,6 +2,7 @@
 // turns a malformed scene into an error code, never a wild GPU walk.  No HIP here.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include <vector>
@@ -44,5 +45,30 @@ void build_global_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<
                         std::vector<uint32_t>* slot_of = nullptr);
 void build_refit_links(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& slot_of,
                        std::vector<uint32_t>& out);
+
+// The bytes of the caller's three scene buffers (mats null: nothing is bound, as for ray queries).
+struct SceneBytes {
+    const uint8_t* tris = nullptr;
+    size_t tris_size = 0;
+    const uint8_t* nodes = nullptr;
+    size_t nodes_size = 0;
+    const uint8_t* mats = nullptr;
+    size_t mats_size = 0;
+};
+
+// Everything the host derives from a validated scene: what rti::DeviceScene uploads and remembers.
+struct HostPack {
+    uint32_t n_nodes = 0, n_tris = 0, n_mats = 0;
+    int depth = 0;
+    uint32_t n_top = 0;   // global records staged in LDS
+    bool oct_ok = false;  // every leaf fits the octant records' inline {first, count}
+    uint32_t goct_b = 0;  // float4 offset of the regrouped records' B planes (0: none)
+    std::vector<uint32_t> global_nodes, refit_links, oct_nodes;
+    std::vector<uint32_t> goct_nodes;  // empty when the scene has none
+};
+
+// Validate the scene and pack every record (top_limit: build_global_nodes' `top`).  On an error
+// `out` holds nothing to be used.
+int pack_scene_host(const SceneBytes& in, uint32_t top_limit, HostPack* out);
 
 }  // namespace rtp
