@@ -12,9 +12,11 @@
 // launch that uses them (child indices strictly increasing, leaf ranges inside the
 // triangle array, material indices in range, depth <= 64), so a malformed scene is an
 // error code, never an out-of-bounds or non-terminating GPU walk.
-// That validation and the record packing live in rt_scene_pack.cpp, and how a launch hands its
-// work out in rt_launch_plan.cpp (both pure host code); the packed scene and the rule that keeps it
-// current in rt_device_scene.cpp; this file keeps the other resources, the streams and the launches.
+// That validation and the record packing live in rt_scene_pack.cpp, how a launch hands its work out
+// in rt_launch_plan.cpp, and rtKernelSetTuning's knobs in rt_tuning.cpp (all pure host code); the
+// packed scene and the rule that keeps it current in rt_device_scene.cpp.  A plan names its kernel
+// by a rtk::Variant, which the launch and the occupancy cache (rt_kernels.hpp) both take.  This file
+// keeps the other resources, the streams and the launches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +37,7 @@
 #include "rt_query_plan.hpp"
 #include "rt_refit.hpp"
 #include "rt_scene_pack.hpp"
+#include "rt_tuning.hpp"
 
 namespace {
 
@@ -62,44 +65,13 @@ struct rt_kernel_s {
     float f3[3][4] = {};              // slots 11..13
     int math = RT_MATH_SHIPPED;  // the reference as its host builds it (rt_hip.h)
     int sched = RT_SCHED_STEP;
-    // step schedule thresholds (lanes), swept on MI355X: LDS scenes (camera-ray ring)
-    // profiles/r01/threshold_sweep_ring.txt, shading at 48 since work stealing (44 -> 48: fused
-    // -0.3 %, per-frame -0.5 %, profiles/r03/shade_threshold_sweep.txt); scenes read from HBM/L2
-    // keep 8 / 48
-    uint32_t refill_min = 6, shade_min = 48;
-    bool refill_min_set = false;  // RT_TUNE_REFILL_MIN given: also for small per-frame launches (below)
-    // scenes read from HBM/L2: 0 = auto (64-B node records 8 / 48; octant records 16 / 48,
-    // profiles/r02/goct_sweep.txt)
-    uint32_t refill_min_g = 0, shade_min_g = 0;
-    uint32_t w_node = 35, w_leaf = 55;         // step schedule: node / triangle step cost weights
-    uint32_t w_node_g = 0, w_leaf_g = 0;       // ... on scenes read from HBM/L2 (0: auto)
-    // pixels per work-counter fetch: bulk, and the cap of the launch-sized tail chunk (swept on
-    // MI355X: profiles/r02/chunk_sweep.txt; 128 / 64 of round 1 left the counter at its atomic
-    // throughput once sky tiles were decided at ring fill: 4K Cornell 1.01 -> 0.79 ms/frame)
-    uint32_t chunk_pixels = 0, tail_chunk = 256;  // chunk_pixels 0: auto (512; 1024 pixel-major)
-    uint32_t bulk_percent = 80;                // share of the frame handed out in bulk chunks
+    rtp::Tuning tune;  // rtKernelSetTuning's knobs (rt_tuning.hpp)
     uint32_t band_period = 1, band_phase = 0;  // 8-row band interleave (multi-GPU sharding)
     uint32_t* work_counter = nullptr;  // persistent schedules' chunk counters: [4] per render stream
     uint32_t* accum_key = nullptr;     // sky-shortcut keys: [0..3] fused frames, [4..5] per-frame (zeroed once)
     int pf_parity = 0;                 // per-frame key slot read by the next launch
     int pf_ctr = 0;                    // per-frame chunk-counter slot of the next launch (RT_PF_COUNTER_SLOTS)
-    int tile_major = -1;               // fused work order: -1 auto, 0 frame-major, 1 tile-major, 2 pixel-major
-    int pf_sky = 1;                    // per-frame sky shortcut: 0 off, 1 large launches, 2 always
-    int pf_defer = 2;                  // per-frame step launches through radiance slots + accumulation
-                                       // (0 never, 1 always, 2 while the previous one still runs)
-    uint32_t pf_defer_min = 4u << 20;  // ... (2) from this many work items per launch
-    uint32_t pf_batch = rtk::kMaxFusedFrames;  // RT_TUNE_PERFRAME_BATCH: frames coalesced per launch
-    int max_blocks = 0;                // persistent grid: workgroups per CU (0 = as many as fit)
-    int global_oct = 1;                // scenes not in LDS: walk octant records in HBM/L2 (step;
-                                       // bunny proxy 1.80 -> 1.58 ms/frame, profiles/r02/goct_sweep.txt)
     // wavefront schedule: ray queues (two sets of 4 float4 planes), hit records, stream counts
-    // (refill at 32 free lanes: bunny proxy 2.62 -> 2.45 ms/frame, profiles/r02/wavefront/sweep_bunny.txt)
-    uint32_t wf_refill_min = 32, wf_streams_per_cu = 0, wf_top_limit = 256;  // streams 0: auto
-    uint32_t query_refill_min = 32;    // ray queries: RT_TUNE_QUERY_REFILL_MIN
-    // ray queries: [math][lds][stats][bofs][any] -> workgroups per CU (0 = unknown) at query_occ_smem
-    int query_occ[3][2][2][2][2] = {};
-    size_t query_occ_smem[3][2][2][2][2] = {};
-    int wf_shade_occ[3][2] = {};       // [math][stats] -> shade workgroups per CU (0 = unknown)
     float4* wf_q[2] = {};
     float2* wf_hits = nullptr;
     size_t wf_cap = 0;                 // entries per plane
@@ -132,9 +104,7 @@ struct rt_kernel_s {
     uint64_t pf_waits = ~0ull;         // ctx->host_waits at the previous per-frame step launch
     rti::DeviceScene scene;  // the derived packed scene (rt_device_scene.hpp)
     bool last_lds = false;
-    // [sched][math][lds][stats][bofs or goct, + 2 for fused launches] -> blocks per CU (0 = unknown)
-    int occ_cache[rtk::kNumSched][3][2][2][4] = {};
-    size_t occ_smem[rtk::kNumSched][3][2][2][4] = {};
+    rtk::OccupancyCache occ;  // workgroups per CU of the kernels launched so far
 };
 
 namespace {
@@ -184,6 +154,29 @@ bool same_args(const rt_context ctx, const rt_kernel k) {
 int prepare_scene(rt_kernel k) {
     return k->scene.prepare(k->ctx, k->bufs[RT_ARG_BUFFER_SCENE], k->bufs[RT_ARG_BUFFER_NODE],
                             k->bufs[RT_ARG_BUFFER_MATERIAL]);
+}
+
+// a render launch's arguments: every slot set, the work size, the image size, the output and hit
+// buffers (what enqueue checks first, and rtEnqueueKernel before it holds a frame back)
+int check_launch_args(rt_kernel k, size_t global_work_size) {
+    for (int i = 0; i < RT_ARG_COUNT; ++i)
+        if (!k->set[i]) return RT_INVALID_KERNEL_ARGS;
+    if (global_work_size == 0 || global_work_size > 0xffffffffull) return RT_INVALID_GLOBAL_WORK_SIZE;
+    if (k->u32[RT_ARG_WIDTH] == 0 || k->u32[RT_ARG_HEIGHT] == 0) return RT_INVALID_KERNEL_ARGS;
+    if (k->bufs[RT_ARG_BUFFER_OUT]->size < global_work_size * 16) return RT_INVALID_GLOBAL_WORK_SIZE;
+    if (k->hit_ids && (k->hit_ids->size < (global_work_size + kHitPad) * 4 || k->hit_t->size < global_work_size * 4))
+        return RT_INVALID_MEM_OBJECT;
+    return RT_SUCCESS;
+}
+
+// the image size, the frame count and the camera slots
+void fill_camera(rt_kernel k, rtk::KernelArgs* a) {
+    a->width = k->u32[RT_ARG_WIDTH], a->height = k->u32[RT_ARG_HEIGHT], a->frameCount = k->u32[RT_ARG_FRAME_COUNT];
+    for (int i = 0; i < 3; ++i) {
+        a->camPos[i] = k->f3[0][i];
+        a->camFront[i] = k->f3[1][i];
+        a->camUp[i] = k->f3[2][i];
+    }
 }
 
 hipEvent_t take_event(rt_kernel k) {
@@ -514,7 +507,7 @@ int rtEnqueueKernel(rt_context ctx, rt_kernel k, size_t global_work_size) {
     // (not once a stream or a device pointer of the context has been handed out: the host may then
     // synchronise behind the library's back, e.g. hipStreamSynchronize on the exposed stream, and
     // must find every frame it enqueued launched)
-    const bool coalesce = ctx && k && k->ctx == ctx && k->pf_batch > 1 && k->sched == RT_SCHED_STEP && !k->stats &&
+    const bool coalesce = ctx && k && k->ctx == ctx && k->tune.pf_batch > 1 && k->sched == RT_SCHED_STEP && !k->stats &&
                           !k->timing && !ctx->mexposed && !ctx->dexposed;
     if (!coalesce) {
         const int rc = flush_first(ctx);
@@ -522,21 +515,13 @@ int rtEnqueueKernel(rt_context ctx, rt_kernel k, size_t global_work_size) {
     }
     int rc = ensure_device(ctx);
     if (rc) return rc;
-    for (int i = 0; i < RT_ARG_COUNT; ++i)
-        if (!k->set[i]) return RT_INVALID_KERNEL_ARGS;
-    if (global_work_size == 0 || global_work_size > 0xffffffffull) return RT_INVALID_GLOBAL_WORK_SIZE;
-    uint32_t W, H, f;
-    std::memcpy(&W, &k->u32[RT_ARG_WIDTH], 4);
-    std::memcpy(&H, &k->u32[RT_ARG_HEIGHT], 4);
-    std::memcpy(&f, &k->u32[RT_ARG_FRAME_COUNT], 4);
-    if (W == 0 || H == 0) return RT_INVALID_KERNEL_ARGS;
-    if (k->bufs[RT_ARG_BUFFER_OUT]->size < global_work_size * 16) return RT_INVALID_GLOBAL_WORK_SIZE;
-    if (k->hit_ids && (k->hit_ids->size < (global_work_size + kHitPad) * 4 || k->hit_t->size < global_work_size * 4))
-        return RT_INVALID_MEM_OBJECT;
+    rc = check_launch_args(k, global_work_size);
+    if (rc) return rc;
+    const uint32_t f = k->u32[RT_ARG_FRAME_COUNT];
     // an error of an earlier held launch is reported now, and this frame is not queued: the
     // caller retrying it starts a fresh run instead of accumulating it twice
     if (ctx->pend_error != RT_SUCCESS) return pending_error(ctx, RT_SUCCESS);
-    if (ctx->pend_k == k && ctx->pend_gws == global_work_size && ctx->pend_n < k->pf_batch &&
+    if (ctx->pend_k == k && ctx->pend_gws == global_work_size && ctx->pend_n < k->tune.pf_batch &&
         f == ctx->pend_f0 + ctx->pend_n && f != 0u && same_args(ctx, k)) {
         ++ctx->pend_n;  // the next frame of the run
         return RT_SUCCESS;
@@ -606,28 +591,10 @@ static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, size_t global_work_s
     in.n_nodes = sc.n_nodes(), in.n_tris = sc.n_tris(), in.n_mats = sc.n_mats(), in.n_top = sc.n_top();
     in.oct_ok = sc.oct_ok();
     in.goct_available = sc.goct() != nullptr, in.goct_b = sc.goct_b();
-    in.force_global = k->force_global, in.global_oct = k->global_oct;
-    in.refill_min = k->refill_min, in.shade_min = k->shade_min, in.refill_min_set = k->refill_min_set;
-    in.refill_min_g = k->refill_min_g, in.shade_min_g = k->shade_min_g;
-    in.w_node = k->w_node, in.w_leaf = k->w_leaf, in.w_node_g = k->w_node_g, in.w_leaf_g = k->w_leaf_g;
-    in.chunk_pixels = k->chunk_pixels, in.tail_chunk = k->tail_chunk, in.bulk_percent = k->bulk_percent;
-    in.tile_major = k->tile_major, in.pf_sky = k->pf_sky, in.max_blocks = k->max_blocks;
-    in.wf_top_limit = k->wf_top_limit, in.wf_streams_per_cu = k->wf_streams_per_cu;
-    in.wf_refill_min = k->wf_refill_min;
+    in.force_global = k->force_global;
+    in.tune = k->tune;
     in.num_cus = ctx->num_cus;
     return in;
-}
-
-// workgroups per CU of the kernel the plan chose, at the plan's LDS size (cached per variant)
-static int lookup_occupancy(rt_kernel k, const rtp::LaunchPlan& p, bool fused) {
-    int& occ = k->occ_cache[p.si][k->math][p.lds][k->stats][p.var];
-    size_t& at = k->occ_smem[p.si][k->math][p.lds][k->stats][p.var];
-    if (occ == 0 || at != p.smem) {
-        occ = p.wf ? rtk::occupancy_wf_extend(k->math, p.lds, k->stats, p.bofs, p.smem, p.goct)
-                   : rtk::occupancy_kernel_entry(p.si, k->math, p.lds, k->stats, p.bofs, p.smem, p.goct, fused);
-        at = p.smem;
-    }
-    return occ;
 }
 
 // KernelEntry's arguments: the plan's scalars plus the kernel's pointers (the radiance set and the
@@ -646,17 +613,10 @@ static void fill_args(rt_kernel k, const rtp::LaunchPlan& p, rtk::KernelArgs* ar
     a.shadeMats = sc.shade_mats() + (k->math == RT_MATH_SHIPPED ? 4 * (size_t)sc.n_mats() : 0);
     a.nMats = sc.n_mats(), a.nTris = sc.n_tris();
     a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords, a.nTop = p.nTop;
-    std::memcpy(&a.width, &k->u32[RT_ARG_WIDTH], 4);
-    std::memcpy(&a.height, &k->u32[RT_ARG_HEIGHT], 4);
-    std::memcpy(&a.frameCount, &k->u32[RT_ARG_FRAME_COUNT], 4);
+    fill_camera(k, &a);
     std::memcpy(&a.lightBounces, &k->u32[RT_ARG_LIGHT_BOUNCES], 4);
     std::memcpy(&a.lightType, &k->u32[RT_ARG_LIGHT_TYPE], 4);
     std::memcpy(&a.skyboxIntensity, &k->u32[RT_ARG_SKYBOX_INTENSITY], 4);
-    for (int i = 0; i < 3; ++i) {
-        a.camPos[i] = k->f3[0][i];
-        a.camFront[i] = k->f3[1][i];
-        a.camUp[i] = k->f3[2][i];
-    }
     a.gidBegin = p.gidBegin, a.gidEnd = p.gidEnd;
     a.rowBegin = p.rowBegin, a.rowCount = p.rowCount, a.tilesX = p.tilesX, a.nTiles = p.nTiles;
     a.bandPeriod = p.bandPeriod, a.bandPhase = p.bandPhase;
@@ -800,16 +760,8 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     int rc = ensure_device(ctx);
     if (rc) return rc;
     if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
-    for (int i = 0; i < RT_ARG_COUNT; ++i)
-        if (!k->set[i]) return RT_INVALID_KERNEL_ARGS;
-    if (global_work_size == 0 || global_work_size > 0xffffffffull) return RT_INVALID_GLOBAL_WORK_SIZE;
-    uint32_t W, H;
-    std::memcpy(&W, &k->u32[RT_ARG_WIDTH], 4);
-    std::memcpy(&H, &k->u32[RT_ARG_HEIGHT], 4);
-    if (W == 0 || H == 0) return RT_INVALID_KERNEL_ARGS;
-    if (k->bufs[RT_ARG_BUFFER_OUT]->size < global_work_size * 16) return RT_INVALID_GLOBAL_WORK_SIZE;
-    if (k->hit_ids && (k->hit_ids->size < (global_work_size + kHitPad) * 4 || k->hit_t->size < global_work_size * 4))
-        return RT_INVALID_MEM_OBJECT;
+    rc = check_launch_args(k, global_work_size);
+    if (rc) return rc;
     rc = prepare_scene(k);
     if (rc) return rc;
 
@@ -830,9 +782,9 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     // a blocking read or write) since the previous per-frame launch: no GPU-side query, which
     // would itself cost the read-back loop (an event after every render: 3.63 -> 4.07 ms/frame).
     bool defer = false;
-    if (n_frames == 1 && si == RT_SCHED_STEP && k->pf_defer) {
-        defer = k->pf_defer == 1 ||
-                (k->pf_defer == 2 && k->pf_waits == ctx->host_waits && global_work_size >= k->pf_defer_min &&
+    if (n_frames == 1 && si == RT_SCHED_STEP && k->tune.pf_defer) {
+        defer = k->tune.pf_defer == 1 ||
+                (k->tune.pf_defer == 2 && k->pf_waits == ctx->host_waits && global_work_size >= k->tune.pf_defer_min &&
                  !ctx->mexposed && !ctx->dexposed);  // (a host that can synchronise outside the library)
         k->pf_waits = ctx->host_waits;
     }
@@ -846,11 +798,9 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     rtp::LaunchPlan p;
     rc = rtp::plan_shape(in, &p);
     if (rc || p.nothing) return rc;
-    if (wf) {
-        int& occ_s = k->wf_shade_occ[k->math][k->stats];
-        if (occ_s == 0) occ_s = rtk::occupancy_wf_shade(k->math, k->stats);
-    }
-    rtp::plan_handout(in, lookup_occupancy(k, p, fused), k->wf_shade_occ[k->math][k->stats], &p);
+    const rtk::Variant& v = p.variant;
+    rtp::plan_handout(in, k->occ.get(wf ? rtk::Family::WfExtend : rtk::Family::Entry, v, p.smem),
+                      wf ? k->occ.get(rtk::Family::WfShade, v, 0) : 0, &p);
 
     // 4. the kernel's arguments
     rtk::KernelArgs a;
@@ -872,7 +822,7 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     // everything below (counter clear, timing events, the render; the accumulation when it is not
     // overlapped) goes to rstr: the main stream unless a render stream was taken above
     if (rstr == ctx->stream) ctx->mdirty = true;
-    k->last_lds = p.lds;
+    k->last_lds = v.lds();
 
     // 7. wavefront: the ray queues
     rtk::WfArgs wa{};
@@ -897,10 +847,8 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     }
     TimedLaunch timed{k, rstr, k->pending_events};
     if (!timed.begin()) return RT_OUT_OF_RESOURCES;
-    hipError_t e = wf ? rtk::launch_wavefront(a, wa, wq, wcnt, k->math, p.lds, k->stats, p.bofs, (unsigned)p.grid,
-                                              p.smem, p.grid_s, rstr, p.goct)
-                      : rtk::launch_kernel_entry(a, si, k->math, p.lds, k->stats, (unsigned)p.grid, p.smem, rstr,
-                                                 p.goct);
+    hipError_t e = wf ? rtk::launch_wavefront(a, wa, wq, wcnt, v, (unsigned)p.grid, p.smem, p.grid_s, rstr)
+                      : rtk::launch_kernel_entry(a, v, (unsigned)p.grid, p.smem, rstr);
     if (e != hipSuccess) return map_hip(e);
     timed.end();
     if (a.pfKeyIn) k->pf_parity ^= 1;
@@ -929,6 +877,7 @@ static rtp::QueryIn query_inputs(rt_context ctx, rt_kernel k, rt_mem rays, size_
     in.rays_bytes = rays->size, in.hits_bytes = hits->size;
     in.same_buffer = rays == hits;
     in.mode = mode;
+    in.math = k->math, in.stats = k->stats;
     in.oct_ok = true;
     if (packed) {
         const rti::DeviceScene& sc = k->scene;
@@ -937,9 +886,7 @@ static rtp::QueryIn query_inputs(rt_context ctx, rt_kernel k, rt_mem rays, size_
         in.goct_available = sc.goct() != nullptr, in.goct_b = sc.goct_b();
     }
     in.force_global = k->force_global;
-    in.refill_min = k->query_refill_min;
-    in.w_node = k->w_node, in.w_leaf = k->w_leaf, in.w_node_g = k->w_node_g, in.w_leaf_g = k->w_leaf_g;
-    in.max_blocks = k->max_blocks;
+    in.tune = k->tune;
     in.num_cus = ctx->num_cus;
     return in;
 }
@@ -964,13 +911,7 @@ int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t firs
     const rtp::QueryIn in = query_inputs(ctx, k, rays, first_ray, n_rays, mode, hits, true);
     rc = rtp::query_shape(in, &p);
     if (rc || p.nothing) return rc;
-    int& occ = k->query_occ[k->math][p.lds][k->stats][p.bofs][p.any];
-    size_t& at = k->query_occ_smem[k->math][p.lds][k->stats][p.bofs][p.any];
-    if (occ == 0 || at != p.smem) {
-        occ = rtk::occupancy_query(k->math, p.lds, k->stats, p.bofs, p.any, p.smem);
-        at = p.smem;
-    }
-    rtp::query_grid(in, occ, &p);
+    rtp::query_grid(in, k->occ.get(rtk::Family::Query, p.variant, p.smem), &p);
     // 4. the arguments
     rtk::KernelArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -986,10 +927,10 @@ int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t firs
     q.first = p.first, q.count = p.count, q.nUnits = p.nUnits, q.refillMin = p.refillMin;
     // 5. the launch, on the context's stream after the pending accumulations and gathers
     hipStream_t st = qs(ctx);
-    k->last_lds = p.lds;
+    k->last_lds = p.variant.lds();
     TimedLaunch timed{k, st, k->pending_events};
     if (!timed.begin()) return RT_OUT_OF_RESOURCES;
-    const hipError_t e = rtk::launch_query(a, q, k->math, p.lds, k->stats, p.bofs, p.any, p.grid, p.smem, st);
+    const hipError_t e = rtk::launch_query(a, q, p.variant, p.grid, p.smem, st);
     if (e != hipSuccess) return map_hip(e);
     timed.end();
     mark_device_write(hits, true);
@@ -1012,16 +953,9 @@ int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt
     if (global_work_size == 0 || global_work_size > 0xffffffffull) return RT_INVALID_GLOBAL_WORK_SIZE;
     rtk::KernelArgs a;
     std::memset(&a, 0, sizeof(a));
-    std::memcpy(&a.width, &k->u32[RT_ARG_WIDTH], 4);
-    std::memcpy(&a.height, &k->u32[RT_ARG_HEIGHT], 4);
-    std::memcpy(&a.frameCount, &k->u32[RT_ARG_FRAME_COUNT], 4);
+    fill_camera(k, &a);
     if (a.width == 0 || a.height == 0) return RT_INVALID_KERNEL_ARGS;
     if (rays->size / sizeof(rt_ray) < global_work_size) return RT_INVALID_BUFFER_SIZE;
-    for (int i = 0; i < 3; ++i) {
-        a.camPos[i] = k->f3[0][i];
-        a.camFront[i] = k->f3[1][i];
-        a.camUp[i] = k->f3[2][i];
-    }
     const hipError_t e =
         rtk::launch_camera_rays(a, static_cast<float4*>(rays->dptr), (uint32_t)global_work_size, k->math, qs(ctx));
     if (e != hipSuccess) return map_hip(e);
@@ -1397,76 +1331,23 @@ int rtValidateBVH(const void* nodes, size_t n_nodes, size_t n_tris, int* depth) 
 int rtKernelSetTuning(rt_kernel k, int param, int value) {
     if (!k) return RT_INVALID_KERNEL;
     flush_kernel(k);
-    auto in = [&](int lo, int hi) { return value >= lo && value <= hi; };
-    switch (param) {
-        case RT_TUNE_REFILL_MIN:
-            if (!in(1, 64)) return RT_INVALID_VALUE;
-            k->refill_min = (uint32_t)value;
-            k->refill_min_set = true;
-            break;
-        case RT_TUNE_SHADE_MIN: if (!in(1, 64)) return RT_INVALID_VALUE; k->shade_min = (uint32_t)value; break;
-        case RT_TUNE_REFILL_MIN_GLOBAL: if (!in(0, 64)) return RT_INVALID_VALUE; k->refill_min_g = (uint32_t)value; break;
-        case RT_TUNE_SHADE_MIN_GLOBAL: if (!in(0, 64)) return RT_INVALID_VALUE; k->shade_min_g = (uint32_t)value; break;
-        case RT_TUNE_STEP_WEIGHT_NODE: if (!in(1, 1000)) return RT_INVALID_VALUE; k->w_node = (uint32_t)value; break;
-        case RT_TUNE_STEP_WEIGHT_LEAF: if (!in(1, 1000)) return RT_INVALID_VALUE; k->w_leaf = (uint32_t)value; break;
-        case RT_TUNE_CHUNK_PIXELS:
-            if (!in(0, 4096) || value % 64) return RT_INVALID_VALUE;  // (0: auto)
-            k->chunk_pixels = (uint32_t)value;
-            break;
-        case RT_TUNE_TAIL_CHUNK:
-            if (!in(64, 4096) || value % 64) return RT_INVALID_VALUE;
-            k->tail_chunk = (uint32_t)value;
-            break;
-        case RT_TUNE_BULK_PERCENT: if (!in(0, 100)) return RT_INVALID_VALUE; k->bulk_percent = (uint32_t)value; break;
-        case RT_TUNE_TOP_NODES: if (!in(0, 1024)) return RT_INVALID_VALUE; k->scene.top_limit = (uint32_t)value; k->scene.invalidate(); break;
-        case RT_TUNE_TILE_MAJOR: if (!in(-1, 2)) return RT_INVALID_VALUE; k->tile_major = value; break;
-        case RT_TUNE_MAX_BLOCKS: if (!in(0, 64)) return RT_INVALID_VALUE; k->max_blocks = value; break;
-        case RT_TUNE_PERFRAME_SKY: if (!in(0, 2)) return RT_INVALID_VALUE; k->pf_sky = value; break;
-        case RT_TUNE_WF_REFILL_MIN: if (!in(1, 64)) return RT_INVALID_VALUE; k->wf_refill_min = (uint32_t)value; break;
-        case RT_TUNE_WF_STREAMS_PER_CU: if (!in(0, 64)) return RT_INVALID_VALUE; k->wf_streams_per_cu = (uint32_t)value; break;
-        case RT_TUNE_WF_TOP_NODES: if (!in(0, 1024)) return RT_INVALID_VALUE; k->wf_top_limit = (uint32_t)value; break;
-        case RT_TUNE_GLOBAL_OCT: if (!in(0, 1)) return RT_INVALID_VALUE; k->global_oct = value; break;
-        case RT_TUNE_PERFRAME_DEFER: if (!in(0, 2)) return RT_INVALID_VALUE; k->pf_defer = value; break;
-        case RT_TUNE_PERFRAME_DEFER_MIN: if (value < 0) return RT_INVALID_VALUE; k->pf_defer_min = (uint32_t)value; break;
-        case RT_TUNE_PERFRAME_BATCH: if (!in(1, (int)rtk::kMaxFusedFrames)) return RT_INVALID_VALUE; k->pf_batch = (uint32_t)value; break;
-        case RT_TUNE_STEP_WEIGHT_NODE_GLOBAL: if (!in(0, 1000)) return RT_INVALID_VALUE; k->w_node_g = (uint32_t)value; break;
-        case RT_TUNE_STEP_WEIGHT_LEAF_GLOBAL: if (!in(0, 1000)) return RT_INVALID_VALUE; k->w_leaf_g = (uint32_t)value; break;
-        case RT_TUNE_QUERY_REFILL_MIN: if (!in(1, 64)) return RT_INVALID_VALUE; k->query_refill_min = (uint32_t)value; break;
-        default: return RT_INVALID_VALUE;
+    if (param == RT_TUNE_TOP_NODES) {  // renumbers the packed node records: the scene is packed again
+        if (value < 0 || value > 1024) return RT_INVALID_VALUE;
+        k->scene.top_limit = (uint32_t)value;
+        k->scene.invalidate();
+        return RT_SUCCESS;
     }
-    return RT_SUCCESS;
+    return rtp::tuning_set(k->tune, param, value);
 }
 
 int rtKernelGetTuning(rt_kernel k, int param, int* value) {
     if (!k) return RT_INVALID_KERNEL;
     if (!value) return RT_INVALID_VALUE;
-    switch (param) {
-        case RT_TUNE_REFILL_MIN: *value = (int)k->refill_min; break;
-        case RT_TUNE_SHADE_MIN: *value = (int)k->shade_min; break;
-        case RT_TUNE_REFILL_MIN_GLOBAL: *value = (int)k->refill_min_g; break;
-        case RT_TUNE_SHADE_MIN_GLOBAL: *value = (int)k->shade_min_g; break;
-        case RT_TUNE_STEP_WEIGHT_NODE: *value = (int)k->w_node; break;
-        case RT_TUNE_STEP_WEIGHT_LEAF: *value = (int)k->w_leaf; break;
-        case RT_TUNE_CHUNK_PIXELS: *value = (int)k->chunk_pixels; break;
-        case RT_TUNE_TAIL_CHUNK: *value = (int)k->tail_chunk; break;
-        case RT_TUNE_BULK_PERCENT: *value = (int)k->bulk_percent; break;
-        case RT_TUNE_TOP_NODES: *value = (int)k->scene.top_limit; break;
-        case RT_TUNE_TILE_MAJOR: *value = k->tile_major; break;
-        case RT_TUNE_MAX_BLOCKS: *value = k->max_blocks; break;
-        case RT_TUNE_PERFRAME_SKY: *value = k->pf_sky; break;
-        case RT_TUNE_WF_REFILL_MIN: *value = (int)k->wf_refill_min; break;
-        case RT_TUNE_WF_STREAMS_PER_CU: *value = (int)k->wf_streams_per_cu; break;
-        case RT_TUNE_WF_TOP_NODES: *value = (int)k->wf_top_limit; break;
-        case RT_TUNE_GLOBAL_OCT: *value = k->global_oct; break;
-        case RT_TUNE_PERFRAME_DEFER: *value = k->pf_defer; break;
-        case RT_TUNE_PERFRAME_DEFER_MIN: *value = (int)k->pf_defer_min; break;
-        case RT_TUNE_PERFRAME_BATCH: *value = (int)k->pf_batch; break;
-        case RT_TUNE_STEP_WEIGHT_NODE_GLOBAL: *value = (int)k->w_node_g; break;
-        case RT_TUNE_STEP_WEIGHT_LEAF_GLOBAL: *value = (int)k->w_leaf_g; break;
-        case RT_TUNE_QUERY_REFILL_MIN: *value = (int)k->query_refill_min; break;
-        default: return RT_INVALID_VALUE;
+    if (param == RT_TUNE_TOP_NODES) {
+        *value = (int)k->scene.top_limit;
+        return RT_SUCCESS;
     }
-    return RT_SUCCESS;
+    return rtp::tuning_get(k->tune, param, value);
 }
 
 int rtContextSetAccumOverlap(rt_context ctx, int enable) {

@@ -1,7 +1,8 @@
 // rt_kernels.hip -- KernelEntry entry points for the pinned and devicelib math policies,
-// the scene packing kernels and the host-side launch helpers.  The device code is
-// rt_kernels_body.hpp; the shipped policy lives in rt_kernels_shipped.hip.
-#include "rt_kernels_body.hpp"
+// the scene packing kernels and the host-side launch helpers: one rtk::Policy table per math
+// policy (the shipped one from rt_kernels_shipped.hip), through which every launcher and the
+// occupancy cache pick their kernel.  The device code is rt_kernels_body.hpp.
+#include "rt_kernel_pick.hpp"
 
 #pragma clang fp contract(off)
 
@@ -73,47 +74,30 @@ __global__ void pack_tris(const rt_cl_triangle* __restrict__ in, float4* __restr
 // ---- host-side launch helpers ------------------------------------------------------------
 namespace rtk {
 
-// Kernel variants: [schedule][math][scene in LDS][stats].
-
-template <class M, bool L, bool S, int kMode>
-static KernelFn pick_step(bool bofs, bool goct) {
-    if (M::kId == MathDeviceLib::kId) {
-        if (!L) return goct ? kernel_entry_step_devicelib_goct<S, kMode> : kernel_entry_step_devicelib_global<S, kMode>;
-        return bofs ? kernel_entry_step_devicelib_lds<S, true, kMode> : kernel_entry_step_devicelib_lds<S, false, kMode>;
+template <>
+struct StepEntry<MathDeviceLib> {
+    template <bool S, int kMode>
+    static KernelFn get(Walk w) {
+        switch (w) {
+            case Walk::Lds: return kernel_entry_step_devicelib_lds<S, false, kMode>;
+            case Walk::LdsB: return kernel_entry_step_devicelib_lds<S, true, kMode>;
+            case Walk::GlobalOct: return kernel_entry_step_devicelib_goct<S, kMode>;
+            default: return kernel_entry_step_devicelib_global<S, kMode>;
+        }
     }
-    if (!L) return goct ? kernel_entry_step_pinned<true, S, false, true, kMode> : kernel_entry_step_pinned<false, S, false, false, kMode>;
-    return bofs ? kernel_entry_step_pinned<true, S, true, false, kMode> : kernel_entry_step_pinned<true, S, false, false, kMode>;
-}
-template <class M, bool L, bool S>
-static KernelFn pick_sched(int sched, bool bofs, bool goct, bool fused) {
-    if (sched == kSchedStep) {
-        if constexpr (S || !RT_SPECIALIZE_FUSED)
-            return pick_step<M, L, S, 0>(bofs, goct);
-        else
-            return fused ? pick_step<M, L, S, 1>(bofs, goct) : pick_step<M, L, S, 2>(bofs, goct);
+};
+template <>
+struct StepEntry<MathPinned> {
+    template <bool S, int kMode>
+    static KernelFn get(Walk w) {
+        switch (w) {
+            case Walk::Lds: return kernel_entry_step_pinned<true, S, false, false, kMode>;
+            case Walk::LdsB: return kernel_entry_step_pinned<true, S, true, false, kMode>;
+            case Walk::GlobalOct: return kernel_entry_step_pinned<true, S, false, true, kMode>;
+            default: return kernel_entry_step_pinned<false, S, false, false, kMode>;
+        }
     }
-    return kernel_entry<M, L, S>;
-}
-
-// bofs: LDS node records with the B planes at kOctB (KernelArgs::octB == kOctB); goct: a scene
-// too large for LDS walked through its octant records in HBM/L2 (step schedule); fused: a fused
-// frames launch (KernelArgs::radBuf set)
-static KernelFn pick(int sched, int math, bool lds, bool stats, bool bofs, bool goct, bool fused) {
-    if (math == MathShipped::kId) return pick_shipped(sched, lds, stats, bofs, goct, fused);
-    if (math == MathDeviceLib::kId) {
-        if (lds) return stats ? pick_sched<MathDeviceLib, true, true>(sched, bofs, false, fused) : pick_sched<MathDeviceLib, true, false>(sched, bofs, false, fused);
-        return stats ? pick_sched<MathDeviceLib, false, true>(sched, bofs, goct, fused) : pick_sched<MathDeviceLib, false, false>(sched, bofs, goct, fused);
-    }
-    if (lds) return stats ? pick_sched<MathPinned, true, true>(sched, bofs, false, fused) : pick_sched<MathPinned, true, false>(sched, bofs, false, fused);
-    return stats ? pick_sched<MathPinned, false, true>(sched, bofs, goct, fused) : pick_sched<MathPinned, false, false>(sched, bofs, goct, fused);
-}
-
-hipError_t launch_kernel_entry(const KernelArgs& a, int sched, int math, bool lds, bool stats, unsigned grid,
-                               size_t smem, hipStream_t st, bool goct) {
-    KernelFn fn = pick(sched, math, lds, stats, lds && a.octB == kOctB, goct, a.radBuf != nullptr);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(256), smem, st, a);
-    return hipGetLastError();
-}
+};
 
 template <class M>
 __global__ __launch_bounds__(256) RT_ACCUM_OCC void accum_frames(KernelArgs a, const uint32_t* key) {
@@ -124,37 +108,34 @@ __global__ void accum_key(KernelArgs a, uint32_t* key) {
     accum_key_body<M>(a, key);
 }
 
-hipError_t launch_accum_frames(const KernelArgs& a, int math, uint32_t* key, hipStream_t st) {
-    if (math == MathShipped::kId) return launch_accum_frames_shipped(a, key, st);
-    const dim3 grid((a.nTiles + kAccumWgWaves - 1u) / kAccumWgWaves);
-    if (math == MathDeviceLib::kId) {
-        hipLaunchKernelGGL(accum_key<MathDeviceLib>, dim3(1), dim3(64), 0, st, a, key);
-        hipLaunchKernelGGL(accum_frames<MathDeviceLib>, grid, dim3(64 * kAccumWgWaves), 0, st, a, key);
-    } else {
-        hipLaunchKernelGGL(accum_key<MathPinned>, dim3(1), dim3(64), 0, st, a, key);
-        hipLaunchKernelGGL(accum_frames<MathPinned>, grid, dim3(64 * kAccumWgWaves), 0, st, a, key);
-    }
+// the kernels of a math policy (pack_mats: the IEEE material records serve both policies of this TU)
+static const Policy& policy(int math) {
+    static const Policy devicelib = {pick_entry<MathDeviceLib>,   wf_pick<MathDeviceLib>,  query_pick<MathDeviceLib>,
+                                     accum_frames<MathDeviceLib>, accum_key<MathDeviceLib>, camera_rays<MathDeviceLib>,
+                                     pack_mats};
+    static const Policy pinned = {pick_entry<MathPinned>,   wf_pick<MathPinned>,  query_pick<MathPinned>,
+                                  accum_frames<MathPinned>, accum_key<MathPinned>, camera_rays<MathPinned>,
+                                  pack_mats};
+    return math == MathShipped::kId ? shipped_policy() : math == MathDeviceLib::kId ? devicelib : pinned;
+}
+
+hipError_t launch_kernel_entry(const KernelArgs& a, const Variant& v, unsigned grid, size_t smem, hipStream_t st) {
+    hipLaunchKernelGGL(policy(v.math).entry(v), dim3(grid), dim3(256), smem, st, a);
     return hipGetLastError();
 }
 
-int occupancy_kernel_entry(int sched, int math, bool lds, bool stats, bool bofs, size_t smem, bool goct, bool fused) {
-    int blocks = 0;
-    KernelFn fn = pick(sched, math, lds, stats, lds && bofs, goct, fused);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, 256, smem) != hipSuccess) return 1;
-    return blocks > 0 ? blocks : 1;
+hipError_t launch_accum_frames(const KernelArgs& a, int math, uint32_t* key, hipStream_t st) {
+    const Policy& p = policy(math);
+    const dim3 grid((a.nTiles + kAccumWgWaves - 1u) / kAccumWgWaves);
+    hipLaunchKernelGGL(p.accum_key, dim3(1), dim3(64), 0, st, a, key);
+    hipLaunchKernelGGL(p.accum_frames, grid, dim3(64 * kAccumWgWaves), 0, st, a, key);
+    return hipGetLastError();
 }
 
 // ---- wavefront schedule ------------------------------------------------------------------------
-static WfKernels pick_wf(int math, bool lds, bool stats, bool bofs, bool goct) {
-    if (math == MathShipped::kId) return pick_wf_shipped(lds, stats, bofs, goct);
-    if (math == MathDeviceLib::kId) return wf_pick<MathDeviceLib>(lds, stats, bofs, goct);
-    return wf_pick<MathPinned>(lds, stats, bofs, goct);
-}
-
-hipError_t launch_wavefront(const KernelArgs& a, WfArgs w, float4* const q[2], uint32_t* const cnt[2], int math,
-                            bool lds, bool stats, bool bofs, unsigned grid_e, size_t smem_e, unsigned grid_s,
-                            hipStream_t st, bool goct) {
-    const WfKernels kf = pick_wf(math, lds, stats, bofs, goct);
+hipError_t launch_wavefront(const KernelArgs& a, WfArgs w, float4* const q[2], uint32_t* const cnt[2],
+                            const Variant& v, unsigned grid_e, size_t smem_e, unsigned grid_s, hipStream_t st) {
+    const WfKernels kf = policy(v.math).wavefront(v);
     for (int b = 0; b < a.lightBounces; ++b) {
         w.bounce = (uint32_t)b;
         w.inQ = q[b & 1];
@@ -167,50 +148,36 @@ hipError_t launch_wavefront(const KernelArgs& a, WfArgs w, float4* const q[2], u
     return hipGetLastError();
 }
 
-int occupancy_wf_extend(int math, bool lds, bool stats, bool bofs, size_t smem, bool goct) {
-    int blocks = 0;
-    const WfKernels kf = pick_wf(math, lds, stats, lds && bofs, goct);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kf.extend, kWfExtendThreads, smem) != hipSuccess)
-        return 1;
-    return blocks > 0 ? blocks : 1;
-}
-
-int occupancy_wf_shade(int math, bool stats) {
-    int blocks = 0;
-    const WfKernels kf = pick_wf(math, false, stats, false, false);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kf.shade, kWfShadeThreads, 0) != hipSuccess) return 1;
-    return blocks > 0 ? blocks : 1;
-}
-
 // ---- ray queries (rt_query.hpp) ------------------------------------------------------------------
-static QueryKernelFn pick_query(int math, bool lds, bool stats, bool bofs, bool any) {
-    if (math == MathShipped::kId) return pick_query_shipped(lds, stats, bofs, any);
-    if (math == MathDeviceLib::kId) return query_pick<MathDeviceLib>(lds, stats, bofs, any);
-    return query_pick<MathPinned>(lds, stats, bofs, any);
-}
-
-hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, int math, bool lds, bool stats, bool bofs, bool any,
-                        unsigned grid, size_t smem, hipStream_t st) {
-    hipLaunchKernelGGL(pick_query(math, lds, stats, lds && bofs, any), dim3(grid), dim3(kQueryThreads), smem, st, a, q);
+hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, const Variant& v, unsigned grid, size_t smem,
+                        hipStream_t st) {
+    hipLaunchKernelGGL(policy(v.math).query(v), dim3(grid), dim3(kQueryThreads), smem, st, a, q);
     return hipGetLastError();
-}
-
-int occupancy_query(int math, bool lds, bool stats, bool bofs, bool any, size_t smem) {
-    int blocks = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, pick_query(math, lds, stats, lds && bofs, any),
-                                                     kQueryThreads, smem) != hipSuccess)
-        return 1;
-    return blocks > 0 ? blocks : 1;
 }
 
 hipError_t launch_camera_rays(const KernelArgs& a, float4* rays, uint32_t n, int math, hipStream_t st) {
-    if (math == MathShipped::kId) return launch_camera_rays_shipped(a, rays, n, st);
     const dim3 grid((unsigned)(((uint64_t)n + 255u) / 256u));
-    if (math == MathDeviceLib::kId)
-        hipLaunchKernelGGL(camera_rays<MathDeviceLib>, grid, dim3(256), 0, st, a, rays, n);
-    else
-        hipLaunchKernelGGL(camera_rays<MathPinned>, grid, dim3(256), 0, st, a, rays, n);
+    hipLaunchKernelGGL(policy(math).camera_rays, grid, dim3(256), 0, st, a, rays, n);
     return hipGetLastError();
+}
+
+// ---- occupancy ---------------------------------------------------------------------------------
+int OccupancyCache::get(Family f, const Variant& v, size_t smem) {
+    Entry& c = e[(int)f][v.slot()];
+    if (c.blocks != 0 && c.smem == smem) return c.blocks;
+    const Policy& p = policy(v.math);
+    const void* fn = nullptr;
+    int threads = 256;
+    switch (f) {
+        case Family::Entry: fn = reinterpret_cast<const void*>(p.entry(v)); break;
+        case Family::WfExtend: fn = reinterpret_cast<const void*>(p.wavefront(v).extend), threads = kWfExtendThreads; break;
+        case Family::WfShade: fn = reinterpret_cast<const void*>(p.wavefront(v).shade), threads = kWfShadeThreads; break;
+        case Family::Query: fn = reinterpret_cast<const void*>(p.query(v)), threads = kQueryThreads; break;
+    }
+    int blocks = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, threads, smem) != hipSuccess) blocks = 1;
+    c = Entry{blocks > 0 ? blocks : 1, smem};
+    return c.blocks;
 }
 
 // rtDiagPinnedMath: the pinned policy's builtins, element-wise (tests)
@@ -243,10 +210,9 @@ hipError_t launch_pack(const rt_cl_triangle* tris, uint32_t n_tris, float4* pt, 
     if (n_tris) hipLaunchKernelGGL(pack_shade, dim3((n_tris + 255) / 256), dim3(256), 0, st, tris, ps, n_tris);
     if (n_mats) hipLaunchKernelGGL(pack_mats, dim3((n_mats + 255) / 256), dim3(256), 0, st, mats, pm, n_mats);
     // the shipped policy's material records (2.5-ulp divisions) follow the IEEE ones
-    if (n_mats) {
-        hipError_t e = launch_pack_mats_shipped(mats, n_mats, pm + 4 * (size_t)n_mats, st);
-        if (e != hipSuccess) return e;
-    }
+    if (n_mats)
+        hipLaunchKernelGGL(shipped_policy().pack_mats, dim3((n_mats + 255) / 256), dim3(256), 0, st, mats,
+                           pm + 4 * (size_t)n_mats, n_mats);
     return hipGetLastError();
 }
 

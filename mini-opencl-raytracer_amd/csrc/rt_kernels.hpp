@@ -1,4 +1,6 @@
-// rt_kernels.hpp -- launch interface between the C ABI (rt_capi.cpp) and the kernels.
+// rt_kernels.hpp -- launch interface between the C ABI (rt_capi.cpp) and the kernels: the argument
+// structs, one launcher per kernel family taking the rtk::Variant (rt_layout.hpp) its plan chose,
+// the occupancy cache keyed by the same Variant, and the table of kernels a math policy provides.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -92,12 +94,8 @@ struct WfKernels {
 };
 // the launches of one wavefront render: for b < lightBounces, extend(b) then shade(b); queues and
 // counts alternate between q[0]/q[1] and cnt[0]/cnt[1]
-hipError_t launch_wavefront(const KernelArgs& a, WfArgs w, float4* const q[2], uint32_t* const cnt[2], int math,
-                            bool lds, bool stats, bool bofs, unsigned grid_e, size_t smem_e, unsigned grid_s,
-                            hipStream_t st, bool goct);
-int occupancy_wf_extend(int math, bool lds, bool stats, bool bofs, size_t smem, bool goct);
-int occupancy_wf_shade(int math, bool stats);
-WfKernels pick_wf_shipped(bool lds, bool stats, bool bofs, bool goct);
+hipError_t launch_wavefront(const KernelArgs& a, WfArgs w, float4* const q[2], uint32_t* const cnt[2],
+                            const Variant& v, unsigned grid_e, size_t smem_e, unsigned grid_s, hipStream_t st);
 
 // ---- ray queries (rt_query.hpp) ------------------------------------------------------------------
 // rtEnqueueIntersectRays: KernelArgs carries the packed scene (packedTris, octNodes, nNodes, nTris,
@@ -110,36 +108,49 @@ struct QueryArgs {
     uint32_t refillMin;       // take new rays once this many lanes are free
 };
 using QueryKernelFn = void (*)(KernelArgs, QueryArgs);
-// lds: scene staged in LDS (bofs: B planes at kOctB), else octant records and triangles in HBM/L2
-hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, int math, bool lds, bool stats, bool bofs, bool any,
-                        unsigned grid, size_t smem, hipStream_t st);
-int occupancy_query(int math, bool lds, bool stats, bool bofs, bool any, size_t smem);
-QueryKernelFn pick_query_shipped(bool lds, bool stats, bool bofs, bool any);
+hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, const Variant& v, unsigned grid, size_t smem,
+                        hipStream_t st);
 // rtEnqueueCameraRays: width, height, frameCount and the camera slots of `a`; one rt_ray per work-item
 hipError_t launch_camera_rays(const KernelArgs& a, float4* rays, uint32_t n, int math, hipStream_t st);
-hipError_t launch_camera_rays_shipped(const KernelArgs& a, float4* rays, uint32_t n, hipStream_t st);
 
-// goct (step schedule, scene not in LDS): walk the octant records in HBM/L2 instead of the
-// 64-B global node records
-hipError_t launch_kernel_entry(const KernelArgs& a, int sched, int math, bool lds, bool stats, unsigned grid,
-                               size_t smem, hipStream_t st, bool goct = false);
-int occupancy_kernel_entry(int sched, int math, bool lds, bool stats, bool bofs, size_t smem, bool goct = false,
-                           bool fused = true);
+hipError_t launch_kernel_entry(const KernelArgs& a, const Variant& v, unsigned grid, size_t smem, hipStream_t st);
 // accumulate the fused frames' radiances into the output (one pixel per lane)
 // (`key`: 4 words of per-kernel state for the sky shortcut, zeroed once; accum_key_body)
 hipError_t launch_accum_frames(const KernelArgs& a, int math, uint32_t* key, hipStream_t st);
-hipError_t launch_accum_frames_shipped(const KernelArgs& a, uint32_t* key, hipStream_t st);
 hipError_t launch_pinned_math(int op, const float* a, const float* b, float* out, size_t n, hipStream_t st);
 hipError_t launch_pack(const rt_cl_triangle* tris, uint32_t n_tris, float4* pt, float4* ps,
                        const rt_cl_material* mats, uint32_t n_mats, float4* pm, hipStream_t st);
 
-// rt_kernels_shipped.hip: the MathShipped instantiations (own TU: OpenCL-default / and sqrt)
-KernelFn pick_shipped(int sched, bool lds, bool stats, bool bofs, bool goct, bool fused);
+// Workgroups per CU of a kernel at a dynamic LDS size, remembered per (kernel family, variant): the
+// runtime is asked on the first use and again when the LDS size differs.  The kernel is picked as
+// the launch picks it, from the same Variant.
+enum class Family : int { Entry, WfExtend, WfShade, Query };
+struct OccupancyCache {
+    struct Entry {
+        int blocks;   // 0: not asked yet
+        size_t smem;
+    };
+    Entry e[(int)Family::Query + 1][kVariantSlots] = {};
+    int get(Family f, const Variant& v, size_t smem);
+};
+
+// The kernels of one math policy, listed by the TU that instantiates it: rt_kernels.hip holds the
+// pinned and devicelib tables; the shipped one is all rt_kernels_shipped.hip exports (own TU:
+// OpenCL-default / and sqrt).
+struct Policy {
+    KernelFn (*entry)(const Variant&);
+    WfKernels (*wavefront)(const Variant&);
+    QueryKernelFn (*query)(const Variant&);
+    void (*accum_frames)(KernelArgs, const uint32_t*);
+    void (*accum_key)(KernelArgs, uint32_t*);
+    void (*camera_rays)(KernelArgs, float4*, uint32_t);
+    void (*pack_mats)(const rt_cl_material*, float4*, uint32_t);  // the policy's material records
+};
+const Policy& shipped_policy();
 // the step schedule's entry points are specialised per launch kind (step_body kMode: 1 fused, 2
 // per-frame); stats builds and RT_SPECIALIZE_FUSED 0 use the generic body (kMode 0)
 #ifndef RT_SPECIALIZE_FUSED
 #define RT_SPECIALIZE_FUSED 1
 #endif
-hipError_t launch_pack_mats_shipped(const rt_cl_material* mats, uint32_t n_mats, float4* pm, hipStream_t st);
 
 }  // namespace rtk

@@ -5,8 +5,9 @@
 // expansions (MathShipped::rcp/div/sqrt) and every fp-contract=on fusion as an fma at the
 // reference's expression site (madd, rt_math.hpp).  This TU is also compiled with
 // -fno-hip-fp32-correctly-rounded-divide-sqrt, so any division left to the compiler gets the
-// same OpenCL accuracy instead of the HIP default.  Only MathShipped is instantiated here.
-#include "rt_kernels_body.hpp"
+// same OpenCL accuracy instead of the HIP default.  Only MathShipped is instantiated here, and
+// the TU exports one thing: shipped_policy(), the table of its kernels (rt_kernels.hpp).
+#include "rt_kernel_pick.hpp"
 
 #pragma clang fp contract(off)
 
@@ -37,30 +38,6 @@ __global__ void pack_mats_shipped(const rt_cl_material* __restrict__ in, float4*
     material_record<MathShipped>(in[i], out + 4 * i);
 }
 
-template <bool L, bool S, int kMode>
-static KernelFn pick_step_shipped(bool bofs, bool goct) {
-    if (!L) return goct ? kernel_entry_step_shipped_goct<S, kMode> : kernel_entry_step_shipped_global<S, kMode>;
-    return bofs ? kernel_entry_step_shipped_lds<S, true, kMode> : kernel_entry_step_shipped_lds<S, false, kMode>;
-}
-template <bool L, bool S>
-static KernelFn pick_sched_shipped(int sched, bool bofs, bool goct, bool fused) {
-    if (sched == kSchedStep) {
-        if constexpr (S || !RT_SPECIALIZE_FUSED)
-            return pick_step_shipped<L, S, 0>(bofs, goct);
-        else
-            return fused ? pick_step_shipped<L, S, 1>(bofs, goct) : pick_step_shipped<L, S, 2>(bofs, goct);
-    }
-    return kernel_entry<MathShipped, L, S>;
-}
-
-KernelFn pick_shipped(int sched, bool lds, bool stats, bool bofs, bool goct, bool fused) {
-    if (lds)
-        return stats ? pick_sched_shipped<true, true>(sched, bofs, false, fused)
-                     : pick_sched_shipped<true, false>(sched, bofs, false, fused);
-    return stats ? pick_sched_shipped<false, true>(sched, bofs, goct, fused)
-                 : pick_sched_shipped<false, false>(sched, bofs, goct, fused);
-}
-
 __global__ __launch_bounds__(256) RT_ACCUM_OCC void accum_frames_shipped(KernelArgs a, const uint32_t* key) {
     accum_frames_body<MathShipped>(a, key);
 }
@@ -68,30 +45,24 @@ __global__ void accum_key_shipped(KernelArgs a, uint32_t* key) {
     accum_key_body<MathShipped>(a, key);
 }
 
-hipError_t launch_accum_frames_shipped(const KernelArgs& a, uint32_t* key, hipStream_t st) {
-    const dim3 grid((a.nTiles + kAccumWgWaves - 1u) / kAccumWgWaves);
-    hipLaunchKernelGGL(accum_key_shipped, dim3(1), dim3(64), 0, st, a, key);
-    hipLaunchKernelGGL(accum_frames_shipped, grid, dim3(64 * kAccumWgWaves), 0, st, a, key);
-    return hipGetLastError();
-}
+template <>
+struct StepEntry<MathShipped> {
+    template <bool S, int kMode>
+    static KernelFn get(Walk w) {
+        switch (w) {
+            case Walk::Lds: return kernel_entry_step_shipped_lds<S, false, kMode>;
+            case Walk::LdsB: return kernel_entry_step_shipped_lds<S, true, kMode>;
+            case Walk::GlobalOct: return kernel_entry_step_shipped_goct<S, kMode>;
+            default: return kernel_entry_step_shipped_global<S, kMode>;
+        }
+    }
+};
 
-WfKernels pick_wf_shipped(bool lds, bool stats, bool bofs, bool goct) {
-    return wf_pick<MathShipped>(lds, stats, bofs, goct);
-}
-
-QueryKernelFn pick_query_shipped(bool lds, bool stats, bool bofs, bool any) {
-    return query_pick<MathShipped>(lds, stats, bofs, any);
-}
-
-hipError_t launch_camera_rays_shipped(const KernelArgs& a, float4* rays, uint32_t n, hipStream_t st) {
-    hipLaunchKernelGGL(camera_rays<MathShipped>, dim3((unsigned)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, st, a,
-                       rays, n);
-    return hipGetLastError();
-}
-
-hipError_t launch_pack_mats_shipped(const rt_cl_material* mats, uint32_t n_mats, float4* pm, hipStream_t st) {
-    hipLaunchKernelGGL(pack_mats_shipped, dim3((n_mats + 255) / 256), dim3(256), 0, st, mats, pm, n_mats);
-    return hipGetLastError();
+const Policy& shipped_policy() {
+    static const Policy shipped = {pick_entry<MathShipped>, wf_pick<MathShipped>, query_pick<MathShipped>,
+                                   accum_frames_shipped,    accum_key_shipped,    camera_rays<MathShipped>,
+                                   pack_mats_shipped};
+    return shipped;
 }
 
 }  // namespace rtk

@@ -52,8 +52,6 @@ int plan_shape(const PlanIn& in, LaunchPlan* out) {
     const bool wf = si == rtk::kSchedWavefront;
     const bool fused = in.fused;
     const uint32_t W = in.W, n_frames = in.n_frames;
-    a.si = si;
-    a.wf = wf;
 
     uint64_t g0 = std::min<uint64_t>(in.range_first, in.gws);
     uint64_t g1 = in.range_last ? std::min<uint64_t>(in.range_last, in.gws) : in.gws;
@@ -106,9 +104,7 @@ int plan_shape(const PlanIn& in, LaunchPlan* out) {
 
     // scenes too large for LDS: the step schedule may walk the octant records in HBM/L2
     // (RT_TUNE_GLOBAL_OCT) instead of the 64-B global node records
-    const bool goct = !lds && (wf || si == rtk::kSchedStep) && in.oct_ok && in.global_oct;
-    a.lds = lds;
-    a.goct = goct;
+    const bool goct = !lds && (wf || si == rtk::kSchedStep) && in.oct_ok && in.tune.global_oct;
     a.nTop = lds || goct ? 0u : in.n_top;  // global path: top-of-tree node records staged in LDS
     a.nNodes = in.n_nodes;
     a.octStride = oct_stride(in.n_nodes);
@@ -124,18 +120,18 @@ int plan_shape(const PlanIn& in, LaunchPlan* out) {
     }
     // (octant walk: refill at 32 free lanes under the pixel-major order, 16 before: -0.5 %,
     // profiles/r05/goct_bursts_weights.txt)
-    a.refillMin = lds ? in.refill_min : in.refill_min_g ? in.refill_min_g : goct ? 32u : 8u;
-    a.shadeMin = lds ? in.shade_min : in.shade_min_g ? in.shade_min_g : 48u;
-    a.stepWeightNode = in.w_node;
-    a.stepWeightLeaf = in.w_leaf;
+    a.refillMin = lds ? in.tune.refill_min : in.tune.refill_min_g ? in.tune.refill_min_g : goct ? 32u : 8u;
+    a.shadeMin = lds ? in.tune.shade_min : in.tune.shade_min_g ? in.tune.shade_min_g : 48u;
+    a.stepWeightNode = in.tune.w_node;
+    a.stepWeightLeaf = in.tune.w_leaf;
     if (!lds) {
         // scenes in HBM/L2: a node step's loads cost more against a triangle step's than in LDS
         // (octant walk under the pixel-major order: 65 / 55 -- 35: +1.0 %, 45: +0.4 %, 80-130 the same;
         // profiles/r05/goct_bursts_weights.txt)
-        a.stepWeightNode = in.w_node_g ? in.w_node_g : goct ? 65u : in.w_node;
-        a.stepWeightLeaf = in.w_leaf_g ? in.w_leaf_g : in.w_leaf;
+        a.stepWeightNode = in.tune.w_node_g ? in.tune.w_node_g : goct ? 65u : in.tune.w_node;
+        a.stepWeightLeaf = in.tune.w_leaf_g ? in.tune.w_leaf_g : in.tune.w_leaf;
     }
-    if (wf) a.nTop = std::min(a.nTop, in.wf_top_limit);
+    if (wf) a.nTop = std::min(a.nTop, in.tune.wf_top_limit);
     a.smem =
         wf ? (lds ? ((size_t)a.octRecords + 3 * (size_t)in.n_tris) * 16 : (size_t)a.nTop * 64) +
                  (rtk::kWfExtendThreads / 64) * rtk::kWfRingBytes
@@ -147,8 +143,9 @@ int plan_shape(const PlanIn& in, LaunchPlan* out) {
     // fill; the other fused renders write a byte per path at its end
     a.flagTiles = fused && !wf && si == rtk::kSchedStep && lds ? 1u : fused && !wf && si == rtk::kSchedStep && goct ? 2u : 0u;
 
-    a.bofs = lds && a.octB == rtk::kOctB;
-    a.var = (a.bofs || goct ? 1 : 0) + (fused ? 2 : 0);  // occupancy cache: the variant slot
+    const rtk::Walk walk = lds ? (a.octB == rtk::kOctB ? rtk::Walk::LdsB : rtk::Walk::Lds)
+                               : (goct ? rtk::Walk::GlobalOct : rtk::Walk::GlobalNodes);
+    a.variant = rtk::Variant{si, in.math, walk, in.stats, fused, false};
 
     // the chunk counters start at zero: per-frame launches clear theirs here; a fused render's
     // (its radiance set's) were cleared by the accumulation that followed the set's previous render
@@ -168,11 +165,11 @@ int plan_shape(const PlanIn& in, LaunchPlan* out) {
 
 void plan_handout(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out) {
     LaunchPlan& a = *out;
-    const int si = a.si;
-    const bool wf = a.wf, lds = a.lds, fused = in.fused;
+    const int si = a.variant.sched;
+    const bool wf = a.wf(), lds = a.variant.lds(), fused = in.fused;
     const uint32_t n_frames = in.n_frames;
     const uint64_t n_tiles = a.nTiles;
-    uint64_t grid = (uint64_t)(in.max_blocks ? std::min(occ, in.max_blocks) : occ) * (uint64_t)in.num_cus;
+    uint64_t grid = (uint64_t)(in.tune.max_blocks ? std::min(occ, in.tune.max_blocks) : occ) * (uint64_t)in.num_cus;
     // tiles: one workgroup per 16x16 tile at most; persistent schedules: one 8x8 tile per wave
     // (wavefront extend: 8 waves per workgroup)
     grid = std::min<uint64_t>(grid, si == rtk::kSchedTiles ? n_tiles
@@ -195,9 +192,9 @@ void plan_handout(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out) {
         const bool pow2 = (n_frames == 2 || n_frames == 4 || n_frames == 8) && si == rtk::kSchedStep;
         const bool big = !lds && tot >= 4096u * waves;
         a.tileMajor = n_frames < 2 ? 0u
-                      : in.tile_major == 2 ? (!lds && pow2 ? 2u : 1u)
-                      : in.tile_major == 1 ? 1u
-                      : in.tile_major == 0 ? 0u
+                      : in.tune.tile_major == 2 ? (!lds && pow2 ? 2u : 1u)
+                      : in.tune.tile_major == 1 ? 1u
+                      : in.tune.tile_major == 0 ? 0u
                       : !lds && pow2       ? 2u
                       : big                ? 1u
                                            : 0u;
@@ -209,9 +206,9 @@ void plan_handout(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out) {
         // profiles/r02/multigpu/n8_chunk_sweep_*.txt); full 4K launches keep 80 %
         // bulk chunks of 512 work items, 1024 in the pixel-major order (two whole tiles x 8 frames per
         // fetch: bunny proxy -0.8 %, profiles/r05/goct_bursts_weights.txt)
-        const uint32_t chunk = in.chunk_pixels ? in.chunk_pixels : a.tileMajor == 2u ? 1024u : 512u;
+        const uint32_t chunk = in.tune.chunk_pixels ? in.tune.chunk_pixels : a.tileMajor == 2u ? 1024u : 512u;
         a.chunkPixels = chunk;
-        uint64_t bulk = tot * in.bulk_percent / 100;
+        uint64_t bulk = tot * in.tune.bulk_percent / 100;
         const uint64_t reserve = 2u * waves * chunk;
         bulk = std::min<uint64_t>(bulk, tot > reserve ? tot - reserve : 0u);
         a.chunkSplit = tot >= 2u * waves * chunk ? (uint32_t)(bulk / chunk * chunk) : 0u;
@@ -226,7 +223,7 @@ void plan_handout(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out) {
                            tot >= 256u * waves;  // (512^2 frames, ~50 work items per wave: +5 % with them)
         const uint64_t share = (tot - a.chunkSplit) * (parts ? 1u : RT_TAIL_SHARE_WAVES) / waves;
         uint32_t tail = 64;
-        while (tail * 2u <= in.tail_chunk && (uint64_t)tail * 2u * 5u <= share * 2u) tail *= 2u;
+        while (tail * 2u <= in.tune.tail_chunk && (uint64_t)tail * 2u * 5u <= share * 2u) tail *= 2u;
         a.tailChunk = tail;
         // RT_STATIC_FIRST: a per-frame launch without a bulk region starts every wave on its own tail chunk,
         // with no atomic (step_body), and the tail counter hands out from past those chunks.  (The
@@ -245,7 +242,7 @@ void plan_handout(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out) {
             // such launches (a 1080p frame: ~400 work items per wave) refill at 16 free lanes, not 6:
             // 1080p 2-bounce frames -2.8 % (4K fused launches lose 5 % at 16,
             // profiles/r06/work_handout_ab.txt)
-            if (lds && !in.refill_min_set) a.refillMin = 16u;
+            if (lds && !in.tune.refill_min_set) a.refillMin = 16u;
         }
     }
 
@@ -254,17 +251,17 @@ void plan_handout(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out) {
     // (512^2; round 6: the threshold was 1k pixels per wave before the small-launch hand-out,
     // profiles/r06/work_handout_ab.txt)
     a.use_pf_sky = !fused && si == rtk::kSchedStep &&
-                   (in.pf_sky == 2 || (in.pf_sky == 1 && a.gidEnd - a.gidBegin >= 256u * 4u * grid));
+                   (in.tune.pf_sky == 2 || (in.tune.pf_sky == 1 && a.gidEnd - a.gidBegin >= 256u * 4u * grid));
     if (wf) {
         // queues for every (frame slot, work-item) of the launch, streams of 64-entry blocks
         const uint64_t blocks = n_tiles * n_frames;
         // streams: by default one per shade workgroup the GPU holds at once, so the shade
         // launch is a single round of workgroups (no second, partly empty round)
-        const uint64_t per_cu = in.wf_streams_per_cu ? in.wf_streams_per_cu : (uint64_t)occ_shade;
+        const uint64_t per_cu = in.tune.wf_streams_per_cu ? in.tune.wf_streams_per_cu : (uint64_t)occ_shade;
         a.cap = (uint32_t)(blocks * 64);
         a.G = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)in.num_cus * per_cu));
         a.nBlocks = (uint32_t)blocks;
-        a.wfRefillMin = in.wf_refill_min;
+        a.wfRefillMin = in.tune.wf_refill_min;
         a.grid_s = a.G;  // one workgroup per stream
     }
 }

@@ -1,11 +1,15 @@
 // rt_launch_plan.hpp -- how one KernelEntry launch hands its work out, as a pure function of plain
 // values (rt_launch_plan.cpp): no HIP, no allocation, no globals.  enqueue (rt_capi.cpp) fills a
-// PlanIn, calls plan_shape, looks the kernel's occupancy up for the LDS size that gives, calls
-// plan_handout, and turns the LaunchPlan into rtk::KernelArgs, resources and launches.
+// PlanIn, calls plan_shape, looks the occupancy of the kernel that names (LaunchPlan::variant) up for
+// the LDS size it gives, calls plan_handout, and turns the LaunchPlan into rtk::KernelArgs, resources
+// and launches.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "rt_layout.hpp"
+#include "rt_tuning.hpp"
 
 namespace rtp {
 
@@ -25,24 +29,15 @@ struct PlanIn {
     bool goct_available;                    // regrouped octant records exist ...
     uint32_t goct_b;                        // ... and their B planes' float4 offset
     bool force_global;
-    int global_oct;
-    // tuning (rt_kernel_s; rtKernelSetTuning)
-    uint32_t refill_min, shade_min;
-    bool refill_min_set;
-    uint32_t refill_min_g, shade_min_g;
-    uint32_t w_node, w_leaf, w_node_g, w_leaf_g;
-    uint32_t chunk_pixels, tail_chunk, bulk_percent;
-    int tile_major, pf_sky, max_blocks;
-    uint32_t wf_top_limit, wf_streams_per_cu, wf_refill_min;
+    Tuning tune;                            // rtKernelSetTuning
     int num_cus;
 };
 
 struct LaunchPlan {
     bool nothing;                           // no work item in range / no band row: RT_SUCCESS, no launch
     // ---- plan_shape ----
-    int si;                                 // the schedule the launch runs (rtk::kSched*)
-    bool wf, lds, goct, bofs;
-    int var;                                // occupancy cache: the variant slot
+    rtk::Variant variant;                   // the kernel: the schedule the launch runs, the scene walk, ...
+    bool wf() const { return variant.sched == rtk::kSchedWavefront; }
     size_t smem;                            // dynamic LDS bytes
     // rtk::KernelArgs scalars
     uint64_t gidBegin, gidEnd;
@@ -76,7 +71,7 @@ int resolve_schedule(int sched, int32_t light_bounces);
 // make), RT_INVALID_GLOBAL_WORK_SIZE or RT_INVALID_OPERATION.
 int plan_shape(const PlanIn& in, LaunchPlan* out);
 // The grid and the work hand-out, from the occupancy (workgroups per CU) of the kernel plan_shape
-// chose at out->smem; occ_shade: the wavefront shade kernel's (read only when out->wf).
+// chose at out->smem; occ_shade: the wavefront shade kernel's (read only when out->wf()).
 void plan_handout(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out);
 
 // both steps (occupancies known beforehand: tests)

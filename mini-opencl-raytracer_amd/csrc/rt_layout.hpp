@@ -1,5 +1,6 @@
-// rt_layout.hpp -- layout constants the host side (rt_capi.cpp, rt_scene_pack.cpp,
-// rt_launch_plan.cpp) and the kernels (through rt_kernels.hpp) share.  No HIP here.
+// rt_layout.hpp -- layout constants, and the key that names a kernel variant (rtk::Variant), which
+// the host side (rt_capi.cpp, rt_scene_pack.cpp, the planners) and the kernels (through
+// rt_kernels.hpp) share.  No HIP here.
 #pragma once
 
 #include <stdint.h>
@@ -11,7 +12,6 @@ constexpr int kSchedTiles = 0;  // one pixel per lane per 16x16 tile, all bounce
 // schedule and retired in round 3; DESIGN.md section 5 keeps their numbers)
 constexpr int kSchedStep = 2;   // per-wave state machine: node / triangle steps, batched shading
 constexpr int kSchedWavefront = 4;  // extend / shade launches per bounce over HBM ray queues
-constexpr int kNumSched = 5;
 // frames per fused launch (rtEnqueueKernelFrames splits longer runs)
 constexpr uint32_t kMaxFusedFrames = 8;
 // step schedule LDS per wave: the finish queue, 64 x {radiance, gid}
@@ -38,6 +38,31 @@ constexpr uint32_t kOctBMaxStride = 64;
 constexpr uint32_t kPartStride = 256;
 constexpr uint32_t kMaxParts = 8;
 constexpr uint32_t kOctB = 8 * kOctBMaxStride;
+
+// ---- kernel variants ----
+// How a kernel reads the scene: one of four walks, so "B planes at kOctB" without LDS, or octant
+// records in HBM/L2 with the scene in LDS, cannot be written down.
+enum class Walk : int {
+    Lds = 0,          // node records, triangles and shading records staged in LDS
+    LdsB = 1,         // ... with the B planes at kOctB (KernelArgs::octB == kOctB)
+    GlobalOct = 2,    // scene too large for LDS: its octant records walked in HBM/L2
+    GlobalNodes = 3,  // ... its 64-byte node records walked in HBM/L2
+};
+// Which kernel a launch runs.  The planners (rt_launch_plan.cpp, rt_query_plan.cpp) fill one; the
+// launch and its occupancy query (rt_kernels.hpp) both pick the kernel from it.
+struct Variant {
+    int sched;    // kSched* (renders; ray queries leave it 0)
+    int math;     // RT_MATH_*
+    Walk walk;
+    bool stats;   // rt_stats counters
+    bool fused;   // the launch writes radiance slots (step schedule: the entry points' kMode)
+    bool any;     // ray queries: any-hit
+    bool lds() const { return walk == Walk::Lds || walk == Walk::LdsB; }
+    // dense index for per-variant caches, < kVariantSlots (schedules 0, 2, 4; maths 0..2)
+    int slot() const { return (((((sched >> 1) * 3 + math) * 4 + (int)walk) * 2 + stats) * 2 + fused) * 2 + any; }
+};
+constexpr int kVariantSlots = 3 * 3 * 4 * 2 * 2 * 2;
+static_assert((kSchedTiles >> 1) == 0 && (kSchedStep >> 1) == 1 && (kSchedWavefront >> 1) == 2, "Variant::slot");
 
 // ---- wavefront schedule (rt_wavefront.hpp) ----
 constexpr unsigned kWfExtendThreads = 512;  // extend workgroup: 8 waves (LDS scene staged once per 8)

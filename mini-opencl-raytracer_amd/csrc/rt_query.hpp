@@ -199,15 +199,17 @@ __global__ __launch_bounds__(256) void camera_rays(KernelArgs a, float4* rays, u
     camera_rays_body<M>(a, rays, n);
 }
 
+// (a scene not in LDS is walked through its octant records in HBM/L2)
 template <class M, bool S, bool A>
-QueryKernelFn query_pick_sa(bool lds, bool bofs) {
-    return lds ? (bofs ? query_rays<M, S, true, false, A> : query_rays<M, S, false, false, A>)
-               : query_rays<M, S, false, true, A>;
+QueryKernelFn query_pick_sa(Walk w) {
+    return w == Walk::LdsB  ? query_rays<M, S, true, false, A>
+           : w == Walk::Lds ? query_rays<M, S, false, false, A>
+                            : query_rays<M, S, false, true, A>;
 }
 template <class M>
-QueryKernelFn query_pick(bool lds, bool stats, bool bofs, bool any) {
-    if (stats) return any ? query_pick_sa<M, true, true>(lds, bofs) : query_pick_sa<M, true, false>(lds, bofs);
-    return any ? query_pick_sa<M, false, true>(lds, bofs) : query_pick_sa<M, false, false>(lds, bofs);
+QueryKernelFn query_pick(const Variant& v) {
+    if (v.stats) return v.any ? query_pick_sa<M, true, true>(v.walk) : query_pick_sa<M, true, false>(v.walk);
+    return v.any ? query_pick_sa<M, false, true>(v.walk) : query_pick_sa<M, false, false>(v.walk);
 }
 
 }  // namespace rtk

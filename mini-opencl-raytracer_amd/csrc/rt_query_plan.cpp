@@ -27,7 +27,6 @@ int query_shape(const QueryIn& in, QueryPlan* out) {
     const uint64_t end = in.first_ray + in.n_rays;
     if (end > in.rays_bytes / 32u || end > in.hits_bytes / 16u) return RT_INVALID_BUFFER_SIZE;
     if (!in.oct_ok) return RT_INVALID_OPERATION;
-    p.any = in.mode == kQueryAny;
     p.first = (uint32_t)in.first_ray;
     p.count = (uint32_t)in.n_rays;
     p.nUnits = (uint32_t)((in.n_rays + 63u) / 64u);
@@ -36,12 +35,12 @@ int query_shape(const QueryIn& in, QueryPlan* out) {
     // plus one ray ring per wave
     const size_t rings = (rtk::kQueryThreads / 64) * (size_t)rtk::kQueryRingBytes;
     const size_t scene_bytes = (size_t)oct_records(in.n_nodes) * 16 + (size_t)in.n_tris * 48;
-    p.lds = !in.force_global && scene_bytes + rings <= kQueryLdsBudget;
+    const bool lds = !in.force_global && scene_bytes + rings <= kQueryLdsBudget;
     p.nNodes = in.n_nodes;
     p.octStride = oct_stride(in.n_nodes);
     p.octB = oct_b(in.n_nodes);
     p.octRecords = oct_records(in.n_nodes);
-    if (!p.lds && RT_GOCT_GROUP && in.goct_available && in.goct_b) {
+    if (!lds && RT_GOCT_GROUP && in.goct_available && in.goct_b) {
         // regrouped records, links as walk words (build_oct_nodes_grouped), as the render's walk
         p.regrouped = true;
         p.octStride = RT_GOCT_GROUP;
@@ -49,18 +48,20 @@ int query_shape(const QueryIn& in, QueryPlan* out) {
         p.octRecords = 2u * p.octB;
         p.nNodes = RT_GOCT_END_WORD ? rtk::kEndWalk : goct_word(in.n_nodes, RT_GOCT_GROUP);  // the END word
     }
-    p.bofs = p.lds && p.octB == rtk::kOctB;
-    p.smem = (p.lds ? scene_bytes : 0) + rings;
-    p.refillMin = in.refill_min;
+    const rtk::Walk walk = lds ? (p.octB == rtk::kOctB ? rtk::Walk::LdsB : rtk::Walk::Lds) : rtk::Walk::GlobalOct;
+    p.variant = rtk::Variant{0, in.math, walk, in.stats, false, in.mode == kQueryAny};
+    p.smem = (lds ? scene_bytes : 0) + rings;
+    p.refillMin = in.tune.query_refill_min;
     // step weights: the render's, per scene path (rt_launch_plan.cpp)
-    p.stepWeightNode = p.lds ? in.w_node : in.w_node_g ? in.w_node_g : 65u;
-    p.stepWeightLeaf = p.lds ? in.w_leaf : in.w_leaf_g ? in.w_leaf_g : in.w_leaf;
+    const Tuning& t = in.tune;
+    p.stepWeightNode = lds ? t.w_node : t.w_node_g ? t.w_node_g : 65u;
+    p.stepWeightLeaf = lds ? t.w_leaf : t.w_leaf_g ? t.w_leaf_g : t.w_leaf;
     return RT_SUCCESS;
 }
 
 void query_grid(const QueryIn& in, int occ, QueryPlan* out) {
     QueryPlan& p = *out;
-    const int per_cu = std::max(1, in.max_blocks ? std::min(occ, in.max_blocks) : occ);
+    const int per_cu = std::max(1, in.tune.max_blocks ? std::min(occ, in.tune.max_blocks) : occ);
     uint64_t grid = (uint64_t)per_cu * (uint64_t)std::max(1, in.num_cus);
     // one unit per wave at least: eight waves per workgroup
     grid = std::min<uint64_t>(grid, ((uint64_t)p.nUnits + 7) / 8);

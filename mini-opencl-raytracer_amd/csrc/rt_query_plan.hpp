@@ -7,6 +7,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rt_layout.hpp"
+#include "rt_tuning.hpp"
+
 namespace rtp {
 
 constexpr int kQueryClosest = 0, kQueryAny = 1;      // RT_QUERY_CLOSEST, RT_QUERY_ANY
@@ -18,21 +21,22 @@ struct QueryIn {
     uint64_t rays_bytes, hits_bytes;     // sizes of the two buffers
     bool same_buffer;                    // rays and hits are one buffer
     int mode;                            // RT_QUERY_*
+    int math;                            // RT_MATH_*
+    bool stats;                          // rt_stats counters on
     uint32_t n_nodes, n_tris;            // the packed scene
     bool oct_ok;                         // every leaf fits the octant records
     bool goct_available;                 // regrouped octant records exist ...
     uint32_t goct_b;                     // ... and their B planes' float4 offset
     bool force_global;
-    uint32_t refill_min;                 // RT_TUNE_QUERY_REFILL_MIN
-    uint32_t w_node, w_leaf, w_node_g, w_leaf_g;  // step weights (the render's tuning)
-    int max_blocks;                      // RT_TUNE_MAX_BLOCKS
+    Tuning tune;                         // query_refill_min, max_blocks and the render's step weights
     int num_cus;
 };
 
 struct QueryPlan {
     bool nothing;                        // n_rays == 0: RT_SUCCESS, no launch
     // ---- query_shape ----
-    bool lds, bofs, any;                 // scene staged in LDS (B planes at kOctB); any-hit
+    rtk::Variant variant;                // the kernel: scene staged in LDS (B planes at kOctB) or its octant
+                                         // records walked in HBM/L2; any-hit
     bool regrouped;                      // HBM/L2 path: walk the regrouped octant records
     size_t smem;                         // dynamic LDS bytes
     uint32_t first, count;               // the range, 32-bit

@@ -372,15 +372,16 @@ __global__ __launch_bounds__(kWfShadeThreads) void wf_shade(KernelArgs a, WfArgs
 }
 
 template <class M, bool S>
-WfKernels wf_pick_s(bool lds, bool bofs, bool goct) {
-    WfKernelFn e = lds    ? (bofs ? wf_extend<M, true, S, true> : wf_extend<M, true, S, false>)
-                   : goct ? wf_extend<M, true, S, false, true>
-                          : wf_extend<M, false, S, false>;
+WfKernels wf_pick_s(Walk w) {
+    WfKernelFn e = w == Walk::LdsB        ? wf_extend<M, true, S, true>
+                   : w == Walk::Lds       ? wf_extend<M, true, S, false>
+                   : w == Walk::GlobalOct ? wf_extend<M, true, S, false, true>
+                                          : wf_extend<M, false, S, false>;
     return WfKernels{e, wf_shade<M, S>};
 }
 template <class M>
-WfKernels wf_pick(bool lds, bool stats, bool bofs, bool goct) {
-    return stats ? wf_pick_s<M, true>(lds, bofs, goct) : wf_pick_s<M, false>(lds, bofs, goct);
+WfKernels wf_pick(const Variant& v) {
+    return v.stats ? wf_pick_s<M, true>(v.walk) : wf_pick_s<M, false>(v.walk);
 }
 
 }  // namespace rtk

@@ -1,7 +1,9 @@
 // plan_main.cpp -- stand-alone driver of the launch plan (csrc/rt_launch_plan.cpp), CPU only.
-//   plan_main plan   reads one launch per line from stdin ("name=value" tokens: every PlanIn field,
-//                    occ, occ_s), prints one JSON line per launch: rc, nothing, every LaunchPlan
-//                    field, and "inv": the hand-out invariants that plan breaks ("" = none).
+//   plan_main plan   reads one launch per line from stdin ("name=value" tokens: every PlanIn field
+//                    -- the knobs of PlanIn::tune by their own names -- occ, occ_s), prints one JSON
+//                    line per launch: rc, nothing, every LaunchPlan field (the variant as si, wf,
+//                    lds, goct, bofs and var, the slot of the occupancy cache the plan once
+//                    indexed), and "inv": the hand-out invariants that plan breaks ("" = none).
 //                    tests/test_launch_plan.py compares these with tests/golden/launch_plans.json;
 //                    after a deliberate rule change this output regenerates the table.
 //   plan_main sweep  plans a sweep of sizes, frames, bands, scene paths and occupancies and checks
@@ -20,12 +22,13 @@
 #define PLAN_IN_FIELDS(X)                                                                                     \
     X(W) X(H) X(gws) X(range_first) X(range_last) X(n_frames) X(light_bounces) X(sched) X(math) X(stats)     \
     X(hit_bound) X(fused) X(overlap) X(band_period) X(band_phase) X(n_nodes) X(n_tris) X(n_mats) X(n_top)    \
-    X(oct_ok) X(goct_available) X(goct_b) X(force_global) X(global_oct) X(refill_min) X(refill_min_set)      \
-    X(shade_min) X(refill_min_g) X(shade_min_g) X(w_node) X(w_leaf) X(w_node_g) X(w_leaf_g) X(chunk_pixels)  \
-    X(tail_chunk) X(bulk_percent) X(tile_major) X(pf_sky) X(max_blocks) X(wf_top_limit) X(wf_streams_per_cu) \
-    X(wf_refill_min) X(num_cus)
+    X(oct_ok) X(goct_available) X(goct_b) X(force_global) X(num_cus)
+#define PLAN_TUNE_FIELDS(X)                                                                                   \
+    X(global_oct) X(refill_min) X(refill_min_set) X(shade_min) X(refill_min_g) X(shade_min_g) X(w_node)      \
+    X(w_leaf) X(w_node_g) X(w_leaf_g) X(chunk_pixels) X(tail_chunk) X(bulk_percent) X(tile_major) X(pf_sky)  \
+    X(max_blocks) X(wf_top_limit) X(wf_streams_per_cu) X(wf_refill_min)
 #define PLAN_OUT_FIELDS(X)                                                                                    \
-    X(si) X(wf) X(lds) X(goct) X(bofs) X(var) X(smem) X(grid) X(grid_s) X(gidBegin) X(gidEnd) X(rowBegin)    \
+    X(smem) X(grid) X(grid_s) X(gidBegin) X(gidEnd) X(rowBegin)    \
     X(rowCount) X(tilesX) X(nTiles) X(bandPeriod) X(bandPhase) X(nTop) X(regrouped) X(octStride) X(octB)     \
     X(octRecords) X(nNodes) X(refillMin) X(shadeMin) X(stepWeightNode) X(stepWeightLeaf) X(flagTiles)        \
     X(tileMajor) X(chunkPixels) X(tailChunk) X(chunkSplit) X(tailBase) X(staticFirst) X(nParts) X(partLen)   \
@@ -39,9 +42,12 @@ static std::string broken(const rtp::PlanIn& in, const rtp::LaunchPlan& p) {
         if (!ok) bad += std::string(bad.empty() ? "" : ",") + name;
     };
     const uint64_t tot = (uint64_t)p.nTiles * 64u * p.nFrames;
+    const rtk::Variant& v = p.variant;
+    // (the launch once derived this from KernelArgs::octB by itself)
+    need((v.walk == rtk::Walk::LdsB) == (v.lds() && p.octB == rtk::kOctB), "b_plane_walk_matches_octB");
     need(p.chunkPixels % 64 == 0 && p.tailChunk % 64 == 0 && p.chunkPixels > 0, "chunks_whole_tiles");
     const uint32_t t = p.tailChunk / 64;
-    need(t >= 1 && (t & (t - 1)) == 0 && p.tailChunk <= in.tail_chunk, "tail_pow2_within_cap");
+    need(t >= 1 && (t & (t - 1)) == 0 && p.tailChunk <= in.tune.tail_chunk, "tail_pow2_within_cap");
     need(p.chunkPixels > 0 && p.chunkSplit % p.chunkPixels == 0 && p.chunkSplit <= tot, "split_whole_chunks");
     need(p.chunkSplit <= p.tailBase && p.tailBase <= tot, "tail_base_in_range");
     need(!p.staticFirst || p.chunkSplit == 0, "static_first_without_bulk");
@@ -49,13 +55,13 @@ static std::string broken(const rtp::PlanIn& in, const rtp::LaunchPlan& p) {
                            (uint64_t)p.nParts * p.partLen >= tot),
          "partitions_cover");
     const uint64_t work = (uint64_t)p.nTiles * p.nFrames;
-    const uint64_t cap = p.si == rtk::kSchedTiles ? p.nTiles : p.wf ? (work + 7) / 8 : (work + 3) / 4;
+    const uint64_t cap = v.sched == rtk::kSchedTiles ? p.nTiles : p.wf() ? (work + 7) / 8 : (work + 3) / 4;
     need(p.grid >= 1 && p.grid <= (cap ? cap : 1), "grid_within_tiles");
     need(tot <= 0xfff00000ull, "work_items_32bit");
-    const size_t extras = p.wf ? (rtk::kWfExtendThreads / 64) * rtk::kWfRingBytes
+    const size_t extras = p.wf() ? (rtk::kWfExtendThreads / 64) * rtk::kWfRingBytes
                                : 4 * rtk::kFinishWaveBytes + 4 * rtk::kRingWaveBytes + rtk::kStealBytes;
-    need(!p.lds || p.smem <= 64 * 1024 + extras, "lds_budget");
-    need(!p.wf || (p.cap == p.nBlocks * 64u && p.G >= 1 && p.G <= p.nBlocks), "wavefront_queues");
+    need(!v.lds() || p.smem <= 64 * 1024 + extras, "lds_budget");
+    need(!p.wf() || (p.cap == p.nBlocks * 64u && p.G >= 1 && p.G <= p.nBlocks), "wavefront_queues");
     return bad;
 }
 
@@ -78,6 +84,9 @@ static int plan_lines() {
 #define X(f) if (key == #f) { in.f = (decltype(in.f))v; known = true; }
             PLAN_IN_FIELDS(X)
 #undef X
+#define X(f) if (key == #f) { in.tune.f = (decltype(in.tune.f))v; known = true; }
+            PLAN_TUNE_FIELDS(X)
+#undef X
             if (!known) {
                 std::fprintf(stderr, "plan_main: unknown field %s\n", key.c_str());
                 return 2;
@@ -90,7 +99,11 @@ static int plan_lines() {
         std::printf("{\"rc\":%d,\"nothing\":%d", rc, (int)p.nothing);
         if (rc == RT_SUCCESS && !p.nothing) {
             std::printf(",\"inv\":\"%s\",\"out\":{", broken(in, p).c_str());
-            const char* sep = "";
+            const rtk::Variant& pv = p.variant;
+            const bool goct = pv.walk == rtk::Walk::GlobalOct, bofs = pv.walk == rtk::Walk::LdsB;
+            std::printf("\"si\":%d,\"wf\":%d,\"lds\":%d,\"goct\":%d,\"bofs\":%d,\"var\":%d", pv.sched, (int)p.wf(),
+                        (int)pv.lds(), (int)goct, (int)bofs, (bofs || goct ? 1 : 0) + (pv.fused ? 2 : 0));
+            const char* sep = ",";
 #define X(f) std::printf("%s\"" #f "\":%lld", sep, (long long)p.f); sep = ",";
             PLAN_OUT_FIELDS(X)
 #undef X
@@ -130,10 +143,8 @@ static int sweep() {
         in.overlap = true;
         in.band_period = period, in.band_phase = phase;
         in.n_nodes = sc.n_nodes, in.n_tris = sc.n_tris, in.n_mats = sc.n_mats, in.n_top = sc.n_top;
-        in.oct_ok = true, in.goct_available = true, in.goct_b = sc.goct_b, in.global_oct = sc.global_oct;
-        in.refill_min = 6, in.shade_min = 48, in.w_node = 35, in.w_leaf = 55;
-        in.tail_chunk = tail, in.bulk_percent = 80, in.tile_major = -1, in.pf_sky = 1;
-        in.wf_top_limit = 256, in.wf_refill_min = 32;
+        in.oct_ok = true, in.goct_available = true, in.goct_b = sc.goct_b, in.tune.global_oct = sc.global_oct;
+        in.tune.tail_chunk = tail;  // (the other knobs at their defaults)
         in.num_cus = 256;
         rtp::LaunchPlan p;
         const int rc = rtp::plan_launch(in, occ, occ, &p);
@@ -150,7 +161,7 @@ static int sweep() {
         if (!bad.empty() && ++failures <= 20)
             std::printf("broken [%s]: %ux%u frames %u sched %d fused %d band %u/%u nodes %u goct %d occ %d tail %u\n",
                         bad.c_str(), in.W, in.H, nf, in.sched, (int)in.fused, period, phase, in.n_nodes,
-                        in.global_oct, occ, tail);
+                        in.tune.global_oct, occ, tail);
     }
     std::printf("sweep: %llu plans, %llu accepted, %llu failures\n", plans, accepted, failures);
     return failures ? 1 : 0;

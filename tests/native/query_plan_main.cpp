@@ -21,7 +21,6 @@ static rtp::QueryIn base_in() {
     in.mode = rtp::kQueryClosest;
     in.n_nodes = 21, in.n_tris = 36;
     in.oct_ok = true, in.goct_available = true, in.goct_b = 176;
-    in.refill_min = 32, in.w_node = 35, in.w_leaf = 55;
     in.num_cus = 256;
     return in;
 }
@@ -33,6 +32,7 @@ static std::string broken(const rtp::QueryIn& in, int occ, const rtp::QueryPlan&
         if (!ok) bad += std::string(bad.empty() ? "" : ",") + name;
     };
     need(p.first == in.first_ray && p.count == in.n_rays, "range_kept");
+    const bool lds = p.variant.lds();
     // unit j holds rays [first + 64 j, min(first + 64 j + 64, first + count)): contiguous from `first`,
     // so every ray is in exactly one unit when the units tile [0, count) and none is empty
     // (the units depend on the count alone: walked once per count)
@@ -56,14 +56,15 @@ static std::string broken(const rtp::QueryIn& in, int occ, const rtp::QueryPlan&
     need(p.smem <= 160 * 1024, "lds_160k");
     const size_t rings = (rtk::kQueryThreads / 64) * (size_t)rtk::kQueryRingBytes;
     const size_t scene = (size_t)rtp::oct_records(in.n_nodes) * 16 + (size_t)in.n_tris * 48;
-    need(p.smem == (p.lds ? scene : 0) + rings, "lds_bytes");
-    need(!p.lds || (!in.force_global && p.smem <= rtp::kQueryLdsBudget), "lds_budget");
-    need(p.lds || in.force_global || scene + rings > rtp::kQueryLdsBudget, "lds_when_it_fits");
-    need(!p.lds || (p.octRecords == rtp::oct_records(in.n_nodes) && p.nNodes == in.n_nodes && !p.regrouped),
+    need(p.smem == (lds ? scene : 0) + rings, "lds_bytes");
+    need(!lds || (!in.force_global && p.smem <= rtp::kQueryLdsBudget), "lds_budget");
+    need(lds || in.force_global || scene + rings > rtp::kQueryLdsBudget, "lds_when_it_fits");
+    need(!lds || (p.octRecords == rtp::oct_records(in.n_nodes) && p.nNodes == in.n_nodes && !p.regrouped),
          "lds_records");
-    need(p.bofs == (p.lds && p.octB == rtk::kOctB), "bofs");
-    need(p.any == (in.mode == rtp::kQueryAny), "mode");
-    need(p.refillMin == in.refill_min && p.stepWeightNode > 0 && p.stepWeightLeaf > 0, "tuning");
+    need((p.variant.walk == rtk::Walk::LdsB) == (lds && p.octB == rtk::kOctB), "bofs");
+    need(lds || p.variant.walk == rtk::Walk::GlobalOct, "octant_walk_outside_lds");
+    need(p.variant.any == (in.mode == rtp::kQueryAny), "mode");
+    need(p.refillMin == in.tune.query_refill_min && p.stepWeightNode > 0 && p.stepWeightLeaf > 0, "tuning");
     return bad;
 }
 
@@ -103,7 +104,7 @@ static int sweep() {
             continue;
         }
         ++accepted;
-        (p.lds ? lds_plans : global_plans) += 1;
+        (p.variant.lds() ? lds_plans : global_plans) += 1;
         const std::string bad = broken(in, occ, p);
         if (!bad.empty() && ++failures <= 20)
             std::printf("broken [%s]: first %llu n %llu nodes %u tris %u force %d mode %d occ %d\n", bad.c_str(),

@@ -121,3 +121,41 @@ def test_round5_tuning_ranges(cornell):
     r.frame(1, light_bounces=2)
     assert np.isfinite(r.result()).all()
     r.close()
+
+
+def test_tuning_table_through_the_c_abi(cornell):
+    """Every knob of rtKernelSetTuning (tests/tuning_table.py, TOP_NODES with them) reads its default on
+    a fresh kernel, takes both ends of its range, and refuses one past either end with
+    CL_INVALID_VALUE, keeping its value; with the defaults back, a 2-bounce frame of every schedule
+    is the same bits as before the knobs were touched."""
+    from tuning_table import INT_MAX, KNOBS, REFUSED_IDS, TOP_NODES
+    r = HipRenderer(cornell, 64, 48, perframe_batch=None)  # (None: the library's default stays)
+    lib, h = r.k._lib, r.k.handle
+    scheds = (N.SCHED_TILES, N.SCHED_STEP, N.SCHED_WAVEFRONT)
+
+    def frames():
+        out = []
+        for sched in scheds:
+            r.k.set_schedule(sched)
+            r.frame(1, light_bounces=2)
+            out.append(r.result().view(np.uint32).copy())
+        return out
+
+    knobs = KNOBS + [TOP_NODES]
+    assert {name: r.k.get_tuning(name) for name, *_ in knobs} == {name: default for name, default, *_ in knobs}
+    before = frames()
+    for name, default, lo, hi, _ in knobs:
+        tid = N.TUNING[name]
+        for v in (lo, hi):
+            assert lib.rtKernelSetTuning(h, tid, v) == 0, (name, v)
+            assert r.k.get_tuning(name) == v
+        for v in (lo - 1,) + ((hi + 1,) if hi < INT_MAX else ()):
+            assert lib.rtKernelSetTuning(h, tid, v) == -30, (name, v)
+            assert r.k.get_tuning(name) == hi, (name, v)
+        r.k.set_tuning(name, default)
+    for tid in REFUSED_IDS:
+        assert lib.rtKernelSetTuning(h, tid, 16) == -30, tid
+    assert {name: r.k.get_tuning(name) for name, *_ in knobs} == {name: default for name, default, *_ in knobs}
+    for sched, a, b in zip(scheds, before, frames()):
+        assert np.array_equal(a, b), sched
+    r.close()
