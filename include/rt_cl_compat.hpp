@@ -96,6 +96,12 @@ public:
     inline void IntersectRays(std::shared_ptr<CLKernel> kernel, const Buffer& rays, const Buffer& hits, size_t nRays,
                               int mode = RT_QUERY_CLOSEST, size_t firstRay = 0) const;
     inline void CameraRays(std::shared_ptr<CLKernel> kernel, size_t workSize, const Buffer& rays) const;
+    // extensions: the surface at each hit, and first-hit feature buffers (rtEnqueueHitSurfaces,
+    // rtEnqueueFrameFeatures)
+    inline void HitSurfaces(std::shared_ptr<CLKernel> kernel, const Buffer& rays, const Buffer& hits,
+                            const Buffer& surfaces, size_t n, size_t first = 0) const;
+    inline void FrameFeatures(std::shared_ptr<CLKernel> kernel, size_t workSize, unsigned nFrames,
+                              const Buffer& features) const;
     // extensions: moving geometry (rtEnqueueUpdateVertices, rtRefitBVH); normals may be null
     void UpdateVertices(const Buffer& tris, size_t firstTri, size_t nTris, const Buffer& positions,
                         const Buffer* normals = nullptr) const {
@@ -149,6 +155,16 @@ inline void CLContext::IntersectRays(std::shared_ptr<CLKernel> kernel, const Buf
 }
 inline void CLContext::CameraRays(std::shared_ptr<CLKernel> kernel, size_t workSize, const Buffer& rays) const {
     check(rtEnqueueCameraRays(ctx_, kernel->GetKernel(), workSize, rays.get()), "Failed to enqueue camera rays");
+}
+inline void CLContext::HitSurfaces(std::shared_ptr<CLKernel> kernel, const Buffer& rays, const Buffer& hits,
+                                   const Buffer& surfaces, size_t n, size_t first) const {
+    check(rtEnqueueHitSurfaces(ctx_, kernel->GetKernel(), rays.get(), hits.get(), first, n, surfaces.get()),
+          "Failed to enqueue hit surfaces");
+}
+inline void CLContext::FrameFeatures(std::shared_ptr<CLKernel> kernel, size_t workSize, unsigned nFrames,
+                                     const Buffer& features) const {
+    check(rtEnqueueFrameFeatures(ctx_, kernel->GetKernel(), workSize, nFrames, features.get()),
+          "Failed to enqueue frame features");
 }
 inline void CLContext::RefitBVH(std::shared_ptr<CLKernel> kernel) const {
     check(rtRefitBVH(ctx_, kernel->GetKernel()), "Failed to refit BVH");

@@ -191,7 +191,8 @@ typedef struct rt_stats {
     uint64_t rays, node_visits, tri_tests, hits;
     uint64_t launches;
     double kernel_ms;  /* sum of KernelEntry durations (HIP events) when timing is on; ray queries
-                        * (rtEnqueueIntersectRays) add theirs, and count in `launches` */
+                        * (rtEnqueueIntersectRays), surface records and feature buffers add theirs,
+                        * and count in `launches` */
     /* diagnostic (step schedule, stats on): shader-clock cycles summed over waves spent
      * refilling/finishing pixels, traversing, shading, and in total */
     uint64_t cycles_refill, cycles_traverse, cycles_shade, cycles_total;
@@ -268,6 +269,65 @@ typedef struct rt_ray_hit {
 int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t first_ray, size_t n_rays, int mode,
                            rt_mem hits);
 int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem rays);
+
+/* ---- surface records of ray hits, and first-hit feature buffers ----------------------------
+ * rtEnqueueHitSurfaces writes, for records [first, first + n) of `rays` (rt_ray) and `hits`
+ * (rt_ray_hit), the same slots of `surfaces` (rt_surface); the other slots are not touched.  The
+ * scene is the one bound to `k`, prepared exactly as a query prepares it, and the call runs in k's
+ * math mode M.  u, v and t are taken from the hit record as they are: nothing is intersected again.
+ * Per record with 0 <= prim < the scene's triangle count:
+ *   position    origin' + dir' * t of the ray InitRay(origin, dir) makes (kernel_bvh.cl:42-55, :144):
+ *               dir is normalised as the query normalised it.
+ *   normal      normalize(n1 * w + (n2 * u + n3 * v)), w = (1 - u) - v (kernel_bvh.cl:146) -- computed
+ *               by the device code the render shades with, so it is the render's normal in mode M,
+ *               bit for bit.
+ *   texcoord    the same weights over v1/v2/v3.uv.xy (kernel_bvh.cl:147); not normalised.
+ *   geo_normal  normalize(cross(v2 - v1, v3 - v1)); the zero vector for a zero-area triangle.
+ *   material    the triangle's mtlIndex.  The material buffer is not read and need not be bound.
+ *   t, prim     copied from the hit; reserved is written as 0.
+ * Any other prim is a miss: prim = -1, t copied, material = 0xFFFFFFFF, every other word 0.  The hit
+ * buffer is the caller's to write, so an index outside the triangle array is never used as one.
+ * Errors (nothing is launched), checked in this order: first + n > 2^31 RT_INVALID_VALUE; `surfaces`
+ * the same buffer as `rays` or `hits`, a buffer of another context or NULL, or `rays` and `hits` one
+ * buffer, RT_INVALID_MEM_OBJECT; the range beyond any of the three buffers (32, 16 and 64 B per
+ * record) RT_INVALID_BUFFER_SIZE; scene or node slot unbound RT_INVALID_KERNEL_ARGS; n == 0
+ * RT_SUCCESS with no launch.
+ * Ordering is a query's: asynchronous on the context's in-order queue, coalesced per-frame launches
+ * first, after the pending accumulations; `surfaces` counts as written for the buffers' generations;
+ * with timing on the launch adds to kernel_ms and `launches`.  After rtEnqueueUpdateVertices +
+ * rtRefitBVH it sees the moved positions and normals without a full preparation.
+ *
+ * rtEnqueueFrameFeatures writes per work-item gid in [0, global_work_size) the first-hit features of
+ * frames FRAME_COUNT .. FRAME_COUNT + n_frames - 1 (uint32 wrap), averaged over the same jittered
+ * camera rays the render traces for them.  Four sums start at +0.0f; per frame, in frame order, the
+ * ray is rtEnqueueCameraRays' record for gid, the hit its RT_QUERY_CLOSEST answer, and a hit adds --
+ * one fp32 addition each -- materials[material].diffuse.xyz to albedo, the surface normal to normal, t
+ * to depth and 1.0f to coverage; a miss adds nothing.  After the last frame every sum is multiplied
+ * once by 1.0f / (float)n_frames (the IEEE quotient in every math mode).  The mean normal is not
+ * normalised again.  `features` is never read, FRAME_COUNT stays as set, and work range and row
+ * interleave are ignored as for rtEnqueueCameraRays.  It runs as three launches per frame on the
+ * context's queue (camera rays, closest-hit query, the surface kernel folding into `features`) over
+ * 48 B of scratch per work-item that the kernel object owns, grows before anything is enqueued and
+ * frees when it is released; nothing waits on the host.  With timing on the whole call counts as one
+ * launch.
+ * Errors (nothing is launched): n_frames 0 or above 4096 RT_INVALID_VALUE; WIDTH, HEIGHT,
+ * FRAME_COUNT or a camera slot unset, WIDTH or HEIGHT zero, or scene, node or material slot unbound
+ * RT_INVALID_KERNEL_ARGS; global_work_size 0 or above 2^32 - 1 RT_INVALID_GLOBAL_WORK_SIZE;
+ * `features` smaller than 32 B per work-item RT_INVALID_BUFFER_SIZE; a BVH leaf of more than 127
+ * triangles RT_INVALID_OPERATION; `features` NULL or of another context RT_INVALID_MEM_OBJECT. */
+typedef struct rt_surface {
+    float position[3];   float    t;           /* t copied from the hit */
+    float normal[3];     int32_t  prim;        /* shading normal; prim copied, -1 = miss */
+    float geo_normal[3]; uint32_t material;    /* mtlIndex of the triangle; 0xFFFFFFFF on a miss */
+    float texcoord[2];   uint32_t reserved[2]; /* written as 0 */
+} rt_surface; /* 64 B */
+typedef struct rt_pixel_features {
+    float albedo[3]; float depth;
+    float normal[3]; float coverage;
+} rt_pixel_features; /* 32 B */
+int rtEnqueueHitSurfaces(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem hits, size_t first, size_t n,
+                         rt_mem surfaces);
+int rtEnqueueFrameFeatures(rt_context ctx, rt_kernel k, size_t global_work_size, unsigned n_frames, rt_mem features);
 
 /* ---- moving geometry: vertex update + device-side BVH refit (extension) ----
  * For a mesh whose triangles move while the tree's shape stays put.  Both enqueue calls are

@@ -67,6 +67,14 @@ RAY_DTYPE = np.dtype([("origin", np.float32, (3,)), ("tmin", np.float32), ("dir"
 RAY_HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32)])
 assert RAY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 16
 QUERY_CLOSEST, QUERY_ANY = 0, 1
+# rt_surface / rt_pixel_features (rt_hip.h): the records of rtEnqueueHitSurfaces and rtEnqueueFrameFeatures
+SURFACE_DTYPE = np.dtype([("position", np.float32, (3,)), ("t", np.float32),
+                          ("normal", np.float32, (3,)), ("prim", np.int32),
+                          ("geo_normal", np.float32, (3,)), ("material", np.uint32),
+                          ("texcoord", np.float32, (2,)), ("reserved", np.uint32, (2,))])
+PIXEL_FEATURES_DTYPE = np.dtype([("albedo", np.float32, (3,)), ("depth", np.float32),
+                                 ("normal", np.float32, (3,)), ("coverage", np.float32)])
+assert SURFACE_DTYPE.itemsize == 64 and PIXEL_FEATURES_DTYPE.itemsize == 32
 # rt_tri_points (rt_hip.h): the records of rtEnqueueUpdateVertices, three float3 slots (w ignored)
 TRI_POINTS_DTYPE = np.dtype([("p1", FLOAT3), ("p2", FLOAT3), ("p3", FLOAT3)])
 assert TRI_POINTS_DTYPE.itemsize == 48
@@ -140,6 +148,8 @@ _HIP_PROTOS = {
     "rtEnqueueKernelFrames": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint]),
     "rtEnqueueIntersectRays": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, _vp]),
     "rtEnqueueCameraRays": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp]),
+    "rtEnqueueHitSurfaces": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
+    "rtEnqueueFrameFeatures": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint, _vp]),
     "rtEnqueueUpdateVertices": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
     "rtRefitBVH": (ctypes.c_int, [_vp, _vp]),
     "rtDiagScenePrepares": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),

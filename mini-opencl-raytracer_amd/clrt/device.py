@@ -92,6 +92,20 @@ class CLContext:
         check(self._lib.rtEnqueueCameraRays(self.handle, kernel.handle, int(work_size), rays.handle),
               "Failed to enqueue camera rays")
 
+    def HitSurfaces(self, kernel: "CLKernel", rays: "Buffer", hits: "Buffer", surfaces: "Buffer", n: int,
+                    first: int = 0) -> None:
+        """rtEnqueueHitSurfaces: the surface (N.SURFACE_DTYPE: position, shading and geometric normal,
+        material, texture coordinate) at hits [first, first + n) of `hits` along the same slots of `rays`,
+        into the same slots of `surfaces`; nothing is intersected again."""
+        check(self._lib.rtEnqueueHitSurfaces(self.handle, kernel.handle, rays.handle, hits.handle, int(first), int(n),
+                                             surfaces.handle), "Failed to enqueue hit surfaces")
+
+    def FrameFeatures(self, kernel: "CLKernel", work_size: int, n_frames: int, features: "Buffer") -> None:
+        """rtEnqueueFrameFeatures: first-hit albedo, depth, normal and coverage per work-item
+        (N.PIXEL_FEATURES_DTYPE), averaged over frames FRAME_COUNT .. FRAME_COUNT + n_frames - 1."""
+        check(self._lib.rtEnqueueFrameFeatures(self.handle, kernel.handle, int(work_size), int(n_frames),
+                                               features.handle), "Failed to enqueue frame features")
+
     def UpdateVertices(self, tris: "Buffer", first: int, n: int, positions: "Buffer",
                        normals: "Buffer | None" = None) -> None:
         """rtEnqueueUpdateVertices: the position (and normal) xyz of triangles [first, first + n) of `tris`

@@ -46,6 +46,8 @@ class Raytracer:
         self.pixels = np.zeros((self.height * self.width, 4), np.float32)
         self._scene_bufs: list = []
         self._cast_bufs: tuple | None = None  # (capacity in rays, ray buffer, hit buffer) of cast()
+        self._surf_buf: tuple | None = None   # (capacity in records, surface buffer) of surfaces()
+        self._feat_buf: Buffer | None = None  # features(): width * height records
         self._move_bufs: tuple | None = None  # (capacity in triangles, positions, normals) of move_vertices()
         self._move_keep: list = []            # host arrays of uploads still in the queue
 
@@ -106,17 +108,25 @@ class Raytracer:
         are (n, 3) arrays (directions need not be unit length), `tmin` / `tmax` scalars or (n,) arrays.
         Returns n N.RAY_HIT_DTYPE records {prim, t, u, v}; a miss is {-1, tmax, 0, 0}.  `any_hit` stops
         each walk at its first accepted triangle.  The device buffers are kept and reused."""
+        n, rb, hb = self._enqueue_cast(origins, dirs, tmin, tmax, any_hit)
+        hits = np.empty(n, N.RAY_HIT_DTYPE)
+        if n == 0:
+            return hits
+        self.ctx.ReadBuffer(hb, hits, blocking=True)
+        return hits
+
+    def _enqueue_cast(self, origins, dirs, tmin, tmax, any_hit):
+        """The rays uploaded into the kept buffers and their query enqueued: (n, ray buffer, hit buffer)."""
         origins = np.asarray(origins, np.float32).reshape(-1, 3)
         dirs = np.asarray(dirs, np.float32).reshape(-1, 3)
         n = len(origins)
         if len(dirs) != n:
             raise ValueError("origins and dirs differ in length")
+        if n == 0:
+            return 0, None, None
         rays = np.empty(n, N.RAY_DTYPE)
         rays["origin"], rays["dir"] = origins, dirs
         rays["tmin"], rays["tmax"] = tmin, tmax
-        hits = np.empty(n, N.RAY_HIT_DTYPE)
-        if n == 0:
-            return hits
         if self._cast_bufs is None or self._cast_bufs[0] < n:
             if self._cast_bufs:
                 self._cast_bufs[1].release()
@@ -126,8 +136,42 @@ class Raytracer:
         _, rb, hb = self._cast_bufs
         self.ctx.WriteBuffer(rb, rays)
         self.ctx.IntersectRays(self.kernel, rb, hb, n, N.QUERY_ANY if any_hit else N.QUERY_CLOSEST)
-        self.ctx.ReadBuffer(hb, hits, blocking=True)
-        return hits
+        return n, rb, hb
+
+    def surfaces(self, origins, dirs, tmin=-np.inf, tmax=100000.0) -> tuple:
+        """cast()'s closest hits and the surface at each (rtEnqueueHitSurfaces): returns (hits, surfaces),
+        n N.RAY_HIT_DTYPE and n N.SURFACE_DTYPE records -- position, the shading normal the render uses in
+        the kernel's math mode, geometric normal, material index and texture coordinate; a miss has prim
+        -1 and material 0xFFFFFFFF.  The hits never leave the device in between; cast()'s buffers are
+        reused."""
+        n, rb, hb = self._enqueue_cast(origins, dirs, tmin, tmax, False)
+        hits = np.empty(n, N.RAY_HIT_DTYPE)
+        surf = np.empty(n, N.SURFACE_DTYPE)
+        if n == 0:
+            return hits, surf
+        if self._surf_buf is None or self._surf_buf[0] < n:
+            if self._surf_buf:
+                self._surf_buf[1].release()
+            self._surf_buf = (n, self.ctx.create_buffer(N.MEM_READ_WRITE, n * N.SURFACE_DTYPE.itemsize))
+        sb = self._surf_buf[1]
+        self.ctx.HitSurfaces(self.kernel, rb, hb, sb, n)
+        self.ctx.ReadBuffer(hb, hits)
+        self.ctx.ReadBuffer(sb, surf, blocking=True)
+        return hits, surf
+
+    def features(self, n_frames: int = 1) -> np.ndarray:
+        """First-hit feature buffers for a denoiser (rtEnqueueFrameFeatures): an (H, W) array of
+        N.PIXEL_FEATURES_DTYPE -- albedo, depth, normal and coverage averaged over the jittered camera
+        rays of frames frame_count .. frame_count + n_frames - 1 at the current camera, the rays
+        RenderFrame traces for those frames.  frame_count is left as it is."""
+        self.set_uniforms()
+        work = self.width * self.height
+        if self._feat_buf is None:
+            self._feat_buf = self.ctx.create_buffer(N.MEM_READ_WRITE, work * N.PIXEL_FEATURES_DTYPE.itemsize)
+        self.ctx.FrameFeatures(self.kernel, work, n_frames, self._feat_buf)
+        out = np.empty((self.height, self.width), N.PIXEL_FEATURES_DTYPE)
+        self.ctx.ReadBuffer(self._feat_buf, out, blocking=True)
+        return out
 
     def move_vertices(self, positions, normals=None, first: int = 0) -> None:
         """Move triangles [first, first + n) of the uploaded scene and refit its BVH on the device
@@ -214,6 +258,12 @@ class Raytracer:
             self._cast_bufs[1].release()
             self._cast_bufs[2].release()
             self._cast_bufs = None
+        if self._surf_buf:
+            self._surf_buf[1].release()
+            self._surf_buf = None
+        if self._feat_buf:
+            self._feat_buf.release()
+            self._feat_buf = None
         if self._move_bufs:
             self._move_bufs[1].release()
             self._move_bufs[2].release()

@@ -103,6 +103,7 @@ struct rt_kernel_s {
     hipEvent_t render_done = nullptr;  // recorded on the main stream after a fused render
     uint64_t pf_waits = ~0ull;         // ctx->host_waits at the previous per-frame step launch
     rti::DeviceScene scene;  // the derived packed scene (rt_device_scene.hpp)
+    rti::FeatureScratch feat;  // rtEnqueueFrameFeatures: a frame's camera rays and hits
     bool last_lds = false;
     rtk::OccupancyCache occ;  // workgroups per CU of the kernels launched so far
 };
@@ -435,6 +436,7 @@ int rtReleaseKernel(rt_kernel k) {
     if (k->wf_hits) (void)hipFree(k->wf_hits);
     if (k->wf_cnt) (void)hipFree(k->wf_cnt);
     k->scene.release();
+    k->feat.release();
     if (k->dstats) (void)hipFree(k->dstats);
     if (k->work_counter) (void)hipFree(k->work_counter);
     if (k->accum_key) (void)hipFree(k->accum_key);
@@ -870,12 +872,12 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
 
 // the query plan's inputs: the range, the two buffers, the kernel's settings and its packed scene
 // (packed false: before the scene is packed -- the range and argument checks only)
-static rtp::QueryIn query_inputs(rt_context ctx, rt_kernel k, rt_mem rays, size_t first_ray, size_t n_rays, int mode,
-                                 rt_mem hits, bool packed) {
+static rtp::QueryIn query_inputs(rt_context ctx, rt_kernel k, size_t rays_bytes, size_t first_ray, size_t n_rays,
+                                 int mode, size_t hits_bytes, bool same_buffer, bool packed) {
     rtp::QueryIn in{};
     in.first_ray = first_ray, in.n_rays = n_rays;
-    in.rays_bytes = rays->size, in.hits_bytes = hits->size;
-    in.same_buffer = rays == hits;
+    in.rays_bytes = rays_bytes, in.hits_bytes = hits_bytes;
+    in.same_buffer = same_buffer;
     in.mode = mode;
     in.math = k->math, in.stats = k->stats;
     in.oct_ok = true;
@@ -891,6 +893,24 @@ static rtp::QueryIn query_inputs(rt_context ctx, rt_kernel k, rt_mem rays, size_
     return in;
 }
 
+// a planned query's arguments: the packed scene of k, the range and the two arrays
+static void fill_query_args(rt_kernel k, const rtp::QueryPlan& p, const float4* rays, float4* hits, rtk::KernelArgs* args,
+                            rtk::QueryArgs* qargs) {
+    rtk::KernelArgs& a = *args;
+    std::memset(&a, 0, sizeof(a));
+    a.packedTris = k->scene.packed_tris();
+    a.octNodes = p.regrouped ? k->scene.goct() : k->scene.oct_nodes();
+    a.nTris = k->scene.n_tris();
+    a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords;
+    a.stepWeightNode = p.stepWeightNode, a.stepWeightLeaf = p.stepWeightLeaf;
+    a.stats = k->dstats;
+    rtk::QueryArgs& q = *qargs;
+    q = rtk::QueryArgs{};
+    q.rays = rays;
+    q.hits = hits;
+    q.first = p.first, q.count = p.count, q.nUnits = p.nUnits, q.refillMin = p.refillMin;
+}
+
 int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t first_ray, size_t n_rays, int mode,
                            rt_mem hits) {
     // 1. the handles and the range: no scene is packed and nothing launched on an error
@@ -901,30 +921,21 @@ int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t firs
     rc = flush_first(ctx);
     if (rc) return rc;
     rtp::QueryPlan p;
-    rc = rtp::query_shape(query_inputs(ctx, k, rays, first_ray, n_rays, mode, hits, false), &p);
+    rc = rtp::query_shape(query_inputs(ctx, k, rays->size, first_ray, n_rays, mode, hits->size, rays == hits, false), &p);
     if (rc || p.nothing) return pending_error(ctx, rc);
     if (!k->set[RT_ARG_BUFFER_SCENE] || !k->set[RT_ARG_BUFFER_NODE]) return RT_INVALID_KERNEL_ARGS;
     // 2. the scene, packed and validated as a render launch does (materials only when bound)
     rc = prepare_scene(k);
     if (rc) return rc;
     // 3. the plan, with the kernel's occupancy at the LDS size it chose
-    const rtp::QueryIn in = query_inputs(ctx, k, rays, first_ray, n_rays, mode, hits, true);
+    const rtp::QueryIn in = query_inputs(ctx, k, rays->size, first_ray, n_rays, mode, hits->size, false, true);
     rc = rtp::query_shape(in, &p);
     if (rc || p.nothing) return rc;
     rtp::query_grid(in, k->occ.get(rtk::Family::Query, p.variant, p.smem), &p);
     // 4. the arguments
     rtk::KernelArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.packedTris = k->scene.packed_tris();
-    a.octNodes = p.regrouped ? k->scene.goct() : k->scene.oct_nodes();
-    a.nTris = k->scene.n_tris();
-    a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords;
-    a.stepWeightNode = p.stepWeightNode, a.stepWeightLeaf = p.stepWeightLeaf;
-    a.stats = k->dstats;
-    rtk::QueryArgs q{};
-    q.rays = static_cast<const float4*>(rays->dptr);
-    q.hits = static_cast<float4*>(hits->dptr);
-    q.first = p.first, q.count = p.count, q.nUnits = p.nUnits, q.refillMin = p.refillMin;
+    rtk::QueryArgs q;
+    fill_query_args(k, p, static_cast<const float4*>(rays->dptr), static_cast<float4*>(hits->dptr), &a, &q);
     // 5. the launch, on the context's stream after the pending accumulations and gathers
     hipStream_t st = qs(ctx);
     k->last_lds = p.variant.lds();
@@ -960,6 +971,137 @@ int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt
         rtk::launch_camera_rays(a, static_cast<float4*>(rays->dptr), (uint32_t)global_work_size, k->math, qs(ctx));
     if (e != hipSuccess) return map_hip(e);
     mark_device_write(rays, true);
+    return pending_error(ctx, RT_SUCCESS);
+}
+
+// ---- surface records of ray hits (rt_surface.hpp; the plan: rt_query_plan.cpp surface_plan) -------
+
+// the surface kernel's arguments: the scene records it gathers from, packed by prepare_scene
+static void fill_surface_args(rt_kernel k, rtk::KernelArgs* args) {
+    rtk::KernelArgs& a = *args;
+    std::memset(&a, 0, sizeof(a));
+    a.trisFull = static_cast<const rt_cl_triangle*>(k->bufs[RT_ARG_BUFFER_SCENE]->dptr);
+    a.packedTris = k->scene.packed_tris();
+    a.shadeTris = k->scene.shade_tris();
+    a.nTris = k->scene.n_tris();
+}
+
+int rtEnqueueHitSurfaces(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem hits, size_t first, size_t n,
+                         rt_mem surfaces) {
+    // 1. the handles and the range: no scene is packed and nothing launched on an error
+    int rc = ensure_device(ctx);
+    if (rc) return rc;
+    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
+    if (!rays || !hits || rays->ctx != ctx || hits->ctx != ctx) return RT_INVALID_MEM_OBJECT;
+    rc = flush_first(ctx);
+    if (rc) return rc;
+    rtp::SurfaceIn in{};
+    in.first = first, in.n = n;
+    in.rays_bytes = rays->size, in.hits_bytes = hits->size;
+    in.out_ok = surfaces && surfaces->ctx == ctx;
+    in.out_bytes = in.out_ok ? surfaces->size : 0;
+    in.out_is_input = surfaces == rays || surfaces == hits;
+    in.rays_is_hits = rays == hits;
+    in.scene_bound = k->set[RT_ARG_BUFFER_SCENE] && k->set[RT_ARG_BUFFER_NODE];
+    rtp::SurfacePlan p;
+    rc = rtp::surface_plan(in, &p);
+    if (rc || p.nothing) return pending_error(ctx, rc);
+    // 2. the scene, packed and validated as a query does (materials only when bound)
+    rc = prepare_scene(k);
+    if (rc) return rc;
+    // 3. the arguments
+    rtk::KernelArgs a;
+    fill_surface_args(k, &a);
+    rtk::SurfaceArgs s{};
+    s.rays = static_cast<const float4*>(rays->dptr);
+    s.hits = static_cast<const float4*>(hits->dptr);
+    s.out = static_cast<float4*>(surfaces->dptr);
+    s.first = p.first, s.count = p.count;
+    // 4. the launch, on the context's stream after the pending accumulations and gathers
+    hipStream_t st = qs(ctx);
+    TimedLaunch timed{k, st, k->pending_events};
+    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
+    const hipError_t e = rtk::launch_surfaces(a, s, k->math, false, p.grid, st);
+    if (e != hipSuccess) return map_hip(e);
+    timed.end();
+    mark_device_write(surfaces, true);
+    rc = drain_if_many(k);
+    if (rc) return rc;
+    ++k->launches;
+    return pending_error(ctx, RT_SUCCESS);
+}
+
+int rtEnqueueFrameFeatures(rt_context ctx, rt_kernel k, size_t global_work_size, unsigned n_frames, rt_mem features) {
+    // 1. the handles and the arguments: nothing is allocated or launched on an error
+    int rc = ensure_device(ctx);
+    if (rc) return rc;
+    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
+    if (!features || features->ctx != ctx) return RT_INVALID_MEM_OBJECT;
+    rc = flush_first(ctx);
+    if (rc) return rc;
+    if (n_frames == 0 || n_frames > rtp::kMaxFeatureFrames) return RT_INVALID_VALUE;
+    for (int i : {RT_ARG_BUFFER_SCENE, RT_ARG_BUFFER_NODE, RT_ARG_BUFFER_MATERIAL, RT_ARG_WIDTH, RT_ARG_HEIGHT,
+                  RT_ARG_FRAME_COUNT, RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT, RT_ARG_CAMERA_UP})
+        if (!k->set[i]) return RT_INVALID_KERNEL_ARGS;
+    rtk::KernelArgs cam;
+    std::memset(&cam, 0, sizeof(cam));
+    fill_camera(k, &cam);
+    if (cam.width == 0 || cam.height == 0) return RT_INVALID_KERNEL_ARGS;
+    if (global_work_size == 0 || global_work_size > 0xffffffffull) return RT_INVALID_GLOBAL_WORK_SIZE;
+    if (features->size / rtp::kFeatureBytes < global_work_size) return RT_INVALID_BUFFER_SIZE;
+    // 2. the scene, and the plans of the frame's query and fold over the scratch (RT_INVALID_OPERATION:
+    // a leaf of more than 127 triangles, as for queries)
+    rc = prepare_scene(k);
+    if (rc) return rc;
+    const size_t gws = global_work_size;
+    const rtp::QueryIn qin =
+        query_inputs(ctx, k, gws * rtp::kRayBytes, 0, gws, RT_QUERY_CLOSEST, gws * rtp::kHitBytes, false, true);
+    rtp::QueryPlan qp;
+    rc = rtp::query_shape(qin, &qp);
+    if (rc) return rc;
+    rtp::query_grid(qin, k->occ.get(rtk::Family::Query, qp.variant, qp.smem), &qp);
+    rtp::SurfaceIn sin{};
+    sin.n = gws;
+    sin.rays_bytes = gws * rtp::kRayBytes, sin.hits_bytes = gws * rtp::kHitBytes, sin.out_bytes = features->size;
+    sin.out_ok = true, sin.scene_bound = true, sin.accumulate = true;
+    rtp::SurfacePlan sp;
+    rc = rtp::surface_plan(sin, &sp);
+    if (rc) return rc;
+    // 3. the scratch, before anything is enqueued (growing it waits for nothing: rt_internal.hpp)
+    const hipError_t me = k->feat.reserve(gws);
+    if (me != hipSuccess) return map_hip(me);
+    // 4. the arguments
+    rtk::KernelArgs qa, sa;
+    rtk::QueryArgs q;
+    fill_query_args(k, qp, k->feat.rays(), k->feat.hits(), &qa, &q);
+    fill_surface_args(k, &sa);
+    sa.materials = static_cast<const rt_cl_material*>(k->bufs[RT_ARG_BUFFER_MATERIAL]->dptr);
+    sa.nMats = k->scene.n_mats();
+    rtk::SurfaceArgs s{};
+    s.rays = k->feat.rays();
+    s.hits = k->feat.hits();
+    s.out = static_cast<float4*>(features->dptr);
+    s.first = sp.first, s.count = sp.count;
+    s.inv = 1.0f / (float)n_frames;
+    // 5. per frame, in frame order on the context's stream: the camera's rays, their closest hits, the fold
+    hipStream_t st = qs(ctx);
+    k->last_lds = qp.variant.lds();
+    TimedLaunch timed{k, st, k->pending_events};
+    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
+    hipError_t e = hipSuccess;
+    for (unsigned f = 0; f < n_frames && e == hipSuccess; ++f) {
+        cam.frameCount = k->u32[RT_ARG_FRAME_COUNT] + f;  // (uint32 wrap, as the render's)
+        s.accFirst = f == 0, s.accLast = f + 1 == n_frames;
+        e = rtk::launch_camera_rays(cam, k->feat.rays(), (uint32_t)gws, k->math, st);
+        if (e == hipSuccess) e = rtk::launch_query(qa, q, qp.variant, qp.grid, qp.smem, st);
+        if (e == hipSuccess) e = rtk::launch_surfaces(sa, s, k->math, true, sp.grid, st);
+    }
+    if (e != hipSuccess) return map_hip(e);
+    timed.end();
+    mark_device_write(features, true);
+    rc = drain_if_many(k);
+    if (rc) return rc;
+    ++k->launches;
     return pending_error(ctx, RT_SUCCESS);
 }
 

@@ -103,6 +103,38 @@ struct rt_mem_s {
 
 namespace rti {
 
+// rtEnqueueFrameFeatures' scratch, owned by the kernel object: one frame's camera rays (32 B per
+// work-item) followed by their hits (16 B).  Grown before anything is enqueued and never freed while
+// launches may still read it: an outgrown block is kept until release() (the kernel's release, which
+// has drained the queue), so growing waits for nothing.  Capacities double, so the kept blocks
+// together are smaller than the live one.
+struct FeatureScratch {
+    void* block = nullptr;
+    size_t items = 0;  // work-items the block holds
+    std::vector<void*> outgrown;
+
+    hipError_t reserve(size_t n) {
+        if (n <= items) return hipSuccess;
+        const size_t want = n > 2 * items ? n : 2 * items;
+        void* b = nullptr;
+        const hipError_t e = hipMalloc(&b, want * 48);
+        if (e != hipSuccess) return e;
+        if (block) outgrown.push_back(block);
+        block = b;
+        items = want;
+        return hipSuccess;
+    }
+    float4* rays() const { return static_cast<float4*>(block); }
+    float4* hits() const { return static_cast<float4*>(block) + 2 * items; }
+    void release() {
+        if (block) (void)hipFree(block);
+        for (void* b : outgrown) (void)hipFree(b);
+        block = nullptr;
+        items = 0;
+        outgrown.clear();
+    }
+};
+
 inline int map_hip(hipError_t e) {
     switch (e) {
         case hipSuccess: return RT_SUCCESS;

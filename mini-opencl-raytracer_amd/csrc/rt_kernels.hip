@@ -112,10 +112,12 @@ __global__ void accum_key(KernelArgs a, uint32_t* key) {
 static const Policy& policy(int math) {
     static const Policy devicelib = {pick_entry<MathDeviceLib>,   wf_pick<MathDeviceLib>,  query_pick<MathDeviceLib>,
                                      accum_frames<MathDeviceLib>, accum_key<MathDeviceLib>, camera_rays<MathDeviceLib>,
-                                     pack_mats};
+                                     pack_mats,
+                                     hit_surfaces<MathDeviceLib, false>, hit_surfaces<MathDeviceLib, true>};
     static const Policy pinned = {pick_entry<MathPinned>,   wf_pick<MathPinned>,  query_pick<MathPinned>,
                                   accum_frames<MathPinned>, accum_key<MathPinned>, camera_rays<MathPinned>,
-                                  pack_mats};
+                                  pack_mats,
+                                  hit_surfaces<MathPinned, false>, hit_surfaces<MathPinned, true>};
     return math == MathShipped::kId ? shipped_policy() : math == MathDeviceLib::kId ? devicelib : pinned;
 }
 
@@ -158,6 +160,14 @@ hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, const Variant& 
 hipError_t launch_camera_rays(const KernelArgs& a, float4* rays, uint32_t n, int math, hipStream_t st) {
     const dim3 grid((unsigned)(((uint64_t)n + 255u) / 256u));
     hipLaunchKernelGGL(policy(math).camera_rays, grid, dim3(256), 0, st, a, rays, n);
+    return hipGetLastError();
+}
+
+// ---- surface records (rt_surface.hpp) ------------------------------------------------------------
+hipError_t launch_surfaces(const KernelArgs& a, const SurfaceArgs& s, int math, bool accumulate, unsigned grid,
+                           hipStream_t st) {
+    const Policy& p = policy(math);
+    hipLaunchKernelGGL(accumulate ? p.surfaces_accum : p.surfaces, dim3(grid), dim3(kSurfaceThreads), 0, st, a, s);
     return hipGetLastError();
 }
 

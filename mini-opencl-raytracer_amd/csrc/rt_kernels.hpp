@@ -113,6 +113,22 @@ hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, const Variant& 
 // rtEnqueueCameraRays: width, height, frameCount and the camera slots of `a`; one rt_ray per work-item
 hipError_t launch_camera_rays(const KernelArgs& a, float4* rays, uint32_t n, int math, hipStream_t st);
 
+// ---- surface records of ray hits (rt_surface.hpp) ------------------------------------------------
+// rtEnqueueHitSurfaces / rtEnqueueFrameFeatures: KernelArgs carries trisFull (uvs), packedTris (e1, e2),
+// shadeTris (normals, mtlIndex), nTris and -- accumulating variant only -- materials; the rest is unused.
+struct SurfaceArgs {
+    const float4* rays;       // rt_ray records as 2 x float4
+    const float4* hits;       // rt_ray_hit records
+    float4* out;              // rt_surface records (4 x float4), or rt_pixel_features (2 x float4) when accumulating
+    uint32_t first, count;    // the range [first, first + count) of all three arrays
+    uint32_t accFirst;        // accumulating: the sums start at +0 (the output is not read)
+    uint32_t accLast;         // accumulating: the sums are scaled by `inv` before they are stored
+    float inv;                // 1.0f / n_frames, the IEEE quotient (computed on the host)
+};
+using SurfaceKernelFn = void (*)(KernelArgs, SurfaceArgs);
+hipError_t launch_surfaces(const KernelArgs& a, const SurfaceArgs& s, int math, bool accumulate, unsigned grid,
+                           hipStream_t st);
+
 hipError_t launch_kernel_entry(const KernelArgs& a, const Variant& v, unsigned grid, size_t smem, hipStream_t st);
 // accumulate the fused frames' radiances into the output (one pixel per lane)
 // (`key`: 4 words of per-kernel state for the sky shortcut, zeroed once; accum_key_body)
@@ -145,6 +161,7 @@ struct Policy {
     void (*accum_key)(KernelArgs, uint32_t*);
     void (*camera_rays)(KernelArgs, float4*, uint32_t);
     void (*pack_mats)(const rt_cl_material*, float4*, uint32_t);  // the policy's material records
+    SurfaceKernelFn surfaces, surfaces_accum;  // hit_surfaces<M, false / true>
 };
 const Policy& shipped_policy();
 // the step schedule's entry points are specialised per launch kind (step_body kMode: 1 fused, 2

@@ -583,6 +583,19 @@ struct LaneStats {
     uint32_t rays = 0, visits = 0, tests = 0, hits = 0;
 };
 
+// The hit record's position and interpolated normal (kernel_bvh.cl:144, :146), shared by the render's
+// shading and the surface records of rt_surface.hpp: the barycentric weights are w = (1 - u) - v for
+// v1, u for v2 and v for v3, in the reference's association order.
+template <class M>
+__device__ __forceinline__ F3 hit_position(const Ray& r, float t) {
+    return madd<M>(r.d, t, r.o);
+}
+template <class M>
+__device__ __forceinline__ F3 shading_normal(F3 n1, F3 n2, F3 n3, float u, float v) {
+    const float w = (1.0f - u) - v;
+    return normalize<M>(madd<M>(n1, w, madd<M>(n2, u, n3 * v)));
+}
+
 // The body of Render's bounce loop after Intersect (kernel_bvh.cl:358-380): radiance and
 // beta updates, BRDF sample and the next ray.  Returns false where the reference breaks
 // out of the loop (miss, or pdf <= 0 / NaN).
@@ -616,10 +629,8 @@ __device__ __forceinline__ bool shade_bounce(const Traversal& h, Ray& ray, F3& r
         s2 = *reinterpret_cast<const v4f*>(rec + 1);
         s3 = *reinterpret_cast<const v2f*>(rec + 2);
     }
-    const float w = (1.0f - h.u) - h.v;
-    const F3 normal = normalize<M>(
-        madd<M>(F3{s1.x, s1.y, s1.z}, w, madd<M>(F3{s2.x, s2.y, s2.z}, h.u, F3{s2.w, s3.x, s3.y} * h.v)));
-    const F3 pos = madd<M>(ray.d, h.t, ray.o);
+    const F3 normal = shading_normal<M>(F3{s1.x, s1.y, s1.z}, F3{s2.x, s2.y, s2.z}, F3{s2.w, s3.x, s3.y}, h.u, h.v);
+    const F3 pos = hit_position<M>(ray, h.t);
     const uint32_t mi = 4u * __float_as_uint(s1.w);
     v4f m0, m1, m2;
     const uint32_t mi0 = kScalarRec ? __builtin_amdgcn_readfirstlane(mi) : 0u;
@@ -1835,3 +1846,4 @@ __device__ __forceinline__ void material_record(const rt_cl_material& m, float4*
 
 #include "rt_wavefront.hpp"
 #include "rt_query.hpp"
+#include "rt_surface.hpp"

@@ -61,7 +61,8 @@ struct StepEntry<MathShipped> {
 const Policy& shipped_policy() {
     static const Policy shipped = {pick_entry<MathShipped>, wf_pick<MathShipped>, query_pick<MathShipped>,
                                    accum_frames_shipped,    accum_key_shipped,    camera_rays<MathShipped>,
-                                   pack_mats_shipped};
+                                   pack_mats_shipped,
+                                   hit_surfaces<MathShipped, false>, hit_surfaces<MathShipped, true>};
     return shipped;
 }
 

@@ -74,4 +74,7 @@ constexpr uint32_t kWfRingBytes = 64u * 32u;  // extend: per-wave ray ring ({o, 
 constexpr unsigned kQueryThreads = 512;          // query workgroup: 8 waves (LDS scene staged once per 8)
 constexpr uint32_t kQueryRingBytes = 64u * 32u;  // per-wave ring of 64 rt_ray records
 
+// ---- surface records (rt_surface.hpp) ----
+constexpr unsigned kSurfaceThreads = 256;        // one record per lane, no LDS
+
 }  // namespace rtk

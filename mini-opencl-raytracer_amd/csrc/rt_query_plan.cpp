@@ -1,7 +1,8 @@
 // rt_query_plan.cpp -- the plan of one ray query (rt_query_plan.hpp): the range check, the scene
 // path and its LDS size, the 64-ray units and the grid.  Pure arithmetic: a ray answered twice or
 // never, or a range that runs past a buffer, starts here, so it is kept where a CPU test can sweep
-// it (tests/native/query_plan_main.cpp).
+// it (tests/native/query_plan_main.cpp).  surface_plan: the checks and grid of the surface kernel
+// (tests/native/surface_plan_main.cpp).
 #include "rt_query_plan.hpp"
 
 #include <algorithm>
@@ -66,6 +67,28 @@ void query_grid(const QueryIn& in, int occ, QueryPlan* out) {
     // one unit per wave at least: eight waves per workgroup
     grid = std::min<uint64_t>(grid, ((uint64_t)p.nUnits + 7) / 8);
     p.grid = (uint32_t)std::max<uint64_t>(grid, 1);
+}
+
+int surface_plan(const SurfaceIn& in, SurfacePlan* out) {
+    *out = SurfacePlan{};
+    SurfacePlan& p = *out;
+    // (each term first: their sum cannot wrap)
+    if (in.first > kQueryMaxRays || in.n > kQueryMaxRays || in.first + in.n > kQueryMaxRays) return RT_INVALID_VALUE;
+    if (!in.out_ok || in.out_is_input || in.rays_is_hits) return RT_INVALID_MEM_OBJECT;
+    const uint64_t end = in.first + in.n;
+    const uint64_t out_record = in.accumulate ? kFeatureBytes : kSurfaceBytes;
+    if (end > in.rays_bytes / kRayBytes || end > in.hits_bytes / kHitBytes || end > in.out_bytes / out_record)
+        return RT_INVALID_BUFFER_SIZE;
+    if (!in.scene_bound) return RT_INVALID_KERNEL_ARGS;
+    if (in.n == 0) {
+        p.nothing = true;
+        return RT_SUCCESS;
+    }
+    p.accumulate = in.accumulate;
+    p.first = (uint32_t)in.first;
+    p.count = (uint32_t)in.n;
+    p.grid = (uint32_t)((in.n + rtk::kSurfaceThreads - 1) / rtk::kSurfaceThreads);  // <= 2^23
+    return RT_SUCCESS;
 }
 
 }  // namespace rtp

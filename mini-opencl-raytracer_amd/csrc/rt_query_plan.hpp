@@ -1,7 +1,8 @@
 // rt_query_plan.hpp -- how one ray query (rtEnqueueIntersectRays) is launched, as a pure function
 // of plain values (rt_query_plan.cpp): no HIP, no allocation, no globals.  The C ABI fills a
 // QueryIn, calls query_shape, looks the kernel's occupancy up for the LDS size that gives, and
-// calls query_grid.  The render's plan (rt_launch_plan.hpp) is separate and untouched.
+// calls query_grid.  The render's plan (rt_launch_plan.hpp) is separate and untouched.  surface_plan is the
+// same for the surface records of rt_surface.hpp (rtEnqueueHitSurfaces, rtEnqueueFrameFeatures).
 #pragma once
 
 #include <stddef.h>
@@ -60,5 +61,33 @@ inline int query_plan(const QueryIn& in, int occ, QueryPlan* out) {
     if (rc == 0 && !out->nothing) query_grid(in, occ, out);
     return rc;
 }
+
+// ---- surface records (rtEnqueueHitSurfaces, and the accumulating launches of rtEnqueueFrameFeatures) ----
+constexpr uint32_t kRayBytes = 32, kHitBytes = 16, kSurfaceBytes = 64, kFeatureBytes = 32;
+constexpr unsigned kMaxFeatureFrames = 4096;         // rtEnqueueFrameFeatures: coverage stays an exact count
+
+struct SurfaceIn {
+    uint64_t first, n;                   // the range [first, first + n)
+    uint64_t rays_bytes, hits_bytes;     // sizes of the two inputs
+    uint64_t out_bytes;                  // size of the output
+    bool out_ok;                         // the output is a buffer of this context
+    bool out_is_input;                   // ... and also `rays` or `hits`
+    bool rays_is_hits;                   // `rays` and `hits` are one buffer
+    bool scene_bound;                    // scene and node slots are bound
+    bool accumulate;                     // the output holds rt_pixel_features sums, not rt_surface records
+};
+
+struct SurfacePlan {
+    bool nothing;                        // n == 0: RT_SUCCESS, no launch
+    bool accumulate;                     // the kernel variant
+    uint32_t first, count;               // the range, 32-bit
+    uint32_t grid;                       // workgroups of kSurfaceThreads: record first + i goes to lane i
+};
+
+// RT_SUCCESS (out->nothing set when n == 0), or, in this order: RT_INVALID_VALUE (first + n > 2^31),
+// RT_INVALID_MEM_OBJECT (the output is no buffer of the context, or one of the inputs; the inputs are
+// one buffer), RT_INVALID_BUFFER_SIZE (the range ends beyond any of the three buffers),
+// RT_INVALID_KERNEL_ARGS (scene or node slot unbound).
+int surface_plan(const SurfaceIn& in, SurfacePlan* out);
 
 }  // namespace rtp

@@ -4,6 +4,9 @@
 # change meant to leave the kernels' instruction streams alone must print "identical" for them.
 # (s_add_u32 / s_addc_u32 literals are PC-relative offsets after s_getpc_b64 -- they move with the
 # size of other kernels in the code object -- and are masked.)
+# (Zero padding between a function's end and the next function's alignment decodes as
+# "v_cndmask_b32_e32 v0, s0, v0, vcc" or "...": such trailing lines are not instructions of the
+# function and are dropped, so adding a kernel behind another does not report that one as changed.)
 # usage: scripts/isa_compare.sh save DIR | compare DIR
 set -eu
 B=${ISA_BUILD:-mini-opencl-raytracer_amd/build}  # (ISA_BUILD: a variant's object directory)
@@ -18,6 +21,10 @@ dump() {  # dump OUTDIR
       | awk '/^[0-9a-f]+ <.*>:$/ {name=$2; next} name != "" {$1 = $1; if (NF) print name "\t" $0}' > $1/$o.isa
   done
 }
+body() {  # body FUNCTION FILE: the function's instruction text without trailing padding
+  grep -F "$1" $2 | cut -f2- \
+    | awk '{l[NR] = $0} END {n = NR; while (n > 0 && (l[n] == "..." || l[n] == "" || l[n] == "v_cndmask_b32_e32 v0, s0, v0, vcc")) n--; for (i = 1; i <= n; i++) print l[i]}'
+}
 case $1 in
   save) rm -rf $2; dump $2 ;;
   compare)
@@ -25,8 +32,8 @@ case $1 in
     dump /tmp/isa_now
     for o in rt_kernels_shipped rt_kernels; do
       for f in $(cut -f1 $2/$o.isa | sort -u); do
-        a=$(grep -F "$f" $2/$o.isa | cut -f2- | md5sum | cut -c1-12)
-        b=$(grep -F "$f" /tmp/isa_now/$o.isa | cut -f2- | md5sum | cut -c1-12)
+        a=$(body "$f" $2/$o.isa | md5sum | cut -c1-12)
+        b=$(body "$f" /tmp/isa_now/$o.isa | md5sum | cut -c1-12)
         n=$(grep -cF "$f" /tmp/isa_now/$o.isa || true)
         [ "$a" = "$b" ] && echo "identical  $o $f" || echo "CHANGED    $o $f ($n insts now)"
       done
