@@ -155,7 +155,15 @@ int rtKernelSetSchedule(rt_kernel k, int sched);
  * in *n_nodes -- the node contract of CLBVHnode.cpp:161-183, so the buffers bind to
  * KernelEntry as they are (the tree is the first *n_nodes records; the rest of a 2n-1 buffer is
  * ignored, see rtValidateBVH).  The tree is not the host SAH tree (hit IDs may differ where
- * triangles tie). */
+ * triangles tie).  Triangles past n_tris and every node record from *n_nodes to the buffer's end
+ * keep their bytes.  max_prims_in_node 0 builds as 1, above 65535 as 65535 (nPrimitives has 16
+ * bits).  The output is a function of the input alone (one rounding per fp32 operation, a stable
+ * sort), and its bounds follow the rule of rtRefitBVH, the fold from +inf / -inf included: a
+ * freshly built tree is a fixed point of the refit, for non-finite vertices too.
+ * Errors (nothing is written): RT_INVALID_VALUE for a method that is neither RT_BVH_*, n_tris == 0
+ * or >= 2^30, or a NULL n_nodes; RT_INVALID_MEM_OBJECT for a NULL buffer, another context's, or
+ * tris == nodes (the build would overwrite its own input); RT_INVALID_BUFFER_SIZE for `tris` under
+ * n_tris * 256 bytes or `nodes` under (2*n_tris - 1) * 48. */
 int rtBuildBVH(rt_context ctx, rt_mem tris, size_t n_tris, unsigned max_prims_in_node, rt_mem nodes,
                size_t* n_nodes);
 /* The same with the tree's topology chosen: RT_BVH_PLOC (rtBuildBVH's) or RT_BVH_LBVH. */

@@ -43,14 +43,17 @@ __device__ inline float3 tri_centroid(const rt_cl_triangle& t) {
                        (t.v1.position.z + t.v2.position.z + t.v3.position.z) * (1.0f / 3.0f));
 }
 
+// The bounds rule of rtRefitBVH (rt_hip.h): the fold starts from +inf / -inf, so an axis on which
+// all three vertices are NaN gives (+inf, -inf), never NaN -- a built tree is a fixed point of the refit.
 __device__ inline Box tri_box(const rt_cl_triangle& t) {
+    const float p[3][3] = {{t.v1.position.x, t.v1.position.y, t.v1.position.z},
+                           {t.v2.position.x, t.v2.position.y, t.v2.position.z},
+                           {t.v3.position.x, t.v3.position.y, t.v3.position.z}};
     Box b;
-    b.lo[0] = fminf(fminf(t.v1.position.x, t.v2.position.x), t.v3.position.x);
-    b.lo[1] = fminf(fminf(t.v1.position.y, t.v2.position.y), t.v3.position.y);
-    b.lo[2] = fminf(fminf(t.v1.position.z, t.v2.position.z), t.v3.position.z);
-    b.hi[0] = fmaxf(fmaxf(t.v1.position.x, t.v2.position.x), t.v3.position.x);
-    b.hi[1] = fmaxf(fmaxf(t.v1.position.y, t.v2.position.y), t.v3.position.y);
-    b.hi[2] = fmaxf(fmaxf(t.v1.position.z, t.v2.position.z), t.v3.position.z);
+    for (int k = 0; k < 3; ++k) {
+        b.lo[k] = fminf(fminf(fminf(INFINITY, p[0][k]), p[1][k]), p[2][k]);
+        b.hi[k] = fmaxf(fmaxf(fmaxf(-INFINITY, p[0][k]), p[1][k]), p[2][k]);
+    }
     return b;
 }
 

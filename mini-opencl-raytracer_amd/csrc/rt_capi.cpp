@@ -1117,6 +1117,7 @@ int rtBuildBVHEx(rt_context ctx, rt_mem tris, size_t n_tris, unsigned max_prims_
     if (rc) return rc;
     if (ctx->pend_k) (void)rti::flush_frames(ctx);
     if (!tris || !nodes || tris->ctx != ctx || nodes->ctx != ctx) return RT_INVALID_MEM_OBJECT;
+    if (tris == nodes) return RT_INVALID_MEM_OBJECT;  // the build would overwrite its own input
     if (!n_nodes || n_tris == 0 || n_tris >= (1u << 30)) return RT_INVALID_VALUE;
     if (tris->size < n_tris * sizeof(rt_cl_triangle)) return RT_INVALID_BUFFER_SIZE;
     if (nodes->size < (2 * n_tris - 1) * sizeof(rt_cl_bvh_node)) return RT_INVALID_BUFFER_SIZE;
