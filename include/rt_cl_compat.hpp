@@ -102,6 +102,9 @@ public:
                             const Buffer& surfaces, size_t n, size_t first = 0) const;
     inline void FrameFeatures(std::shared_ptr<CLKernel> kernel, size_t workSize, unsigned nFrames,
                               const Buffer& features) const;
+    // extension: the feature-guided a-trous denoiser over an image of 16-B slots (rtEnqueueDenoise)
+    inline void Denoise(std::shared_ptr<CLKernel> kernel, const Buffer& image, const Buffer& features, unsigned width,
+                        unsigned height, const rt_denoise_params& params, const Buffer& out) const;
     // extensions: moving geometry (rtEnqueueUpdateVertices, rtRefitBVH); normals may be null
     void UpdateVertices(const Buffer& tris, size_t firstTri, size_t nTris, const Buffer& positions,
                         const Buffer* normals = nullptr) const {
@@ -165,6 +168,12 @@ inline void CLContext::FrameFeatures(std::shared_ptr<CLKernel> kernel, size_t wo
                                      const Buffer& features) const {
     check(rtEnqueueFrameFeatures(ctx_, kernel->GetKernel(), workSize, nFrames, features.get()),
           "Failed to enqueue frame features");
+}
+inline void CLContext::Denoise(std::shared_ptr<CLKernel> kernel, const Buffer& image, const Buffer& features,
+                               unsigned width, unsigned height, const rt_denoise_params& params,
+                               const Buffer& out) const {
+    check(rtEnqueueDenoise(ctx_, kernel->GetKernel(), image.get(), features.get(), width, height, &params, out.get()),
+          "Failed to enqueue denoise");
 }
 inline void CLContext::RefitBVH(std::shared_ptr<CLKernel> kernel) const {
     check(rtRefitBVH(ctx_, kernel->GetKernel()), "Failed to refit BVH");

@@ -337,6 +337,54 @@ int rtEnqueueHitSurfaces(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem hits, 
                          rt_mem surfaces);
 int rtEnqueueFrameFeatures(rt_context ctx, rt_kernel k, size_t global_work_size, unsigned n_frames, rt_mem features);
 
+/* ---- feature-guided denoiser (extension) -----------------------------------------------------
+ * rtEnqueueDenoise filters a rendered image on the device with an edge-avoiding a-trous wavelet
+ * filter (Dammertz et al. 2010) guided by the buffer rtEnqueueFrameFeatures writes.  `image` and `out`
+ * hold width * height slots of 16 B, {r, g, b, w} fp32 (BUFFER_OUT's layout, and a gathered image's);
+ * `features` holds as many rt_pixel_features.  Pixel p = (x, y) is record y * width + x.  The filter
+ * is one definition in every math mode of `k`; every operation below is one correctly rounded fp32
+ * operation, nothing is contracted and denormals are kept.
+ *   iterations  i = 0 .. params->iterations - 1 with step s = 2^i; iteration 0 reads `image`, every
+ *               later one the output of the one before; the features are the same in all of them.
+ *   taps        q = p + s * (dx, dy), dy outer and dx inner, each -2 .. 2 in that order, with kernel
+ *               weight k = h[dy + 2] * h[dx + 2], h = {1/16, 1/4, 3/8, 1/4, 1/16}.  A tap whose q lies
+ *               outside the image or has coverage_q == 0 is skipped: it adds nothing.
+ *   centre      a pixel with coverage_p == 0 is copied unchanged, all 16 bytes.
+ *   weight      dot3(a) = (a.x * a.x + a.y * a.y) + a.z * a.z;  e(x) = m * m, m = max(0, 1 - x).
+ *               With c the iteration's input colour:
+ *                 x_c = dot3(c_p - c_q) * inv_c[i]          x_n = dot3(normal_p - normal_q) * inv_n
+ *                 d = (depth_p - depth_q) * rz_p,  x_z = (d * d) * inv_z,
+ *                     rz_p = 1.0f / max(fabsf(depth_p), 0x1p-64f), once per centre
+ *                 x_a = dot3(albedo_p - albedo_q) * inv_a
+ *                 w = (((k * e(x_c)) * e(x_n)) * e(x_z)) * e(x_a)
+ *               inv_X = 1.0f / (sigma_X * sigma_X), computed on the host in fp32; for colour the sigma
+ *               of iteration i is ldexpf(sigma_color, -i) (the tolerance halves per iteration).  A
+ *               sigma of 0 disables its term: it is left out of the product.
+ *   sums        sum_w += w; sum_r += w * c_q.r; likewise g and b; all four start at +0.0f.
+ *   output      rgb = sum_rgb / sum_w, three IEEE divisions (the centre tap has w = 9/64, so sum_w > 0);
+ *               the w slot is that pixel's w slot of `image`, carried through every iteration.
+ * Behaviour is specified for finite inputs.  Non-finite pixel or feature values may propagate in any
+ * way, but no value of either buffer ever becomes an address.
+ * Two or more iterations alternate between `out` and one scratch image of 16 B per pixel that the
+ * kernel object owns, grows before anything is enqueued and frees when it is released: iteration i
+ * writes `out` when iterations - 1 - i is even, else the scratch, so the last one lands in `out`.
+ * `image` and `features` are never written, and bytes of `out` past width * height * 16 are not touched.
+ * No scene need be bound to `k`.
+ * Ordering is a query's: asynchronous on the context's in-order queue, coalesced per-frame launches
+ * first, after the pending accumulations; `out` counts as written for the buffers' generations; with
+ * timing on the whole call adds to kernel_ms and counts as one launch.
+ * Errors (nothing is launched or allocated), checked in this order after the context and the kernel:
+ * params NULL, iterations outside 1 .. 5, a sigma that is negative, not finite, in (0, 2^-20) or above
+ * 2^20, width or height zero, or width * height > 2^31 RT_INVALID_VALUE; a buffer that is NULL or
+ * another context's, or `out` the same buffer as `image` or `features`, RT_INVALID_MEM_OBJECT; any of
+ * the three buffers too small RT_INVALID_BUFFER_SIZE. */
+typedef struct rt_denoise_params {
+    unsigned iterations;
+    float sigma_color, sigma_normal, sigma_depth, sigma_albedo;
+} rt_denoise_params;
+int rtEnqueueDenoise(rt_context ctx, rt_kernel k, rt_mem image, rt_mem features, unsigned width, unsigned height,
+                     const rt_denoise_params* params, rt_mem out);
+
 /* ---- moving geometry: vertex update + device-side BVH refit (extension) ----
  * For a mesh whose triangles move while the tree's shape stays put.  Both enqueue calls are
  * asynchronous on the context's in-order queue and never wait on the host: they launch the

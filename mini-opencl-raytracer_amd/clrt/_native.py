@@ -109,6 +109,13 @@ class Stats(ctypes.Structure):
                 ("render_period_ms", ctypes.c_double)]
 
 
+class DENOISE_PARAMS(ctypes.Structure):
+    """rt_denoise_params (rt_hip.h): rtEnqueueDenoise's iteration count and edge-stopping tolerances
+    (a sigma of 0 turns its term off)."""
+    _fields_ = [("iterations", ctypes.c_uint), ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_depth", ctypes.c_float), ("sigma_albedo", ctypes.c_float)]
+
+
 class Rect(ctypes.Structure):
     """rt_rect (rt_hip.h): one 2-D copy of the band gather's pack plan."""
     _fields_ = [("img_offset", ctypes.c_uint64), ("img_pitch", ctypes.c_uint64), ("width", ctypes.c_uint64),
@@ -150,6 +157,8 @@ _HIP_PROTOS = {
     "rtEnqueueCameraRays": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp]),
     "rtEnqueueHitSurfaces": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtEnqueueFrameFeatures": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint, _vp]),
+    "rtEnqueueDenoise": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
+                                        ctypes.POINTER(DENOISE_PARAMS), _vp]),
     "rtEnqueueUpdateVertices": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
     "rtRefitBVH": (ctypes.c_int, [_vp, _vp]),
     "rtDiagScenePrepares": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),

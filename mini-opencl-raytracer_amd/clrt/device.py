@@ -106,6 +106,17 @@ class CLContext:
         check(self._lib.rtEnqueueFrameFeatures(self.handle, kernel.handle, int(work_size), int(n_frames),
                                                features.handle), "Failed to enqueue frame features")
 
+    def Denoise(self, kernel: "CLKernel", image: "Buffer", features: "Buffer", width: int, height: int,
+                out: "Buffer", iterations: int = 3, sigma_color: float = 4.0, sigma_normal: float = 0.5,
+                sigma_depth: float = 0.1, sigma_albedo: float = 0.25) -> None:
+        """rtEnqueueDenoise: `iterations` passes of the edge-avoiding a-trous filter over the width x height
+        image of 16-B {r, g, b, w} slots in `image`, guided by the N.PIXEL_FEATURES_DTYPE records of
+        `features`, into `out`; a sigma of 0 turns its term off.  Asynchronous; neither input is written."""
+        params = N.DENOISE_PARAMS(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth),
+                                  float(sigma_albedo))
+        check(self._lib.rtEnqueueDenoise(self.handle, kernel.handle, image.handle, features.handle, int(width),
+                                         int(height), ctypes.byref(params), out.handle), "Failed to enqueue denoise")
+
     def UpdateVertices(self, tris: "Buffer", first: int, n: int, positions: "Buffer",
                        normals: "Buffer | None" = None) -> None:
         """rtEnqueueUpdateVertices: the position (and normal) xyz of triangles [first, first + n) of `tris`

@@ -48,6 +48,7 @@ class Raytracer:
         self._cast_bufs: tuple | None = None  # (capacity in rays, ray buffer, hit buffer) of cast()
         self._surf_buf: tuple | None = None   # (capacity in records, surface buffer) of surfaces()
         self._feat_buf: Buffer | None = None  # features(): width * height records
+        self._denoise_buf: Buffer | None = None  # denoise(): the filtered image, width * height slots
         self._move_bufs: tuple | None = None  # (capacity in triangles, positions, normals) of move_vertices()
         self._move_keep: list = []            # host arrays of uploads still in the queue
 
@@ -164,13 +165,47 @@ class Raytracer:
         N.PIXEL_FEATURES_DTYPE -- albedo, depth, normal and coverage averaged over the jittered camera
         rays of frames frame_count .. frame_count + n_frames - 1 at the current camera, the rays
         RenderFrame traces for those frames.  frame_count is left as it is."""
+        self._enqueue_features(n_frames)
+        out = np.empty((self.height, self.width), N.PIXEL_FEATURES_DTYPE)
+        self.ctx.ReadBuffer(self._feat_buf, out, blocking=True)
+        return out
+
+    def _enqueue_features(self, n_frames: int) -> Buffer:
+        """The features of frames frame_count .. frame_count + n_frames - 1 enqueued into the kept buffer."""
         self.set_uniforms()
         work = self.width * self.height
         if self._feat_buf is None:
             self._feat_buf = self.ctx.create_buffer(N.MEM_READ_WRITE, work * N.PIXEL_FEATURES_DTYPE.itemsize)
         self.ctx.FrameFeatures(self.kernel, work, n_frames, self._feat_buf)
-        out = np.empty((self.height, self.width), N.PIXEL_FEATURES_DTYPE)
-        self.ctx.ReadBuffer(self._feat_buf, out, blocking=True)
+        return self._feat_buf
+
+    def denoise(self, n_frames: int | None = None, iterations: int = 3, sigma_color: float = 4.0,
+                sigma_normal: float = 0.5, sigma_depth: float = 0.1, sigma_albedo: float = 0.25) -> np.ndarray:
+        """The accumulated image filtered on the device (rtEnqueueDenoise: an edge-avoiding a-trous wavelet
+        filter guided by first-hit albedo, depth, normal and coverage), as an (H, W, 4) float32 array.
+        The guides are features() over frames 1 .. n_frames; with n_frames None, over the frames rendered
+        so far (frame_count - 1 of them, the first 4096 at the most), whose jittered camera rays are the
+        ones the image was averaged over.  The accumulation buffer is only read -- the result goes into
+        a kept buffer of its own -- and frame_count stays, so the progressive render goes on.  A sigma
+        of 0 turns its edge-stopping term off.  The defaults suit a few frames per pixel; for a single
+        frame the colour term mostly sees noise, and sigma_color=0 filtered a 1-frame Cornell box
+        better in a host prototype (error 0.47 of the unfiltered image's against 0.78)."""
+        if n_frames is None:
+            n_frames = min(max(self.frame_count - 1, 1), 4096)
+        at = self.frame_count
+        self.frame_count = 1
+        try:
+            fb = self._enqueue_features(n_frames)
+        finally:
+            self.frame_count = at
+            self.kernel.set_uint(N.FRAME_COUNT, at)
+        work = self.width * self.height
+        if self._denoise_buf is None:
+            self._denoise_buf = self.ctx.create_buffer(N.MEM_READ_WRITE, work * 16)
+        self.ctx.Denoise(self.kernel, self.output, fb, self.width, self.height, self._denoise_buf, iterations,
+                         sigma_color, sigma_normal, sigma_depth, sigma_albedo)
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self.ctx.ReadBuffer(self._denoise_buf, out, blocking=True)
         return out
 
     def move_vertices(self, positions, normals=None, first: int = 0) -> None:
@@ -264,6 +299,9 @@ class Raytracer:
         if self._feat_buf:
             self._feat_buf.release()
             self._feat_buf = None
+        if self._denoise_buf:
+            self._denoise_buf.release()
+            self._denoise_buf = None
         if self._move_bufs:
             self._move_bufs[1].release()
             self._move_bufs[2].release()

@@ -30,6 +30,8 @@
 #include "../../include/rt_cl_types.h"
 #include "../../include/rt_hip.h"
 #include "rt_bvh.hpp"
+#include "rt_denoise.hpp"
+#include "rt_denoise_plan.hpp"
 #include "rt_device_scene.hpp"
 #include "rt_internal.hpp"
 #include "rt_kernels.hpp"
@@ -104,6 +106,7 @@ struct rt_kernel_s {
     uint64_t pf_waits = ~0ull;         // ctx->host_waits at the previous per-frame step launch
     rti::DeviceScene scene;  // the derived packed scene (rt_device_scene.hpp)
     rti::FeatureScratch feat;  // rtEnqueueFrameFeatures: a frame's camera rays and hits
+    rti::DenoiseScratch denoise;  // rtEnqueueDenoise: the ping-pong image
     bool last_lds = false;
     rtk::OccupancyCache occ;  // workgroups per CU of the kernels launched so far
 };
@@ -437,6 +440,7 @@ int rtReleaseKernel(rt_kernel k) {
     if (k->wf_cnt) (void)hipFree(k->wf_cnt);
     k->scene.release();
     k->feat.release();
+    k->denoise.release();
     if (k->dstats) (void)hipFree(k->dstats);
     if (k->work_counter) (void)hipFree(k->work_counter);
     if (k->accum_key) (void)hipFree(k->accum_key);
@@ -1099,6 +1103,67 @@ int rtEnqueueFrameFeatures(rt_context ctx, rt_kernel k, size_t global_work_size,
     if (e != hipSuccess) return map_hip(e);
     timed.end();
     mark_device_write(features, true);
+    rc = drain_if_many(k);
+    if (rc) return rc;
+    ++k->launches;
+    return pending_error(ctx, RT_SUCCESS);
+}
+
+// ---- feature-guided a-trous denoise (rt_denoise.hip; the plan: rt_denoise_plan.cpp) ---------------
+
+int rtEnqueueDenoise(rt_context ctx, rt_kernel k, rt_mem image, rt_mem features, unsigned width, unsigned height,
+                     const rt_denoise_params* params, rt_mem out) {
+    // 1. the handles and the plan: nothing is allocated or launched on an error
+    int rc = ensure_device(ctx);
+    if (rc) return rc;
+    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
+    rc = flush_first(ctx);
+    if (rc) return rc;
+    rtp::DenoiseIn in{};
+    in.params_ok = params != nullptr;
+    if (params) {
+        in.iterations = params->iterations;
+        in.sigma_color = params->sigma_color, in.sigma_normal = params->sigma_normal;
+        in.sigma_depth = params->sigma_depth, in.sigma_albedo = params->sigma_albedo;
+    }
+    in.width = width, in.height = height;
+    in.image_ok = image && image->ctx == ctx;
+    in.features_ok = features && features->ctx == ctx;
+    in.out_ok = out && out->ctx == ctx;
+    in.out_is_input = out && (out == image || out == features);
+    in.image_bytes = in.image_ok ? image->size : 0;
+    in.features_bytes = in.features_ok ? features->size : 0;
+    in.out_bytes = in.out_ok ? out->size : 0;
+    rtp::DenoisePlan p;
+    rc = rtp::denoise_plan(in, &p);
+    if (rc) return pending_error(ctx, rc);
+    // 2. the scratch, before anything is enqueued (growing it waits for nothing: rt_internal.hpp)
+    if (p.scratch_pixels) {
+        const hipError_t me = k->denoise.reserve((size_t)p.scratch_pixels);
+        if (me != hipSuccess) return map_hip(me);
+    }
+    // 3. one launch per iteration, in order on the context's stream after the pending accumulations
+    // and gathers
+    float4* const bufs[3] = {static_cast<float4*>(image->dptr), static_cast<float4*>(out->dptr), k->denoise.image()};
+    rtd::DenoiseArgs a{};
+    a.features = static_cast<const float4*>(features->dptr);
+    a.width = p.width, a.height = p.height;
+    a.terms = p.terms;
+    a.invN = p.inv_n, a.invZ = p.inv_z, a.invA = p.inv_a;
+    hipStream_t st = qs(ctx);
+    TimedLaunch timed{k, st, k->pending_events};
+    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
+    hipError_t e = hipSuccess;
+    for (unsigned i = 0; i < p.iterations && e == hipSuccess; ++i) {
+        const rtp::DenoiseStep& t = p.it[i];
+        a.src = bufs[t.src], a.dst = bufs[t.dst];
+        a.tilesX = t.tiles_x, a.tilesPerClass = t.tiles_per_class;
+        a.invC = t.inv_c;
+        e = rtd::launch_denoise(a, t, st);
+    }
+    if (e != hipSuccess) return map_hip(e);
+    timed.end();
+    mark_device_write(out, true);
     rc = drain_if_many(k);
     if (rc) return rc;
     ++k->launches;

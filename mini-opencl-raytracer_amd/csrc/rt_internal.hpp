@@ -103,29 +103,26 @@ struct rt_mem_s {
 
 namespace rti {
 
-// rtEnqueueFrameFeatures' scratch, owned by the kernel object: one frame's camera rays (32 B per
-// work-item) followed by their hits (16 B).  Grown before anything is enqueued and never freed while
-// launches may still read it: an outgrown block is kept until release() (the kernel's release, which
-// has drained the queue), so growing waits for nothing.  Capacities double, so the kept blocks
-// together are smaller than the live one.
-struct FeatureScratch {
+// Scratch owned by a kernel object: `items` records of a fixed size.  Grown before anything is enqueued
+// and never freed while launches may still read it: an outgrown block is kept until release() (the
+// kernel's release, which has drained the queue), so growing waits for nothing.  Capacities double,
+// so the kept blocks together are smaller than the live one.
+struct ScratchBlock {
     void* block = nullptr;
-    size_t items = 0;  // work-items the block holds
+    size_t items = 0;  // records the block holds
     std::vector<void*> outgrown;
 
-    hipError_t reserve(size_t n) {
+    hipError_t reserve(size_t n, size_t item_bytes) {
         if (n <= items) return hipSuccess;
         const size_t want = n > 2 * items ? n : 2 * items;
         void* b = nullptr;
-        const hipError_t e = hipMalloc(&b, want * 48);
+        const hipError_t e = hipMalloc(&b, want * item_bytes);
         if (e != hipSuccess) return e;
         if (block) outgrown.push_back(block);
         block = b;
         items = want;
         return hipSuccess;
     }
-    float4* rays() const { return static_cast<float4*>(block); }
-    float4* hits() const { return static_cast<float4*>(block) + 2 * items; }
     void release() {
         if (block) (void)hipFree(block);
         for (void* b : outgrown) (void)hipFree(b);
@@ -133,6 +130,20 @@ struct FeatureScratch {
         items = 0;
         outgrown.clear();
     }
+};
+
+// rtEnqueueFrameFeatures' scratch: one frame's camera rays (32 B per work-item) followed by their
+// hits (16 B).
+struct FeatureScratch : ScratchBlock {
+    hipError_t reserve(size_t n) { return ScratchBlock::reserve(n, 48); }
+    float4* rays() const { return static_cast<float4*>(block); }
+    float4* hits() const { return static_cast<float4*>(block) + 2 * items; }
+};
+
+// rtEnqueueDenoise's scratch: the ping-pong image of two or more iterations, 16 B per pixel.
+struct DenoiseScratch : ScratchBlock {
+    hipError_t reserve(size_t pixels) { return ScratchBlock::reserve(pixels, 16); }
+    float4* image() const { return static_cast<float4*>(block); }
 };
 
 inline int map_hip(hipError_t e) {
