@@ -798,6 +798,15 @@ __device__ __forceinline__ float4 rad_load(const float4* p) {
 // belong to partition b % nParts and take chunks there, statically first, then from its counter,
 // then -- once it is dry -- from the other partitions' counters.  Partition q's range, the number of
 // waves it starts statically and the first work item its counter hands out:
+// Lane 0's value as a scalar.  What one lane fetched for the whole wave (a work-counter grab, a
+// stolen range) comes back through v_readlane, not through a cross-lane shuffle: the compiler then
+// knows the value -- and every flag and count derived from it -- to be wave-uniform, keeps it in
+// scalar registers and branches on it with scalar branches instead of exec-mask bookkeeping.
+__device__ __forceinline__ uint32_t lane0(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 0); }
+__device__ __forceinline__ unsigned long long lane0(unsigned long long v) {
+    return ((unsigned long long)lane0((uint32_t)(v >> 32)) << 32) | lane0((uint32_t)v);
+}
+
 __device__ __forceinline__ void part_range(const KernelArgs& a, uint32_t q, uint32_t total, uint32_t& beg,
                                            uint32_t& end, uint32_t& cbase) {
     beg = min(q * a.partLen, total);
@@ -818,11 +827,11 @@ __device__ __forceinline__ bool next_chunk_parts(const KernelArgs& a, uint32_t t
             // another partition: skip it when its counter is already past its end (a plain read; a
             // stale value is smaller, and only costs the atomic below)
             if (lane == 0) b = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            b = __shfl(b, 0, 64);
+            b = lane0(b);
             if (cbase + b >= end) continue;
         }
         if (lane == 0) b = atomicAdd(ctr, a.tailChunk);
-        b = __shfl(b, 0, 64) + cbase;
+        b = lane0(b) + cbase;
         if (b < end) {
             base = b;
             len = min(a.tailChunk, end - b);
@@ -834,21 +843,21 @@ __device__ __forceinline__ bool next_chunk_parts(const KernelArgs& a, uint32_t t
 
 template <bool kFusedOnly>
 __device__ __forceinline__ bool next_chunk(const KernelArgs& a, uint32_t total, uint32_t lane, uint32_t& base,
-                                           uint32_t& len, bool& tail) {
+                                           uint32_t& len, uint32_t& tail) {
     if (!kFusedOnly && a.nParts > 1u) return next_chunk_parts(a, total, lane, base, len);
     uint32_t b = 0;
     if (!tail) {
         if (lane == 0) b = atomicAdd(&a.workCounter[0], a.chunkPixels);
-        b = __shfl(b, 0, 64);
+        b = lane0(b);
         if (b < a.chunkSplit) {
             base = b;
             len = min(a.chunkPixels, a.chunkSplit - b);
             return true;
         }
-        tail = true;  // this wave never asks the bulk counter again
+        tail = 1u;  // this wave never asks the bulk counter again
     }
     if (lane == 0) b = atomicAdd(&a.workCounter[1], a.tailChunk);
-    b = __shfl(b, 0, 64) + (kFusedOnly ? a.chunkSplit : a.tailBase);
+    b = lane0(b) + (kFusedOnly ? a.chunkSplit : a.tailBase);
     if (b >= total) return false;
     base = b;
     len = min(a.tailChunk, total - b);
@@ -908,8 +917,16 @@ __device__ __forceinline__ void finish_queued(const KernelArgs& a, const float4*
 #ifndef RT_TIMELINE_DIV
 #define RT_TIMELINE_DIV 1
 #endif
+// LDS walk: 4 -- a leaf holds at most 4 triangles, so one decision finishes every leaf it serves.
+// 2 until the decision went scalar: at 40 instructions the decision was worth a triangle test, at 24 the
+// idle slots of leaves with fewer triangles cost less than the decisions saved (1 / 2 / 3 / 4 / 5 / 6:
+// +2.7 % / 0 / +1.1 % / -2.1 % / tied with 4 or slower; profiles/r07/decision_ab.txt)
 #ifndef RT_TRI_BURST
-#define RT_TRI_BURST 2
+#define RT_TRI_BURST 4
+#endif
+// ... of the wavefront and ray-query kernels' LDS walks (their own decision loops; not re-swept)
+#ifndef RT_WTRI_BURST
+#define RT_WTRI_BURST 2
 #endif
 // (The step schedule keeps the accepted triangle's barycentrics during the walk rather than
 // re-evaluating them at shading: same bits, 4K Cornell 0.777 -> 0.773, bunny proxy 1.376 -> 1.364
@@ -922,15 +939,16 @@ __device__ __forceinline__ void finish_queued(const KernelArgs& a, const float4*
 #define RT_GNODE_BURST 6
 #endif
 #ifndef RT_GTRI_BURST
-#define RT_GTRI_BURST RT_TRI_BURST
+#define RT_GTRI_BURST 2
 #endif
 // ... and for the octant walk over HBM/L2: 5 under the pixel-major order (4: +1.1 %, 6: +0.6 %, 8: +1.0 %,
 // 3: +4.6 %; profiles/r05/goct_bursts_weights.txt; round 2's tile-major walk tied 3-5)
 #ifndef RT_ONODE_BURST
 #define RT_ONODE_BURST 5
 #endif
+// (triangle bursts of 3 cost the bunny proxy 0.9 %, 4 tie with 2: profiles/r07/decision_ab.txt)
 #ifndef RT_OTRI_BURST
-#define RT_OTRI_BURST RT_TRI_BURST
+#define RT_OTRI_BURST 2
 #endif
 
 
@@ -1001,12 +1019,12 @@ __device__ __noinline__ void lds_model(bool act, uint32_t key, uint32_t bank, bo
 // step -4 %, per-frame 4K launches -5 % (profiles/r03/steal_ab.txt).
 template <bool kFusedOnly>
 __device__ __forceinline__ bool take_tile(const KernelArgs& a, unsigned long long* steal, uint32_t me, uint32_t lane,
-                                          uint32_t total, uint32_t& chunk_base, uint32_t& chunk_len, bool& chunk_tail,
-                                          bool& dry, uint32_t& unit) {
+                                          uint32_t total, uint32_t& chunk_base, uint32_t& chunk_len, uint32_t& chunk_tail,
+                                          uint32_t& dry, uint32_t& unit) {
     if (!dry) {
         unsigned long long old = 0;
         if (lane == 0) old = atomicAdd(&steal[me], 64ull);
-        old = __shfl(old, 0, 64);
+        old = lane0(old);
         if ((uint32_t)old < (uint32_t)(old >> 32)) {
             unit = (uint32_t)old;
             return true;
@@ -1018,12 +1036,12 @@ __device__ __forceinline__ bool take_tile(const KernelArgs& a, unsigned long lon
             unit = chunk_base;
             return true;
         }
-        dry = true;
+        dry = 1u;
     }
     for (uint32_t k = 1; k < 4u; ++k) {
         unsigned long long old = 0;
         if (lane == 0) old = atomicAdd(&steal[(me + k) & 3u], 64ull);
-        old = __shfl(old, 0, 64);
+        old = lane0(old);
         if ((uint32_t)old < (uint32_t)(old >> 32)) {
             unit = (uint32_t)old;
             return true;
@@ -1140,7 +1158,13 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
     float4* ring_i = ring_d + kRingSlots;
     uint32_t* ring_g = reinterpret_cast<uint32_t*>(ring_d + (fused ? 2u : 1u) * kRingSlots);
     uint32_t rc_head = 0, rc_n = 0;  // wave-uniform: ring entries [rc_head, rc_head + rc_n)
-    bool dry = false;                // wave-uniform: the work counter is exhausted
+    // The wave-uniform flags that steer the loops below (dry, chunk_tail, exhausted) are 32-bit
+    // words fed from scalar sources only (ballots, kernel arguments, lane0): as `bool`s fed from a
+    // shuffle they lived in 64-bit lane masks, and every loop that tested one was compiled as a
+    // divergent loop -- exec-mask state at each back edge and break of the traversal loop
+    // (profiles/r07/decision_isa.txt).
+    uint32_t dry = 0u;               // wave-uniform: the work counter is exhausted
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((uint32_t)tid >> 6);  // wave in the workgroup
 
     LaneStats st;
     uint32_t state = kIdle;
@@ -1163,8 +1187,8 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
     // work: chunks of a.chunkPixels pixels (whole 8x8 tiles) from one global counter --
     // one returning atomic per chunk, so the counter stays far from its throughput limit
     uint32_t chunk_base = 0, chunk_len = 0;    // wave-uniform
-    bool chunk_tail = a.chunkSplit == 0u;                     // wave-uniform: no bulk region
-    bool exhausted = false;                    // wave-uniform
+    uint32_t chunk_tail = a.chunkSplit == 0u ? 1u : 0u;       // wave-uniform: no bulk region
+    uint32_t exhausted = 0u;                   // wave-uniform: no work left for this wave to take
     uint32_t tile_unit = 0, tile_used = 64;    // wave-uniform (HBM/L2 scene paths: the current tile)
     // diagnostic phase timers (stats variant only): shader-clock cycles per phase, per wave
     uint64_t cyc_refill = 0, cyc_trav = 0, cyc_shade = 0;
@@ -1185,6 +1209,16 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
     for (;;) {
         // ---- finish + refill: accumulate finished paths, start new pixels ----------------------
         uint64_t tA = kStats ? __builtin_amdgcn_s_memtime() : 0;
+        // "Refill is due" is decided here, once per outer iteration, and not again between
+        // traversal steps: no lane turns IDLE or DONE inside the traversal loop (a walk that ends
+        // parks at END / SHADE; DONE is only set at shading, IDLE only in this block), so the
+        // count of free lanes is what this block leaves behind.  If the block ran, it has turned
+        // every DONE lane IDLE and filled IDLE lanes until none was left or the work ran out
+        // (`exhausted`); if it did not run, n_free was below kRefillMin or `exhausted` was
+        // already set.  Either way `!exhausted && n_free >= kRefillMin` stays false while a lane
+        // has a walk to continue.  (bounces == 0 leaves the refill with 64 DONE lanes, an
+        // exhausted launch with IDLE ones: neither has a lane to walk, and the traversal loop
+        // ends at its first test, n_trav + n_leaf == 0.)
         const uint32_t n_free = popc_ballot(state == kIdle || state == kDone);
         if (n_free == 64u || (!exhausted && n_free >= kRefillMin)) {
             if (kStats) {
@@ -1246,9 +1280,9 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                 if (idle == 0ull) break;
                 if (rc_n == 0u) {
                     uint32_t unit = 0;  // the tile's first work item in the work order (wave-uniform)
-                    if (!take_tile<kMode == 1>(a, steal, (uint32_t)tid >> 6, (uint32_t)lane, total, chunk_base, chunk_len,
+                    if (!take_tile<kMode == 1>(a, steal, wave, (uint32_t)lane, total, chunk_base, chunk_len,
                                    chunk_tail, dry, unit)) {
-                        exhausted = true;
+                        exhausted = 1u;
 #if RT_TIMELINE
                         rt_dry = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1366,9 +1400,9 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                 if (idle == 0ull) break;
                 // tile_unit: the current tile's first work item, tile_used of its 64 handed out
                 if (tile_used >= 64u) {
-                    if (!take_tile<kMode == 1>(a, steal, (uint32_t)tid >> 6, (uint32_t)lane, total, chunk_base, chunk_len,
+                    if (!take_tile<kMode == 1>(a, steal, wave, (uint32_t)lane, total, chunk_base, chunk_len,
                                    chunk_tail, dry, tile_unit)) {
-                        exhausted = true;
+                        exhausted = 1u;
                         break;
                     }
                     tile_used = 0;
@@ -1454,6 +1488,11 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
         // triangle step (LEAF lanes test one triangle), chosen by which serves more lanes per
         // instruction (weights ~ the two bodies' VALU cost), so the wave never pays both
         // bodies for a mix of lanes.
+        // One classification per decision: the lanes at a node, in a leaf and at END (ready to
+        // shade) are counted once, every exit and the leaf-or-node choice is a scalar compare on
+        // those counts, and the END lanes of the last decision leave the loop as the shading
+        // predicate (`shade_now`: `cur` and `state` do not change between that ballot and a break).
+        bool shade_now = false;
         for (;;) {
             uint32_t n_trav, n_leaf;
             if (kLdsScene) {
@@ -1469,13 +1508,15 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                 n_trav = popc_ballot(state == kTrav);
                 n_leaf = popc_ballot(state == kLeaf);
             }
-            if (n_trav + n_leaf == 0u) break;
             // (the byte-address walk: a walk at END is ready to shade; its state is set at shading)
-            if (popc_ballot(kEndWord ? cur == kEndWalk : state == kShade) >= kShadeMin) break;
-            if (!exhausted && popc_ballot(state == kIdle || state == kDone) >= kRefillMin) break;
+            shade_now = kEndWord ? cur == kEndWalk : state == kShade;
+            const uint32_t n_end = popc_ballot(shade_now);
+            if (n_trav + n_leaf == 0u) break;
+            if (n_end >= kShadeMin) break;
+            // (no refill test here: see the refill decision above)
             const bool leaf_step = n_leaf * a.stepWeightNode > n_trav * a.stepWeightLeaf;
             if (kStats) {
-                u_shadew += popc_ballot(kEndWord ? cur == kEndWalk : state == kShade);
+                u_shadew += n_end;
                 u_freew += popc_ballot(state == kIdle || state == kDone);
                 u_other += leaf_step ? n_trav : n_leaf;
                 if (leaf_step) {
@@ -1604,13 +1645,13 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
         uint64_t tC = kStats ? __builtin_amdgcn_s_memtime() : 0;
         if (kStats) {
             cyc_trav += tC - tB;
-            const uint32_t ns = popc_ballot(kEndWord ? cur == kEndWalk : state == kShade);
+            const uint32_t ns = popc_ballot(shade_now);
             if (ns) {
                 ++u_srounds;
                 u_slanes += ns;
             }
         }
-        if (kEndWord ? cur == kEndWalk : state == kShade) {
+        if (shade_now) {
             if (kWalk && h.prim >= 0)  // the walk's byte address -> the triangle index, (addr - base) / 48
                 h.prim = (int32_t)(__umulhi((uint32_t)h.prim - a.octRecords * 16u, 0xAAAAAAABu) >> 5);
             if (bounce == 0u && a.hitIds) {  // primary hit outputs (extension); fused: last frame's

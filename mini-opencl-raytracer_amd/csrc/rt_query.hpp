@@ -142,7 +142,7 @@ __device__ __forceinline__ void query_body(const KernelArgs& a, const QueryArgs&
         // ---- traversal steps (kernel_bvh.cl:171-219 per lane) ----------------------------------
         const bool leaf_step = n_leaf * a.stepWeightNode > n_trav * a.stepWeightLeaf;
         constexpr int kNodeBurst = kGlobalOct ? RT_GNODE_BURST : RT_NODE_BURST;
-        constexpr int kTriBurst = kGlobalOct ? RT_GTRI_BURST : RT_TRI_BURST;
+        constexpr int kTriBurst = kGlobalOct ? RT_GTRI_BURST : RT_WTRI_BURST;
         if (!leaf_step) {
 #pragma unroll
             for (int rep = 0; rep < kNodeBurst; ++rep) {

@@ -212,7 +212,7 @@ __device__ __forceinline__ void wf_extend_body(const KernelArgs& a, const WfArgs
         // ---- traversal steps (step_body's, kernel_bvh.cl:171-219 per lane) ---------------------
         const bool leaf_step = n_leaf * a.stepWeightNode > n_trav * a.stepWeightLeaf;
         constexpr int kNodeBurst = kLdsScene ? RT_NODE_BURST : RT_GNODE_BURST;
-        constexpr int kTriBurst = kLdsScene ? RT_TRI_BURST : RT_GTRI_BURST;
+        constexpr int kTriBurst = kLdsScene ? RT_WTRI_BURST : RT_GTRI_BURST;
         if (!leaf_step) {
 #pragma unroll
             for (int rep = 0; rep < kNodeBurst; ++rep) {
