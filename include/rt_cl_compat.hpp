@@ -105,6 +105,11 @@ public:
     // extension: the feature-guided a-trous denoiser over an image of 16-B slots (rtEnqueueDenoise)
     inline void Denoise(std::shared_ptr<CLKernel> kernel, const Buffer& image, const Buffer& features, unsigned width,
                         unsigned height, const rt_denoise_params& params, const Buffer& out) const;
+    // extension: temporal reprojection of the previous image into the current view (rtEnqueueTemporalAccumulate);
+    // hist and histFeatures are both null when there is no history yet
+    inline void TemporalAccumulate(std::shared_ptr<CLKernel> kernel, const Buffer& cur, const Buffer& curFeatures,
+                                   const Buffer* hist, const Buffer* histFeatures, unsigned width, unsigned height,
+                                   const rt_temporal_params& params, const Buffer& out) const;
     // extensions: moving geometry (rtEnqueueUpdateVertices, rtRefitBVH); normals may be null
     void UpdateVertices(const Buffer& tris, size_t firstTri, size_t nTris, const Buffer& positions,
                         const Buffer* normals = nullptr) const {
@@ -174,6 +179,14 @@ inline void CLContext::Denoise(std::shared_ptr<CLKernel> kernel, const Buffer& i
                                const Buffer& out) const {
     check(rtEnqueueDenoise(ctx_, kernel->GetKernel(), image.get(), features.get(), width, height, &params, out.get()),
           "Failed to enqueue denoise");
+}
+inline void CLContext::TemporalAccumulate(std::shared_ptr<CLKernel> kernel, const Buffer& cur, const Buffer& curFeatures,
+                                          const Buffer* hist, const Buffer* histFeatures, unsigned width,
+                                          unsigned height, const rt_temporal_params& params, const Buffer& out) const {
+    check(rtEnqueueTemporalAccumulate(ctx_, kernel->GetKernel(), cur.get(), curFeatures.get(),
+                                      hist ? hist->get() : nullptr, histFeatures ? histFeatures->get() : nullptr, width,
+                                      height, &params, out.get()),
+          "Failed to enqueue temporal accumulate");
 }
 inline void CLContext::RefitBVH(std::shared_ptr<CLKernel> kernel) const {
     check(rtRefitBVH(ctx_, kernel->GetKernel()), "Failed to refit BVH");

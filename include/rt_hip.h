@@ -385,6 +385,82 @@ typedef struct rt_denoise_params {
 int rtEnqueueDenoise(rt_context ctx, rt_kernel k, rt_mem image, rt_mem features, unsigned width, unsigned height,
                      const rt_denoise_params* params, rt_mem out);
 
+/* ---- temporal reprojection (extension) --------------------------------------------------------
+ * rtEnqueueTemporalAccumulate carries an image across a camera move: for every pixel of the current
+ * view it rebuilds the world point from the feature buffer's depth, projects it into the previous
+ * camera, fetches the previous image bilinearly from the taps that lie on the same surface, and blends
+ * it with the current frames by per-pixel sample count.  `cur`, `hist` and `out` hold width * height
+ * slots of 16 B, {r, g, b, w} fp32 (BUFFER_OUT's layout, a denoised image's, and this call's own
+ * output); `cur_features` and `hist_features` hold as many rt_pixel_features, taken at params->cur and
+ * params->prev.  Pixel p = (x, y) is record y * width + x; out.w carries the pixel's sample count.
+ * `hist` and `hist_features` are both NULL (no history yet) or both buffers.  The blend runs on the
+ * stored, gamma-encoded values -- the space the denoiser filters in.
+ * The operation is one definition in every math mode of `k`; every operation below is one correctly
+ * rounded fp32 operation, nothing is contracted, denormals are kept, and comparisons are ordinary IEEE
+ * comparisons (false for a NaN).  W = width, H = height.
+ *   helpers     dot3(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z
+ *               cross(a, b) = (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x)
+ *   constants   computed on the host in fp32: A = 0x1.a82408p-2f (the fp32 nearest to tan of the fp32
+ *               0.5f * (45.0f * 3.1415f / 180.0f), kernel_bvh.cl:392); invW = 1.0f / (float)W,
+ *               invH = 1.0f / (float)H, asp = (float)W / (float)H, ia = 1.0f / (A * asp), ib = 1.0f / A,
+ *               right_c = cross(cur.front, cur.up), right_p = cross(prev.front, prev.up).
+ * Per pixel, with c = cur[p] and f = cur_features[p]; every "no history" below writes
+ * {c.r, c.g, c.b, cur_frames}:
+ *   1 centre    no history if `hist` is NULL or !(f.coverage > 0).
+ *   2 point     (the centre ray of CreateRay, the jitter at its mean)
+ *               sx = ((2.0f * (((float)x + 0.5f) * invW) - 1.0f) * A) * asp
+ *               sy = (2.0f * (((float)y + 0.5f) * invH) - 1.0f) * A
+ *               d = (right_c * sx + cur.up * sy) + cur.front, per component
+ *               u = d * (1.0f / sqrtf(dot3(d, d)));  X = cur.pos + u * f.depth
+ *   3 project   v = X - prev.pos;  zf = dot3(v, prev.front); no history unless zf > 0
+ *               a = dot3(v, right_p) / zf, b = dot3(v, prev.up) / zf (IEEE divisions)
+ *               fx = ((a * ia + 1.0f) * 0.5f) * (float)W - 0.5f
+ *               fy = ((b * ib + 1.0f) * 0.5f) * (float)H - 0.5f
+ *               de = sqrtf(dot3(v, v))
+ *               (the exact inverse of CreateRay only for a unit front perpendicular to a unit up, as
+ *               the reference's cameras are; an approximation for others, and as safe)
+ *   4 range     no history unless fx > -1.0f && fx < (float)W && fy > -1.0f && fy < (float)H; only
+ *               then x0f = floorf(fx), tx = fx - x0f, x0 = (int)x0f in [-1, W - 1]; likewise y.
+ *   5 taps      q = (x0 + i, y0 + j), j outer and i inner, each 0 then 1, with weight
+ *               bw = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty).  With
+ *               n_q = history_frames != 0 ? history_frames : hist[q].w a tap counts only when q lies
+ *               inside the image, hist_features[q].coverage > 0,
+ *               fabsf(hist_features[q].depth - de) <= depth_tolerance * de,
+ *               dot3(f.normal, hist_features[q].normal) >= normal_threshold, and n_q >= 1.0f.  A tap
+ *               that does not count adds nothing and is never multiplied in.  Sums start at +0.0f:
+ *               sw += bw; sr += bw * hist[q].r, likewise g and b; sn += bw * n_q.
+ *   6 blend     no history unless sw >= 0x1p-6f.  Otherwise h = s_rgb / sw, hn = sn / sw,
+ *               n = fminf(hn + cur_frames, max_history), alpha = cur_frames / n,
+ *               out.rgb = h + (c - h) * alpha per channel (difference, product, sum), out.w = n.
+ * This holds for every input bit pattern, non-finite ones included (IEEE leaves the sign and payload
+ * of a NaN result open): no index is formed from a coordinate that was not range-tested first, no
+ * float is converted to an integer outside [-1, 2^31), and taps that do not count are dropped by
+ * select, never by a multiplication with zero.
+ * `cur`, `hist` and both feature buffers are never written (inputs may alias one another), bytes of
+ * `out` past width * height * 16 are not touched, and no scene need be bound to `k`.
+ * Ordering is rtEnqueueDenoise's: asynchronous on the context's in-order queue, coalesced per-frame
+ * launches first, after the pending accumulations; `out` counts as written for the buffers'
+ * generations; with timing on the call adds to kernel_ms and counts as one launch.
+ * Errors (nothing is launched), checked in this order after the context and the kernel:
+ * RT_INVALID_VALUE for params NULL; width or height zero or width * height > 2^31; a camera component
+ * that is not finite; cur_frames not finite, < 1 or > 2^20; history_frames negative, not finite, in
+ * (0, 1) or > 2^20; max_history not finite, < cur_frames or > 2^20; depth_tolerance not finite or
+ * outside [0, 1]; normal_threshold not finite or outside [-1, 1].  RT_INVALID_MEM_OBJECT for exactly
+ * one of `hist` and `hist_features` NULL; a required buffer that is NULL or another context's; `out`
+ * the same buffer as any input.  RT_INVALID_BUFFER_SIZE for any buffer too small. */
+typedef struct rt_view { float pos[3], front[3], up[3]; } rt_view;
+typedef struct rt_temporal_params {
+    rt_view cur, prev;        /* cameras of `cur`/`cur_features` and of `hist`/`hist_features` */
+    float cur_frames;         /* frames averaged in `cur`, >= 1 */
+    float history_frames;     /* 0: a history pixel's sample count is its w slot; else this value for every pixel */
+    float max_history;        /* cap of the sample count, >= cur_frames */
+    float depth_tolerance;    /* relative, 0 .. 1 */
+    float normal_threshold;   /* -1 .. 1 */
+} rt_temporal_params;
+int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem cur_features,
+                                rt_mem hist /* may be NULL */, rt_mem hist_features /* NULL iff hist is */,
+                                unsigned width, unsigned height, const rt_temporal_params* params, rt_mem out);
+
 /* ---- moving geometry: vertex update + device-side BVH refit (extension) ----
  * For a mesh whose triangles move while the tree's shape stays put.  Both enqueue calls are
  * asynchronous on the context's in-order queue and never wait on the host: they launch the

@@ -116,6 +116,26 @@ class DENOISE_PARAMS(ctypes.Structure):
                 ("sigma_depth", ctypes.c_float), ("sigma_albedo", ctypes.c_float)]
 
 
+class VIEW(ctypes.Structure):
+    """rt_view (rt_hip.h): a camera's position, front and up vectors."""
+    _fields_ = [("pos", ctypes.c_float * 3), ("front", ctypes.c_float * 3), ("up", ctypes.c_float * 3)]
+
+
+class TEMPORAL_PARAMS(ctypes.Structure):
+    """rt_temporal_params (rt_hip.h): rtEnqueueTemporalAccumulate's two cameras, the frames averaged in the
+    current image, the history's sample count (0: its w slots), the cap of the count and the two
+    surface tests of a history tap."""
+    _fields_ = [("cur", VIEW), ("prev", VIEW), ("cur_frames", ctypes.c_float), ("history_frames", ctypes.c_float),
+                ("max_history", ctypes.c_float), ("depth_tolerance", ctypes.c_float),
+                ("normal_threshold", ctypes.c_float)]
+
+
+# tan of the fp32 0.5f * (45.0f * 3.1415f / 180.0f) rounded to fp32 (kernel_bvh.cl:392): the reprojection's A
+TEMPORAL_TAN_HALF_FOV = float.fromhex("0x1.a82408p-2")
+TEMPORAL_MAX_FRAMES = 2.0 ** 20
+TEMPORAL_MIN_WEIGHT = 2.0 ** -6
+
+
 class Rect(ctypes.Structure):
     """rt_rect (rt_hip.h): one 2-D copy of the band gather's pack plan."""
     _fields_ = [("img_offset", ctypes.c_uint64), ("img_pitch", ctypes.c_uint64), ("width", ctypes.c_uint64),
@@ -159,6 +179,8 @@ _HIP_PROTOS = {
     "rtEnqueueFrameFeatures": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint, _vp]),
     "rtEnqueueDenoise": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
                                         ctypes.POINTER(DENOISE_PARAMS), _vp]),
+    "rtEnqueueTemporalAccumulate": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
+                                                   ctypes.POINTER(TEMPORAL_PARAMS), _vp]),
     "rtEnqueueUpdateVertices": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
     "rtRefitBVH": (ctypes.c_int, [_vp, _vp]),
     "rtDiagScenePrepares": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),

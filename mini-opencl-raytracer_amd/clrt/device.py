@@ -117,6 +117,28 @@ class CLContext:
         check(self._lib.rtEnqueueDenoise(self.handle, kernel.handle, image.handle, features.handle, int(width),
                                          int(height), ctypes.byref(params), out.handle), "Failed to enqueue denoise")
 
+    def TemporalAccumulate(self, kernel: "CLKernel", cur: "Buffer", cur_features: "Buffer", hist: "Buffer | None",
+                           hist_features: "Buffer | None", width: int, height: int, out: "Buffer", cur_view,
+                           prev_view, cur_frames: float = 1.0, history_frames: float = 0.0,
+                           max_history: float = 32.0, depth_tolerance: float = 0.05,
+                           normal_threshold: float = 0.9) -> None:
+        """rtEnqueueTemporalAccumulate: the previous image `hist` (with its features, both None when
+        there is no history yet) reprojected from `prev_view` into `cur_view` and blended with `cur` by
+        per-pixel sample count into `out`; images are width x height 16-B {r, g, b, w} slots, `out`'s w
+        the new sample count.  A view is (position, front, up), three xyz triples.  Asynchronous; no
+        input is written."""
+        def view(v):
+            pos, front, up = v
+            return N.VIEW((ctypes.c_float * 3)(*map(float, pos)), (ctypes.c_float * 3)(*map(float, front)),
+                          (ctypes.c_float * 3)(*map(float, up)))
+        params = N.TEMPORAL_PARAMS(view(cur_view), view(prev_view), float(cur_frames), float(history_frames),
+                                   float(max_history), float(depth_tolerance), float(normal_threshold))
+        check(self._lib.rtEnqueueTemporalAccumulate(self.handle, kernel.handle, cur.handle, cur_features.handle,
+                                                    hist.handle if hist is not None else None,
+                                                    hist_features.handle if hist_features is not None else None,
+                                                    int(width), int(height), ctypes.byref(params), out.handle),
+              "Failed to enqueue temporal accumulate")
+
     def UpdateVertices(self, tris: "Buffer", first: int, n: int, positions: "Buffer",
                        normals: "Buffer | None" = None) -> None:
         """rtEnqueueUpdateVertices: the position (and normal) xyz of triangles [first, first + n) of `tris`

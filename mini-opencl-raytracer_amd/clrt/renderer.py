@@ -49,6 +49,10 @@ class Raytracer:
         self._surf_buf: tuple | None = None   # (capacity in records, surface buffer) of surfaces()
         self._feat_buf: Buffer | None = None  # features(): width * height records
         self._denoise_buf: Buffer | None = None  # denoise(): the filtered image, width * height slots
+        self._temporal_feat: list = [None, None]  # temporal(): this call's and the previous call's features
+        self._temporal_img: list = [None, None]   # ... and outputs; index _temporal_at is the history
+        self._temporal_at = 0
+        self._temporal_view: tuple | None = None  # the camera of the last temporal() (None: no history)
         self._move_bufs: tuple | None = None  # (capacity in triangles, positions, normals) of move_vertices()
         self._move_keep: list = []            # host arrays of uploads still in the queue
 
@@ -170,14 +174,17 @@ class Raytracer:
         self.ctx.ReadBuffer(self._feat_buf, out, blocking=True)
         return out
 
-    def _enqueue_features(self, n_frames: int) -> Buffer:
-        """The features of frames frame_count .. frame_count + n_frames - 1 enqueued into the kept buffer."""
+    def _enqueue_features(self, n_frames: int, into: Buffer | None = None) -> Buffer:
+        """The features of frames frame_count .. frame_count + n_frames - 1 enqueued into the kept buffer
+        (or `into`)."""
         self.set_uniforms()
         work = self.width * self.height
-        if self._feat_buf is None:
-            self._feat_buf = self.ctx.create_buffer(N.MEM_READ_WRITE, work * N.PIXEL_FEATURES_DTYPE.itemsize)
-        self.ctx.FrameFeatures(self.kernel, work, n_frames, self._feat_buf)
-        return self._feat_buf
+        if into is None:
+            if self._feat_buf is None:
+                self._feat_buf = self.ctx.create_buffer(N.MEM_READ_WRITE, work * N.PIXEL_FEATURES_DTYPE.itemsize)
+            into = self._feat_buf
+        self.ctx.FrameFeatures(self.kernel, work, n_frames, into)
+        return into
 
     def denoise(self, n_frames: int | None = None, iterations: int = 3, sigma_color: float = 4.0,
                 sigma_normal: float = 0.5, sigma_depth: float = 0.1, sigma_albedo: float = 0.25) -> np.ndarray:
@@ -207,6 +214,51 @@ class Raytracer:
         out = np.empty((self.height, self.width, 4), np.float32)
         self.ctx.ReadBuffer(self._denoise_buf, out, blocking=True)
         return out
+
+    def temporal(self, n_frames: int | None = None, max_history: float = 32.0, depth_tolerance: float = 0.05,
+                 normal_threshold: float = 0.9) -> np.ndarray:
+        """The accumulated image joined with the result of the previous temporal() call, which is
+        reprojected into the current camera on the device (rtEnqueueTemporalAccumulate), as an (H, W, 4)
+        float32 array whose w slot is the pixel's sample count (at most max_history, which is raised to
+        n_frames where it is below).  A history tap
+        counts only where it lies on the same surface: relative depth within depth_tolerance, normals'
+        dot product at least normal_threshold.  The guides are the features of frames 1 .. n_frames at
+        the current camera, as in denoise(); with n_frames None, of the frames rendered so far.  So after
+        a camera move (frame_count = 1 and a few new frames) the converged image is carried over instead
+        of thrown away.  The first call, and the first after reset_history(), has no history and returns
+        the image with w = n_frames.  Call reset_history() after move_vertices(): a moved surface
+        invalidates the reprojection, which knows the camera's motion only.  The accumulation buffer
+        is only read and frame_count stays, so the progressive render goes on."""
+        if n_frames is None:
+            n_frames = min(max(self.frame_count - 1, 1), 4096)
+        work = self.width * self.height
+        for bufs, size in ((self._temporal_feat, N.PIXEL_FEATURES_DTYPE.itemsize), (self._temporal_img, 16)):
+            for i in range(2):
+                if bufs[i] is None:
+                    bufs[i] = self.ctx.create_buffer(N.MEM_READ_WRITE, work * size)
+        prev, now = self._temporal_at, 1 - self._temporal_at
+        at = self.frame_count
+        self.frame_count = 1
+        try:
+            fb = self._enqueue_features(n_frames, self._temporal_feat[now])
+        finally:
+            self.frame_count = at
+            self.kernel.set_uint(N.FRAME_COUNT, at)
+        view = (tuple(self.camera.position), tuple(self.camera.front), tuple(self.camera.up))
+        has = self._temporal_view is not None
+        self.ctx.TemporalAccumulate(self.kernel, self.output, fb, self._temporal_img[prev] if has else None,
+                                    self._temporal_feat[prev] if has else None, self.width, self.height,
+                                    self._temporal_img[now], view, self._temporal_view if has else view,
+                                    float(n_frames), 0.0, max(float(max_history), float(n_frames)), depth_tolerance,
+                                    normal_threshold)
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self.ctx.ReadBuffer(self._temporal_img[now], out, blocking=True)
+        self._temporal_at, self._temporal_view = now, view
+        return out
+
+    def reset_history(self) -> None:
+        """Drop temporal()'s history: the next call starts from the current image alone."""
+        self._temporal_view = None
 
     def move_vertices(self, positions, normals=None, first: int = 0) -> None:
         """Move triangles [first, first + n) of the uploaded scene and refit its BVH on the device
@@ -302,6 +354,12 @@ class Raytracer:
         if self._denoise_buf:
             self._denoise_buf.release()
             self._denoise_buf = None
+        for bufs in (self._temporal_feat, self._temporal_img):
+            for i in range(2):
+                if bufs[i]:
+                    bufs[i].release()
+                    bufs[i] = None
+        self._temporal_view = None
         if self._move_bufs:
             self._move_bufs[1].release()
             self._move_bufs[2].release()

@@ -39,6 +39,8 @@
 #include "rt_query_plan.hpp"
 #include "rt_refit.hpp"
 #include "rt_scene_pack.hpp"
+#include "rt_temporal.hpp"
+#include "rt_temporal_plan.hpp"
 #include "rt_tuning.hpp"
 
 namespace {
@@ -1161,6 +1163,69 @@ int rtEnqueueDenoise(rt_context ctx, rt_kernel k, rt_mem image, rt_mem features,
         a.invC = t.inv_c;
         e = rtd::launch_denoise(a, t, st);
     }
+    if (e != hipSuccess) return map_hip(e);
+    timed.end();
+    mark_device_write(out, true);
+    rc = drain_if_many(k);
+    if (rc) return rc;
+    ++k->launches;
+    return pending_error(ctx, RT_SUCCESS);
+}
+
+// ---- temporal reprojection (rt_temporal.hip; the plan: rt_temporal_plan.cpp) -----------------------
+
+int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem cur_features, rt_mem hist,
+                                rt_mem hist_features, unsigned width, unsigned height,
+                                const rt_temporal_params* params, rt_mem out) {
+    // 1. the handles and the plan: nothing is launched on an error
+    int rc = ensure_device(ctx);
+    if (rc) return rc;
+    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
+    rc = flush_first(ctx);
+    if (rc) return rc;
+    rtp::TemporalIn in{};
+    in.params_ok = params != nullptr;
+    if (params) {
+        for (int c = 0; c < 3; ++c) {
+            in.cur.pos[c] = params->cur.pos[c], in.cur.front[c] = params->cur.front[c], in.cur.up[c] = params->cur.up[c];
+            in.prev.pos[c] = params->prev.pos[c], in.prev.front[c] = params->prev.front[c];
+            in.prev.up[c] = params->prev.up[c];
+        }
+        in.cur_frames = params->cur_frames, in.history_frames = params->history_frames;
+        in.max_history = params->max_history;
+        in.depth_tolerance = params->depth_tolerance, in.normal_threshold = params->normal_threshold;
+    }
+    in.width = width, in.height = height;
+    in.hist_given = hist != nullptr, in.hist_features_given = hist_features != nullptr;
+    in.cur_ok = cur && cur->ctx == ctx;
+    in.cur_features_ok = cur_features && cur_features->ctx == ctx;
+    in.out_ok = out && out->ctx == ctx;
+    in.hist_ok = hist && hist->ctx == ctx;
+    in.hist_features_ok = hist_features && hist_features->ctx == ctx;
+    in.out_is_input = out && (out == cur || out == cur_features || out == hist || out == hist_features);
+    in.cur_bytes = in.cur_ok ? cur->size : 0;
+    in.cur_features_bytes = in.cur_features_ok ? cur_features->size : 0;
+    in.hist_bytes = in.hist_ok ? hist->size : 0;
+    in.hist_features_bytes = in.hist_features_ok ? hist_features->size : 0;
+    in.out_bytes = in.out_ok ? out->size : 0;
+    rtp::TemporalPlan p;
+    rc = rtp::temporal_plan(in, &p);
+    if (rc) return pending_error(ctx, rc);
+    // 2. one launch, in order on the context's stream after the pending accumulations and gathers
+    rtt::TemporalArgs a{};
+    a.cur = static_cast<const float4*>(cur->dptr);
+    a.cur_features = static_cast<const float4*>(cur_features->dptr);
+    a.hist = p.has_history ? static_cast<const float4*>(hist->dptr) : nullptr;
+    a.hist_features = p.has_history ? static_cast<const float4*>(hist_features->dptr) : nullptr;
+    a.out = static_cast<float4*>(out->dptr);
+    a.width = p.width, a.height = p.height, a.tilesX = p.tiles_x;
+    a.cur_frames = p.cur_frames, a.history_frames = p.history_frames, a.max_history = p.max_history;
+    a.depth_tolerance = p.depth_tolerance, a.normal_threshold = p.normal_threshold;
+    a.k = p.k;
+    hipStream_t st = qs(ctx);
+    TimedLaunch timed{k, st, k->pending_events};
+    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
+    const hipError_t e = rtt::launch_temporal(a, p, st);
     if (e != hipSuccess) return map_hip(e);
     timed.end();
     mark_device_write(out, true);
