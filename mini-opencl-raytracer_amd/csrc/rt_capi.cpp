@@ -14,9 +14,12 @@
 // error code, never an out-of-bounds or non-terminating GPU walk.
 // That validation and the record packing live in rt_scene_pack.cpp, how a launch hands its work out
 // in rt_launch_plan.cpp, and rtKernelSetTuning's knobs in rt_tuning.cpp (all pure host code); the
-// packed scene and the rule that keeps it current in rt_device_scene.cpp.  A plan names its kernel
-// by a rtk::Variant, which the launch and the occupancy cache (rt_kernels.hpp) both take.  This file
-// keeps the other resources, the streams and the launches.
+// packed scene and the rule that keeps it current in rt_device_scene.cpp, the kernel's other device
+// resources (timing events, radiance sets, wavefront queues, work counters) in rt_kernel_state.cpp.
+// A plan names its kernel by a rtk::Variant, which the launch and the occupancy cache
+// (rt_kernels.hpp) both take.  A launch reads its argument slots from a rti::LaunchArgs value
+// (rt_launch_args.hpp): rtSetKernelArg alone writes the kernel's, and held-back frames launch with
+// their own copy.  This file keeps the objects, the streams and the launches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +37,7 @@
 #include "rt_denoise_plan.hpp"
 #include "rt_device_scene.hpp"
 #include "rt_internal.hpp"
+#include "rt_kernel_state.hpp"
 #include "rt_kernels.hpp"
 #include "rt_launch_plan.hpp"
 #include "rt_query_plan.hpp"
@@ -47,7 +51,6 @@ namespace {
 
 constexpr uint64_t kKnownFlags =
     RT_MEM_READ_WRITE | RT_MEM_WRITE_ONLY | RT_MEM_READ_ONLY | RT_MEM_COPY_HOST_PTR;
-constexpr int kStatWords = 20;                // rt_stats counters kept on the device
 #ifndef RT_TIMELINE
 #define RT_TIMELINE 0
 #endif
@@ -63,57 +66,45 @@ using rti::qs;
 
 struct rt_kernel_s {
     rt_context ctx = nullptr;
-    bool set[RT_ARG_COUNT] = {};
-    rt_mem bufs[4] = {};
-    uint32_t u32[RT_ARG_COUNT] = {};  // slots 4..10 (raw 4-byte values)
-    float f3[3][4] = {};              // slots 11..13
+    rti::LaunchArgs args;  // the 14 slots, written by rtSetKernelArg alone
     int math = RT_MATH_SHIPPED;  // the reference as its host builds it (rt_hip.h)
     int sched = RT_SCHED_STEP;
     rtp::Tuning tune;  // rtKernelSetTuning's knobs (rt_tuning.hpp)
     uint32_t band_period = 1, band_phase = 0;  // 8-row band interleave (multi-GPU sharding)
-    uint32_t* work_counter = nullptr;  // persistent schedules' chunk counters: [4] per render stream
-    uint32_t* accum_key = nullptr;     // sky-shortcut keys: [0..3] fused frames, [4..5] per-frame (zeroed once)
-    int pf_parity = 0;                 // per-frame key slot read by the next launch
-    int pf_ctr = 0;                    // per-frame chunk-counter slot of the next launch (RT_PF_COUNTER_SLOTS)
-    // wavefront schedule: ray queues (two sets of 4 float4 planes), hit records, stream counts
-    float4* wf_q[2] = {};
-    float2* wf_hits = nullptr;
-    size_t wf_cap = 0;                 // entries per plane
-    uint32_t* wf_cnt = nullptr;        // 2 x (G + 1) words
-    size_t wf_cnt_cap = 0;             // words
     uint64_t range_first = 0, range_last = 0;
     bool comm_sharded = false;  // bands set by rtCommShardKernel: the gather's plan needs the whole frame
     rt_mem hit_ids = nullptr, hit_t = nullptr;
     bool stats = false, timing = false, force_global = false;
-    unsigned long long* dstats = nullptr;  // device counters [4]
     uint64_t launches = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_events;  // KernelEntry launches
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_accum;   // fused frames' accumulation
-    std::vector<hipEvent_t> event_pool;
-    double kernel_ms = 0.0, accum_ms = 0.0;
-    // render period (rt_stats.render_period_ms): ends of consecutive timed renders
-    hipEvent_t first_end = nullptr;
-    double period_span_ms = 0.0;
-    uint64_t period_intervals = 0;
-    // fused frames: radiance and primary-miss flag per (frame slot, work-item), two sets used
-    // alternately so a render can run while the previous launch's accumulation reads the other
-    float4* rad_buf[RT_RAD_SETS] = {};
-    uint8_t* frame_flags[RT_RAD_SETS] = {};
-    size_t rad_buf_cap[RT_RAD_SETS] = {};  // float4 slots
-    size_t flag_cap[RT_RAD_SETS] = {};     // frame-flag bytes
-    hipEvent_t rad_free[RT_RAD_SETS] = {};  // recorded on astream after the accumulation reading the set
-    bool rad_busy[RT_RAD_SETS] = {};
-    int rad_set = 0;
-    hipEvent_t render_done = nullptr;  // recorded on the main stream after a fused render
     uint64_t pf_waits = ~0ull;         // ctx->host_waits at the previous per-frame step launch
-    rti::DeviceScene scene;  // the derived packed scene (rt_device_scene.hpp)
+    bool last_lds = false;
+    // the device resources, each with its own invariant (rt_device_scene.hpp, rt_kernel_state.hpp,
+    // rt_internal.hpp, rt_kernels.hpp)
+    rti::DeviceScene scene;  // the derived packed scene
+    rti::LaunchTimer timer;  // rtKernelSetTiming's event brackets
+    rti::RadianceSets rad;  // fused frames: radiance per (frame slot, work-item)
+    rti::WavefrontQueues wfq;  // wavefront schedule: ray queues
+    rti::WorkCounters counters;  // chunk counters, sky keys, rt_stats words
     rti::FeatureScratch feat;  // rtEnqueueFrameFeatures: a frame's camera rays and hits
     rti::DenoiseScratch denoise;  // rtEnqueueDenoise: the ping-pong image
-    bool last_lds = false;
     rtk::OccupancyCache occ;  // workgroups per CU of the kernels launched so far
+
+    // (the caller has drained the context's streams, or nothing was ever launched)
+    void release_parts() {
+        timer.release();
+        rad.release();
+        wfq.release();
+        counters.release();
+        scene.release();
+        feat.release();
+        denoise.release();
+    }
 };
 
 namespace {
+
+using rti::LaunchArgs;
+using rti::LaunchTimer;
 
 int ensure_device(rt_context ctx) {
     if (!ctx) return RT_INVALID_CONTEXT;
@@ -133,141 +124,69 @@ int pending_error(rt_context ctx, int rc) {
 // the context's coalesced frames, when they are `k`'s (a setting of k is about to change how
 // they would launch)
 void flush_kernel(rt_kernel k) {
-    if (k && k->ctx && k->ctx->pend_k == k) (void)rti::flush_frames(k->ctx);
+    if (k && k->ctx && k->ctx->held.k == k) (void)rti::flush_frames(k->ctx);
 }
 
 // another call touches the context: its coalesced frames launch first, and an error of theirs is
 // that call's status
 int flush_first(rt_context ctx) {
-    if (!ctx || !ctx->pend_k) return RT_SUCCESS;
     const int rc = rti::flush_frames(ctx);
     return rc ? pending_error(ctx, rc) : RT_SUCCESS;
 }
 
-// the arguments a coalesced launch compares (FRAME_COUNT continues the run; FRAME_SEED is never
-// read by KernelEntry, kernel_bvh.cl:415-456)
-bool same_args(const rt_context ctx, const rt_kernel k) {
-    for (int i = RT_ARG_WIDTH; i < RT_ARG_COUNT; ++i) {
-        if (i == RT_ARG_FRAME_COUNT || i == RT_ARG_FRAME_SEED || i >= RT_ARG_CAMERA_POS) continue;
-        if (ctx->pend_u32[i] != k->u32[i]) return false;
-    }
-    if (std::memcmp(ctx->pend_f3, k->f3, sizeof(k->f3)) != 0) return false;
-    return std::memcmp(ctx->pend_bufs, k->bufs, sizeof(k->bufs)) == 0;
-}
-
-
-// k's packed scene is that of its bound buffers (a malformed scene is refused here, before any launch)
-int prepare_scene(rt_kernel k) {
-    return k->scene.prepare(k->ctx, k->bufs[RT_ARG_BUFFER_SCENE], k->bufs[RT_ARG_BUFFER_NODE],
-                            k->bufs[RT_ARG_BUFFER_MATERIAL]);
-}
+// k's packed scene is that of the buffers bound in `a` (a malformed scene is refused here, before any
+// launch)
+int prepare_scene(rt_kernel k, const LaunchArgs& a) { return k->scene.prepare(k->ctx, a.tris(), a.nodes(), a.materials()); }
 
 // a render launch's arguments: every slot set, the work size, the image size, the output and hit
 // buffers (what enqueue checks first, and rtEnqueueKernel before it holds a frame back)
-int check_launch_args(rt_kernel k, size_t global_work_size) {
-    for (int i = 0; i < RT_ARG_COUNT; ++i)
-        if (!k->set[i]) return RT_INVALID_KERNEL_ARGS;
+int check_launch_args(rt_kernel k, const LaunchArgs& a, size_t global_work_size) {
+    if (!a.complete()) return RT_INVALID_KERNEL_ARGS;
     if (global_work_size == 0 || global_work_size > 0xffffffffull) return RT_INVALID_GLOBAL_WORK_SIZE;
-    if (k->u32[RT_ARG_WIDTH] == 0 || k->u32[RT_ARG_HEIGHT] == 0) return RT_INVALID_KERNEL_ARGS;
-    if (k->bufs[RT_ARG_BUFFER_OUT]->size < global_work_size * 16) return RT_INVALID_GLOBAL_WORK_SIZE;
+    if (a.width() == 0 || a.height() == 0) return RT_INVALID_KERNEL_ARGS;
+    if (a.out()->size < global_work_size * 16) return RT_INVALID_GLOBAL_WORK_SIZE;
     if (k->hit_ids && (k->hit_ids->size < (global_work_size + kHitPad) * 4 || k->hit_t->size < global_work_size * 4))
         return RT_INVALID_MEM_OBJECT;
     return RT_SUCCESS;
 }
 
-// the image size, the frame count and the camera slots
-void fill_camera(rt_kernel k, rtk::KernelArgs* a) {
-    a->width = k->u32[RT_ARG_WIDTH], a->height = k->u32[RT_ARG_HEIGHT], a->frameCount = k->u32[RT_ARG_FRAME_COUNT];
+// the image size, the frame and the camera slots
+void fill_camera(const LaunchArgs& la, uint32_t frame, rtk::KernelArgs* a) {
+    a->width = la.width(), a->height = la.height(), a->frameCount = frame;
     for (int i = 0; i < 3; ++i) {
-        a->camPos[i] = k->f3[0][i];
-        a->camFront[i] = k->f3[1][i];
-        a->camUp[i] = k->f3[2][i];
+        a->camPos[i] = la.f3[0][i];
+        a->camFront[i] = la.f3[1][i];
+        a->camUp[i] = la.f3[2][i];
     }
 }
 
-hipEvent_t take_event(rt_kernel k) {
-    if (!k->event_pool.empty()) {
-        hipEvent_t e = k->event_pool.back();
-        k->event_pool.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
-
-using EventList = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
-
-// The timing bracket of one launch on `st` (rtKernelSetTiming; nothing without it): an event before
-// the launch and one after, kept in `list` until drain_events reads them.
-struct TimedLaunch {
-    rt_kernel k;
-    hipStream_t st;
-    EventList& list;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-
-    bool begin() {  // false: no events to be had
-        if (!k->timing) return true;
-        ev0 = take_event(k);
-        ev1 = take_event(k);
-        if (!ev0 || !ev1) return false;
-        (void)hipEventRecord(ev0, st);
-        return true;
-    }
-    void end() {
-        if (!k->timing) return;
-        (void)hipEventRecord(ev1, st);
-        list.emplace_back(ev0, ev1);
-    }
-};
-
-static int drain_list(rt_kernel k, std::vector<std::pair<hipEvent_t, hipEvent_t>>& list, double& total,
-                      bool renders) {
-    for (auto& pr : list) {
-        float ms = 0.0f;
-        hipError_t e = hipEventSynchronize(pr.second);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, pr.first, pr.second);
-        if (e != hipSuccess) return map_hip(e);
-        total += ms;
-        if (renders) {
-            // render period: end of the first timed render to end of the latest one
-            if (!k->first_end) {
-                k->first_end = pr.second;
-            } else {
-                float span = 0.0f;
-                e = hipEventElapsedTime(&span, k->first_end, pr.second);
-                if (e != hipSuccess) return map_hip(e);
-                k->period_span_ms = span;
-                ++k->period_intervals;
-                k->event_pool.push_back(pr.second);
-            }
-            k->event_pool.push_back(pr.first);
-            continue;
-        }
-        k->event_pool.push_back(pr.first);
-        k->event_pool.push_back(pr.second);
-    }
-    list.clear();
-    return RT_SUCCESS;
-}
-
-int drain_events(rt_kernel k) {
-    int rc = drain_list(k, k->pending_events, k->kernel_ms, true);
+// The shared head of the calls that launch on the context's queue for a kernel: the device, the
+// kernel handle, the buffers that must be the context's, then the coalesced frames.
+int queue_head(rt_context ctx, rt_kernel k, std::initializer_list<rt_mem> mems) {
+    const int rc = ensure_device(ctx);
     if (rc) return rc;
-    return drain_list(k, k->pending_accum, k->accum_ms, false);
+    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
+    for (rt_mem m : mems)
+        if (!m || m->ctx != ctx) return RT_INVALID_MEM_OBJECT;
+    return flush_first(ctx);
 }
 
-// after a launch: the brackets nobody has read yet stay bounded
-int drain_if_many(rt_kernel k) {
-    if (k->pending_events.size() + k->pending_accum.size() <= 4096) return RT_SUCCESS;
-    return drain_events(k);
-}
-
-void reset_period(rt_kernel k) {
-    if (k->first_end) k->event_pool.push_back(k->first_end);
-    k->first_end = nullptr;
-    k->period_span_ms = 0.0;
-    k->period_intervals = 0;
+// The shared tail of the auxiliary enqueues.  `launch(st)` issues the call's launch or launches on
+// the context's stream, after the pending accumulations and gathers and inside the kernel's timing
+// bracket; `written` then counts as written by the device and the call as one launch.
+template <class Launch>
+int launch_on_queue(rt_context ctx, rt_kernel k, rt_mem written, Launch&& launch) {
+    hipStream_t st = qs(ctx);
+    LaunchTimer::Bracket timed = k->timer.bracket(k->timing, st, LaunchTimer::kRender);
+    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
+    const hipError_t e = launch(st);
+    if (e != hipSuccess) return map_hip(e);
+    timed.end();
+    mark_device_write(written, true);
+    const int rc = k->timer.drain_if_many();
+    if (rc) return rc;
+    ++k->launches;
+    return pending_error(ctx, RT_SUCCESS);
 }
 
 }  // namespace
@@ -398,17 +317,9 @@ int rtCreateKernel(rt_context ctx, const char* name, rt_kernel* out) {
     rt_kernel k = new (std::nothrow) rt_kernel_s();
     if (!k) return RT_OUT_OF_HOST_MEMORY;
     k->ctx = ctx;
-    hipError_t e = hipMalloc(&k->dstats, kStatWords * sizeof(unsigned long long));
-    // fused radiance sets' counters (16 B each), then the two per-frame slots of kMaxParts counter
-    // partitions kPartStride words apart
-    const size_t wc_bytes = 16 * RT_RAD_SETS + 2 * sizeof(uint32_t) * rtk::kMaxParts * rtk::kPartStride;
-    if (e == hipSuccess) e = hipMalloc(&k->work_counter, wc_bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(k->work_counter, 0, wc_bytes, qs(ctx));
-    if (e == hipSuccess) e = hipMalloc(&k->accum_key, 32);
-    if (e == hipSuccess) e = hipMemsetAsync(k->accum_key, 0, 32, qs(ctx));
-    if (e == hipSuccess) e = hipMemsetAsync(k->dstats, 0, kStatWords * sizeof(unsigned long long), qs(ctx));
-    if (e == hipSuccess) e = hipStreamSynchronize(qs(ctx));
+    const hipError_t e = k->counters.create(qs(ctx));
     if (e != hipSuccess) {
+        k->release_parts();
         delete k;
         return map_hip(e);
     }
@@ -422,30 +333,8 @@ int rtReleaseKernel(rt_kernel k) {
     if (rc) return rc;
     flush_kernel(k);
     (void)hipStreamSynchronize(qs(k->ctx));
-    for (auto* list : {&k->pending_events, &k->pending_accum})
-        for (auto& pr : *list) {
-            (void)hipEventDestroy(pr.first);
-            (void)hipEventDestroy(pr.second);
-        }
     (void)hipStreamSynchronize(k->ctx->astream);
-    for (int i = 0; i < RT_RAD_SETS; ++i) {
-        if (k->rad_buf[i]) (void)hipFree(k->rad_buf[i]);
-        if (k->frame_flags[i]) (void)hipFree(k->frame_flags[i]);
-        if (k->rad_free[i]) (void)hipEventDestroy(k->rad_free[i]);
-    }
-    if (k->render_done) (void)hipEventDestroy(k->render_done);
-    if (k->first_end) (void)hipEventDestroy(k->first_end);
-    for (hipEvent_t e : k->event_pool) (void)hipEventDestroy(e);
-    for (float4* q : k->wf_q)
-        if (q) (void)hipFree(q);
-    if (k->wf_hits) (void)hipFree(k->wf_hits);
-    if (k->wf_cnt) (void)hipFree(k->wf_cnt);
-    k->scene.release();
-    k->feat.release();
-    k->denoise.release();
-    if (k->dstats) (void)hipFree(k->dstats);
-    if (k->work_counter) (void)hipFree(k->work_counter);
-    if (k->accum_key) (void)hipFree(k->accum_key);
+    k->release_parts();
     delete k;
     return RT_SUCCESS;
 }
@@ -458,20 +347,22 @@ int rtSetKernelArg(rt_kernel k, unsigned index, size_t size, const void* value) 
         if (size != sizeof(rt_mem)) return RT_INVALID_ARG_SIZE;
         rt_mem m = *static_cast<const rt_mem*>(value);
         if (!m || m->ctx != k->ctx) return RT_INVALID_MEM_OBJECT;
-        k->bufs[index] = m;
+        k->args.bufs[index] = m;
     } else if (index <= RT_ARG_SKYBOX_INTENSITY) {
         if (size != 4) return RT_INVALID_ARG_SIZE;
-        std::memcpy(&k->u32[index], value, 4);
+        std::memcpy(&k->args.u32[index], value, 4);
     } else {
         if (size != 16) return RT_INVALID_ARG_SIZE;
-        std::memcpy(k->f3[index - RT_ARG_CAMERA_POS], value, 16);
+        std::memcpy(k->args.f3[index - RT_ARG_CAMERA_POS], value, 16);
     }
-    k->set[index] = true;
+    k->args.set[index] = true;
     return RT_SUCCESS;
 }
 
-static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_t n_frames);
-
+// frames first_frame .. first_frame + n_frames - 1 of `k` with the arguments `args` (whose
+// FRAME_COUNT slot is not read), as one launch
+static int enqueue(rt_context ctx, rt_kernel k, const rti::LaunchArgs& args, size_t global_work_size,
+                   uint32_t first_frame, uint32_t n_frames);
 
 }  // extern "C"
 
@@ -482,24 +373,11 @@ void rti::unpin(rt_mem m) {
 }
 
 int rti::flush_frames(rt_context ctx) {
-    if (!ctx || !ctx->pend_k) return RT_SUCCESS;
-    rt_kernel k = ctx->pend_k;
-    ctx->pend_k = nullptr;  // (enqueue's own qs() calls find nothing pending)
-    // launch with the arguments the frames were enqueued with, then give the kernel back its own
-    uint32_t u32[RT_ARG_COUNT];
-    float f3[3][4];
-    rt_mem bufs[4];
-    std::memcpy(u32, k->u32, sizeof(u32));
-    std::memcpy(f3, k->f3, sizeof(f3));
-    std::memcpy(bufs, k->bufs, sizeof(bufs));
-    std::memcpy(k->u32, ctx->pend_u32, sizeof(u32));
-    std::memcpy(k->f3, ctx->pend_f3, sizeof(f3));
-    std::memcpy(k->bufs, ctx->pend_bufs, sizeof(bufs));
-    std::memcpy(&k->u32[RT_ARG_FRAME_COUNT], &ctx->pend_f0, 4);
-    const int rc = enqueue(ctx, k, ctx->pend_gws, ctx->pend_n);
-    std::memcpy(k->u32, u32, sizeof(u32));
-    std::memcpy(k->f3, f3, sizeof(f3));
-    std::memcpy(k->bufs, bufs, sizeof(bufs));
+    if (!ctx || !ctx->held.k) return RT_SUCCESS;
+    // taken out first: enqueue's own qs() calls find nothing held.  The frames launch with the
+    // arguments they were enqueued with, whatever the kernel's slots hold by now
+    const HeldFrames h = ctx->held.take();
+    const int rc = enqueue(ctx, h.k, h.args, h.gws, h.f0, h.n);
     if (rc != RT_SUCCESS && ctx->pend_error == RT_SUCCESS) ctx->pend_error = rc;
     return rc;
 }
@@ -519,75 +397,58 @@ int rtEnqueueKernel(rt_context ctx, rt_kernel k, size_t global_work_size) {
                           !k->timing && !ctx->mexposed && !ctx->dexposed;
     if (!coalesce) {
         const int rc = flush_first(ctx);
-        return rc ? rc : enqueue(ctx, k, global_work_size, 1);
+        if (rc) return rc;
+        if (!k) {  // (after the context's own check, as enqueue orders them)
+            const int dc = ensure_device(ctx);
+            return dc ? dc : RT_INVALID_KERNEL;
+        }
+        return enqueue(ctx, k, k->args, global_work_size, k->args.frame_count(), 1);
     }
     int rc = ensure_device(ctx);
     if (rc) return rc;
-    rc = check_launch_args(k, global_work_size);
+    rc = check_launch_args(k, k->args, global_work_size);
     if (rc) return rc;
-    const uint32_t f = k->u32[RT_ARG_FRAME_COUNT];
+    const uint32_t f = k->args.frame_count();
     // an error of an earlier held launch is reported now, and this frame is not queued: the
     // caller retrying it starts a fresh run instead of accumulating it twice
     if (ctx->pend_error != RT_SUCCESS) return pending_error(ctx, RT_SUCCESS);
-    if (ctx->pend_k == k && ctx->pend_gws == global_work_size && ctx->pend_n < k->tune.pf_batch &&
-        f == ctx->pend_f0 + ctx->pend_n && f != 0u && same_args(ctx, k)) {
-        ++ctx->pend_n;  // the next frame of the run
+    if (ctx->held.continues(k, global_work_size, k->args, f, k->tune.pf_batch)) {
+        ++ctx->held.n;  // the next frame of the run
         return RT_SUCCESS;
     }
     rc = flush_first(ctx);
     if (rc) return rc;
-    rc = prepare_scene(k);  // (a malformed scene is refused now, not at the launch)
+    rc = prepare_scene(k, k->args);  // (a malformed scene is refused now, not at the launch)
     if (rc) return rc;
-    ctx->pend_k = k;
-    ctx->pend_gws = global_work_size;
-    ctx->pend_f0 = f;
-    ctx->pend_n = 1;
-    std::memcpy(ctx->pend_u32, k->u32, sizeof(k->u32));
-    std::memcpy(ctx->pend_f3, k->f3, sizeof(k->f3));
-    std::memcpy(ctx->pend_bufs, k->bufs, sizeof(k->bufs));
+    ctx->held = rti::HeldFrames{k, global_work_size, f, 1, k->args};
     return pending_error(ctx, RT_SUCCESS);
 }
 
 int rtEnqueueKernelFrames(rt_context ctx, rt_kernel k, size_t global_work_size, unsigned n_frames) {
     if (n_frames == 0) return RT_INVALID_VALUE;
     if (const int rc = flush_first(ctx)) return rc;
-    if (n_frames == 1 || !k || (k->sched != RT_SCHED_STEP && k->sched != RT_SCHED_WAVEFRONT)) {
-        // one launch per frame (the other schedules have no fused form): same results
-        if (!k) return RT_INVALID_KERNEL;
-        uint32_t f0;
-        std::memcpy(&f0, &k->u32[RT_ARG_FRAME_COUNT], 4);
-        int rc = RT_SUCCESS;
-        for (unsigned i = 0; i < n_frames && rc == RT_SUCCESS; ++i) {
-            const uint32_t f = f0 + i;
-            std::memcpy(&k->u32[RT_ARG_FRAME_COUNT], &f, 4);
-            rc = enqueue(ctx, k, global_work_size, 1);
-        }
-        std::memcpy(&k->u32[RT_ARG_FRAME_COUNT], &f0, 4);
-        return rc;
-    }
-    // fused launches of at most kMaxFusedFrames frames each
-    uint32_t f0;
-    std::memcpy(&f0, &k->u32[RT_ARG_FRAME_COUNT], 4);
+    if (!k) return RT_INVALID_KERNEL;
+    // fused launches of at most kMaxFusedFrames frames each; one launch per frame for a single frame
+    // and for the schedules that have no fused form: same results
+    const bool fuse = n_frames > 1 && (k->sched == RT_SCHED_STEP || k->sched == RT_SCHED_WAVEFRONT);
+    const uint32_t f0 = k->args.frame_count();
     int rc = RT_SUCCESS;
     for (unsigned done = 0; done < n_frames && rc == RT_SUCCESS;) {
-        const unsigned n = std::min<unsigned>(n_frames - done, rtk::kMaxFusedFrames);
-        const uint32_t f = f0 + done;
-        std::memcpy(&k->u32[RT_ARG_FRAME_COUNT], &f, 4);
-        rc = enqueue(ctx, k, global_work_size, n);
+        const unsigned n = fuse ? std::min<unsigned>(n_frames - done, rtk::kMaxFusedFrames) : 1;
+        rc = enqueue(ctx, k, k->args, global_work_size, f0 + done, n);
         done += n;
     }
-    std::memcpy(&k->u32[RT_ARG_FRAME_COUNT], &f0, 4);
     return rc;
 }
 
 // ---- enqueue's steps: the resources, streams and launches of one LaunchPlan (rt_launch_plan.hpp) ----
 
 // the plan's inputs: plain values of the launch, the kernel's settings and its packed scene
-static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_t n_frames, bool fused) {
+static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, const LaunchArgs& la, size_t global_work_size,
+                               uint32_t n_frames, bool fused) {
     rtp::PlanIn in{};
-    std::memcpy(&in.W, &k->u32[RT_ARG_WIDTH], 4);
-    std::memcpy(&in.H, &k->u32[RT_ARG_HEIGHT], 4);
-    std::memcpy(&in.light_bounces, &k->u32[RT_ARG_LIGHT_BOUNCES], 4);
+    in.W = la.width(), in.H = la.height();
+    in.light_bounces = la.light_bounces();
     in.gws = global_work_size;
     in.range_first = k->range_first, in.range_last = k->range_last;
     in.n_frames = n_frames;
@@ -607,12 +468,13 @@ static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, size_t global_work_s
 
 // KernelEntry's arguments: the plan's scalars plus the kernel's pointers (the radiance set and the
 // work counters follow, once their resources are there)
-static void fill_args(rt_kernel k, const rtp::LaunchPlan& p, rtk::KernelArgs* args) {
+static void fill_args(rt_kernel k, const LaunchArgs& la, uint32_t first_frame, const rtp::LaunchPlan& p,
+                      rtk::KernelArgs* args) {
     rtk::KernelArgs& a = *args;
     std::memset(&a, 0, sizeof(a));
-    a.result = static_cast<float4*>(k->bufs[RT_ARG_BUFFER_OUT]->dptr);
-    a.trisFull = static_cast<const rt_cl_triangle*>(k->bufs[RT_ARG_BUFFER_SCENE]->dptr);
-    a.materials = static_cast<const rt_cl_material*>(k->bufs[RT_ARG_BUFFER_MATERIAL]->dptr);
+    a.result = static_cast<float4*>(la.out()->dptr);
+    a.trisFull = static_cast<const rt_cl_triangle*>(la.tris()->dptr);
+    a.materials = static_cast<const rt_cl_material*>(la.materials()->dptr);
     const rti::DeviceScene& sc = k->scene;
     a.packedTris = sc.packed_tris();
     a.octNodes = p.regrouped ? sc.goct() : sc.oct_nodes();
@@ -621,10 +483,9 @@ static void fill_args(rt_kernel k, const rtp::LaunchPlan& p, rtk::KernelArgs* ar
     a.shadeMats = sc.shade_mats() + (k->math == RT_MATH_SHIPPED ? 4 * (size_t)sc.n_mats() : 0);
     a.nMats = sc.n_mats(), a.nTris = sc.n_tris();
     a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords, a.nTop = p.nTop;
-    fill_camera(k, &a);
-    std::memcpy(&a.lightBounces, &k->u32[RT_ARG_LIGHT_BOUNCES], 4);
-    std::memcpy(&a.lightType, &k->u32[RT_ARG_LIGHT_TYPE], 4);
-    std::memcpy(&a.skyboxIntensity, &k->u32[RT_ARG_SKYBOX_INTENSITY], 4);
+    fill_camera(la, first_frame, &a);
+    a.lightBounces = la.light_bounces(), a.lightType = la.light_type();
+    a.skyboxIntensity = la.skybox_intensity();
     a.gidBegin = p.gidBegin, a.gidEnd = p.gidEnd;
     a.rowBegin = p.rowBegin, a.rowCount = p.rowCount, a.tilesX = p.tilesX, a.nTiles = p.nTiles;
     a.bandPeriod = p.bandPeriod, a.bandPhase = p.bandPhase;
@@ -635,38 +496,13 @@ static void fill_args(rt_kernel k, const rtp::LaunchPlan& p, rtk::KernelArgs* ar
     a.flagTiles = p.flagTiles, a.tileMajor = p.tileMajor, a.nFrames = p.nFrames, a.radStride = p.radStride;
     a.hitIds = k->hit_ids ? static_cast<int32_t*>(k->hit_ids->dptr) : nullptr;
     a.hitT = k->hit_t ? static_cast<float*>(k->hit_t->dptr) : nullptr;
-    a.stats = k->dstats;
+    a.stats = k->counters.stats();
     // per-frame launches: their own counters (two slots in turn with RT_PF_COUNTER_SLOTS, below)
-    a.workCounter = k->work_counter + 4 * RT_RAD_SETS;
+    a.workCounter = k->counters.per_frame();
     if (p.use_pf_sky) {
-        a.pfKeyIn = k->accum_key + 4 + k->pf_parity;
-        a.pfKeyOut = k->accum_key + 4 + (k->pf_parity ^ 1);
+        a.pfKeyIn = k->counters.key_in();
+        a.pfKeyOut = k->counters.key_out();
     }
-}
-
-// radiance set `rs` holds `need` radiance slots and `fneed` frame-flag bytes, and the events that
-// order its renders and accumulations exist
-static int ensure_radiance_set(rt_context ctx, rt_kernel k, int rs, size_t need, size_t fneed) {
-    if (k->rad_buf_cap[rs] >= need && k->flag_cap[rs] >= fneed) return RT_SUCCESS;
-    // the set may still be read by an accumulation in flight
-    hipError_t me = hipStreamSynchronize(ctx->astream);
-    if (me != hipSuccess) return map_hip(me);
-    if (k->rad_buf[rs]) (void)hipFree(k->rad_buf[rs]);
-    if (k->frame_flags[rs]) (void)hipFree(k->frame_flags[rs]);
-    k->rad_buf[rs] = nullptr;
-    k->frame_flags[rs] = nullptr;
-    k->rad_buf_cap[rs] = 0;
-    k->flag_cap[rs] = 0;
-    me = hipMalloc(&k->rad_buf[rs], need * sizeof(float4));
-    if (me == hipSuccess) me = hipMalloc(&k->frame_flags[rs], fneed);
-    if (me == hipSuccess && !k->rad_free[rs])
-        me = hipEventCreateWithFlags(&k->rad_free[rs], hipEventDisableTiming);
-    if (me == hipSuccess && !k->render_done)
-        me = hipEventCreateWithFlags(&k->render_done, hipEventDisableTiming);
-    if (me != hipSuccess) return map_hip(me);
-    k->rad_buf_cap[rs] = need;
-    k->flag_cap[rs] = fneed;
-    return RT_SUCCESS;
 }
 
 // the stream a fused render of radiance set `rs` goes to, made to wait for what it must follow
@@ -682,42 +518,7 @@ static int pick_render_stream(rt_context ctx, rt_kernel k, bool own_stream, int 
         if (me != hipSuccess) return map_hip(me);
     }
     // the render writes the set: after the accumulation that last read it
-    if (k->rad_busy[rs]) {
-        hipError_t me = hipStreamWaitEvent(*rstr, k->rad_free[rs], 0);
-        if (me != hipSuccess) return map_hip(me);
-        k->rad_busy[rs] = false;
-    }
-    return RT_SUCCESS;
-}
-
-// the wavefront schedule's ray queues hold `cap` entries per plane, its counts G streams
-static int ensure_wavefront_queues(rt_kernel k, size_t cap, uint32_t G, hipStream_t rstr) {
-    if (k->wf_cap < cap) {
-        // earlier renders on this stream may still read them
-        hipError_t me = hipStreamSynchronize(rstr);
-        for (float4*& q : k->wf_q) {
-            if (q) (void)hipFree(q);
-            q = nullptr;
-        }
-        if (k->wf_hits) (void)hipFree(k->wf_hits);
-        k->wf_hits = nullptr;
-        k->wf_cap = 0;
-        for (float4*& q : k->wf_q)
-            if (me == hipSuccess) me = hipMalloc(&q, cap * 4 * sizeof(float4));
-        if (me == hipSuccess) me = hipMalloc(&k->wf_hits, cap * sizeof(float2));
-        if (me != hipSuccess) return map_hip(me);
-        k->wf_cap = cap;
-    }
-    if (k->wf_cnt_cap < 2 * ((size_t)G + 1)) {
-        hipError_t me = hipStreamSynchronize(rstr);
-        if (k->wf_cnt) (void)hipFree(k->wf_cnt);
-        k->wf_cnt = nullptr;
-        k->wf_cnt_cap = 0;
-        if (me == hipSuccess) me = hipMalloc(&k->wf_cnt, 2 * ((size_t)G + 1) * sizeof(uint32_t));
-        if (me != hipSuccess) return map_hip(me);
-        k->wf_cnt_cap = 2 * ((size_t)G + 1);
-    }
-    return RT_SUCCESS;
+    return map_hip(k->rad.wait_free(rs, *rstr));
 }
 
 // fused frames: the gamma accumulation of every frame, in order, per pixel -- on the
@@ -736,47 +537,41 @@ static int enqueue_accum(rt_context ctx, rt_kernel k, const rtk::KernelArgs& a, 
     hipError_t e = hipSuccess;
     if (ctx->overlap) {
         as = ctx->astream;
-        e = hipEventRecord(k->render_done, rstr);
-        if (e == hipSuccess) e = hipStreamWaitEvent(as, k->render_done, 0);
+        e = k->rad.after_render(rstr, as);
         if (e != hipSuccess) return fail(map_hip(e));
     }
-    TimedLaunch timed{k, as, k->pending_accum};
+    LaunchTimer::Bracket timed = k->timer.bracket(k->timing, as, LaunchTimer::kAccum);
     if (!timed.begin()) return fail(RT_OUT_OF_RESOURCES);
     // (a root's gather copies of the previous image read `out`: the accumulation that rewrites
     // it comes after them)
     e = rti::out_read_wait(ctx, as);
     if (e != hipSuccess) return fail(map_hip(e));
 #ifndef RT_DIAG_NO_ACCUM  // diagnostic A/B builds only (wrong images): the render without its accumulation
-    e = rtk::launch_accum_frames(a, k->math, k->accum_key, as);
+    e = rtk::launch_accum_frames(a, k->math, k->counters.fused_keys(), as);
     if (e != hipSuccess) return fail(map_hip(e));
 #endif
     timed.end();
     if (ctx->overlap) {
-        const int rs = k->rad_set;
-        e = hipEventRecord(k->rad_free[rs], as);
-        if (e == hipSuccess) e = hipEventRecord(ctx->atail, as);
+        e = k->rad.accumulated(as, ctx->atail);
         if (e != hipSuccess) return map_hip(e);
-        k->rad_busy[rs] = true;
-        k->rad_set = (k->rad_set + 1) % RT_RAD_SETS;
         ctx->apending = true;
     }
     return RT_SUCCESS;
 }
 
-static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_t n_frames) {
+static int enqueue(rt_context ctx, rt_kernel k, const LaunchArgs& args, size_t global_work_size,
+                   uint32_t first_frame, uint32_t n_frames) {
     // 1. the handles, the arguments, the scene
     int rc = ensure_device(ctx);
     if (rc) return rc;
     if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
-    rc = check_launch_args(k, global_work_size);
+    rc = check_launch_args(k, args, global_work_size);
     if (rc) return rc;
-    rc = prepare_scene(k);
+    rc = prepare_scene(k, args);
     if (rc) return rc;
 
     // 2. defer, fused
-    int32_t lb;
-    std::memcpy(&lb, &k->u32[RT_ARG_LIGHT_BOUNCES], 4);
-    const int si = rtp::resolve_schedule(k->sched, lb);
+    const int si = rtp::resolve_schedule(k->sched, args.light_bounces());
     const bool wf = si == rtk::kSchedWavefront;
     // radiance per (frame slot, work-item) + the accumulation launch: fused frames, every wavefront
     // render, and (RT_TUNE_PERFRAME_DEFER) per-frame step launches -- then consecutive renders need
@@ -802,7 +597,7 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     if (!fused) (void)qs(ctx);
 
     // 3. the plan (rt_launch_plan.cpp), with the kernel's occupancy at the LDS size it chose
-    const rtp::PlanIn in = plan_inputs(ctx, k, global_work_size, n_frames, fused);
+    const rtp::PlanIn in = plan_inputs(ctx, k, args, global_work_size, n_frames, fused);
     rtp::LaunchPlan p;
     rc = rtp::plan_shape(in, &p);
     if (rc || p.nothing) return rc;
@@ -812,20 +607,20 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
 
     // 4. the kernel's arguments
     rtk::KernelArgs a;
-    fill_args(k, p, &a);
+    fill_args(k, args, first_frame, p, &a);
 
     // 5, 6. fused: the radiance set and the stream this launch's render goes to
     hipStream_t rstr = ctx->stream;
     if (fused) {
-        const int rs = ctx->overlap ? k->rad_set : 0;
-        rc = ensure_radiance_set(ctx, k, rs, p.need, p.fneed);
+        const int rs = k->rad.current(ctx->overlap);
+        rc = k->rad.ensure(ctx, rs, p.need, p.fneed);
         if (rc) return rc;
         rc = pick_render_stream(ctx, k, p.own_stream, rs, &rstr);
         if (rc) return rc;
-        a.radBuf = k->rad_buf[rs];
-        a.frameFlags = k->frame_flags[rs];
+        a.radBuf = k->rad.radiance(rs);
+        a.frameFlags = k->rad.flags(rs);
         // one chunk counter per radiance set: renders of the two sets may run together
-        a.workCounter = k->work_counter + 4 * rs;
+        a.workCounter = k->counters.fused(rs);
     }
     // everything below (counter clear, timing events, the render; the accumulation when it is not
     // overlapped) goes to rstr: the main stream unless a render stream was taken above
@@ -837,30 +632,30 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
     float4* wq[2] = {};
     uint32_t* wcnt[2] = {};
     if (wf) {
-        rc = ensure_wavefront_queues(k, (size_t)p.cap, p.G, rstr);
+        rc = k->wfq.ensure((size_t)p.cap, p.G, rstr);
         if (rc) return rc;
-        wq[0] = k->wf_q[0], wq[1] = k->wf_q[1];
-        wcnt[0] = k->wf_cnt, wcnt[1] = k->wf_cnt + p.G + 1;
-        wa.hits = k->wf_hits;
+        wq[0] = k->wfq.queue(0), wq[1] = k->wfq.queue(1);
+        wcnt[0] = k->wfq.counts(0, p.G), wcnt[1] = k->wfq.counts(1, p.G);
+        wa.hits = k->wfq.hits();
         wa.cap = p.cap, wa.G = p.G, wa.nBlocks = p.nBlocks, wa.refillMin = p.wfRefillMin;
     }
 
     // 8. the counter slot or clear, the timing events, the launch
     if (p.pf_slots) {
-        a.workCounter = k->work_counter + 4 * RT_RAD_SETS + k->pf_ctr * rtk::kMaxParts * rtk::kPartStride;
-        a.workCounterClear = k->work_counter + 4 * RT_RAD_SETS + (k->pf_ctr ^ 1) * rtk::kMaxParts * rtk::kPartStride;
+        a.workCounter = k->counters.per_frame_in_use();
+        a.workCounterClear = k->counters.per_frame_to_clear();
     } else if (p.clear_counter_here) {
         hipError_t me = hipMemsetAsync(a.workCounter, 0, 16, rstr);
         if (me != hipSuccess) return map_hip(me);
     }
-    TimedLaunch timed{k, rstr, k->pending_events};
+    LaunchTimer::Bracket timed = k->timer.bracket(k->timing, rstr, LaunchTimer::kRender);
     if (!timed.begin()) return RT_OUT_OF_RESOURCES;
     hipError_t e = wf ? rtk::launch_wavefront(a, wa, wq, wcnt, v, (unsigned)p.grid, p.smem, p.grid_s, rstr)
                       : rtk::launch_kernel_entry(a, v, (unsigned)p.grid, p.smem, rstr);
     if (e != hipSuccess) return map_hip(e);
     timed.end();
-    if (a.pfKeyIn) k->pf_parity ^= 1;
-    if (p.pf_slots) k->pf_ctr ^= 1;  // flips only when the launch call reported success
+    if (a.pfKeyIn) k->counters.flip_key();
+    if (p.pf_slots) k->counters.flip_per_frame_slot();  // flips only when the launch call reported success
 
     // 9. fused: the accumulation launch
     if (fused) {
@@ -868,7 +663,7 @@ static int enqueue(rt_context ctx, rt_kernel k, size_t global_work_size, uint32_
         if (rc) return rc;
     }
     // 10. bookkeeping
-    rc = drain_if_many(k);
+    rc = k->timer.drain_if_many();
     if (rc) return rc;
     ++k->launches;
     return RT_SUCCESS;
@@ -909,7 +704,7 @@ static void fill_query_args(rt_kernel k, const rtp::QueryPlan& p, const float4* 
     a.nTris = k->scene.n_tris();
     a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords;
     a.stepWeightNode = p.stepWeightNode, a.stepWeightLeaf = p.stepWeightLeaf;
-    a.stats = k->dstats;
+    a.stats = k->counters.stats();
     rtk::QueryArgs& q = *qargs;
     q = rtk::QueryArgs{};
     q.rays = rays;
@@ -920,18 +715,14 @@ static void fill_query_args(rt_kernel k, const rtp::QueryPlan& p, const float4* 
 int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t first_ray, size_t n_rays, int mode,
                            rt_mem hits) {
     // 1. the handles and the range: no scene is packed and nothing launched on an error
-    int rc = ensure_device(ctx);
-    if (rc) return rc;
-    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
-    if (!rays || !hits || rays->ctx != ctx || hits->ctx != ctx) return RT_INVALID_MEM_OBJECT;
-    rc = flush_first(ctx);
+    int rc = queue_head(ctx, k, {rays, hits});
     if (rc) return rc;
     rtp::QueryPlan p;
     rc = rtp::query_shape(query_inputs(ctx, k, rays->size, first_ray, n_rays, mode, hits->size, rays == hits, false), &p);
     if (rc || p.nothing) return pending_error(ctx, rc);
-    if (!k->set[RT_ARG_BUFFER_SCENE] || !k->set[RT_ARG_BUFFER_NODE]) return RT_INVALID_KERNEL_ARGS;
+    if (!k->args.has({RT_ARG_BUFFER_SCENE, RT_ARG_BUFFER_NODE})) return RT_INVALID_KERNEL_ARGS;
     // 2. the scene, packed and validated as a render launch does (materials only when bound)
-    rc = prepare_scene(k);
+    rc = prepare_scene(k, k->args);
     if (rc) return rc;
     // 3. the plan, with the kernel's occupancy at the LDS size it chose
     const rtp::QueryIn in = query_inputs(ctx, k, rays->size, first_ray, n_rays, mode, hits->size, false, true);
@@ -943,34 +734,21 @@ int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t firs
     rtk::QueryArgs q;
     fill_query_args(k, p, static_cast<const float4*>(rays->dptr), static_cast<float4*>(hits->dptr), &a, &q);
     // 5. the launch, on the context's stream after the pending accumulations and gathers
-    hipStream_t st = qs(ctx);
     k->last_lds = p.variant.lds();
-    TimedLaunch timed{k, st, k->pending_events};
-    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
-    const hipError_t e = rtk::launch_query(a, q, p.variant, p.grid, p.smem, st);
-    if (e != hipSuccess) return map_hip(e);
-    timed.end();
-    mark_device_write(hits, true);
-    rc = drain_if_many(k);
-    if (rc) return rc;
-    ++k->launches;
-    return pending_error(ctx, RT_SUCCESS);
+    return launch_on_queue(ctx, k, hits,
+                           [&](hipStream_t st) { return rtk::launch_query(a, q, p.variant, p.grid, p.smem, st); });
 }
 
 int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem rays) {
-    int rc = ensure_device(ctx);
+    const int rc = queue_head(ctx, k, {rays});
     if (rc) return rc;
-    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
-    if (!rays || rays->ctx != ctx) return RT_INVALID_MEM_OBJECT;
-    rc = flush_first(ctx);
-    if (rc) return rc;
-    for (int i : {RT_ARG_WIDTH, RT_ARG_HEIGHT, RT_ARG_FRAME_COUNT, RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT,
-                  RT_ARG_CAMERA_UP})
-        if (!k->set[i]) return RT_INVALID_KERNEL_ARGS;
+    if (!k->args.has({RT_ARG_WIDTH, RT_ARG_HEIGHT, RT_ARG_FRAME_COUNT, RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT,
+                      RT_ARG_CAMERA_UP}))
+        return RT_INVALID_KERNEL_ARGS;
     if (global_work_size == 0 || global_work_size > 0xffffffffull) return RT_INVALID_GLOBAL_WORK_SIZE;
     rtk::KernelArgs a;
     std::memset(&a, 0, sizeof(a));
-    fill_camera(k, &a);
+    fill_camera(k->args, k->args.frame_count(), &a);
     if (a.width == 0 || a.height == 0) return RT_INVALID_KERNEL_ARGS;
     if (rays->size / sizeof(rt_ray) < global_work_size) return RT_INVALID_BUFFER_SIZE;
     const hipError_t e =
@@ -986,7 +764,7 @@ int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt
 static void fill_surface_args(rt_kernel k, rtk::KernelArgs* args) {
     rtk::KernelArgs& a = *args;
     std::memset(&a, 0, sizeof(a));
-    a.trisFull = static_cast<const rt_cl_triangle*>(k->bufs[RT_ARG_BUFFER_SCENE]->dptr);
+    a.trisFull = static_cast<const rt_cl_triangle*>(k->args.tris()->dptr);
     a.packedTris = k->scene.packed_tris();
     a.shadeTris = k->scene.shade_tris();
     a.nTris = k->scene.n_tris();
@@ -995,11 +773,7 @@ static void fill_surface_args(rt_kernel k, rtk::KernelArgs* args) {
 int rtEnqueueHitSurfaces(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem hits, size_t first, size_t n,
                          rt_mem surfaces) {
     // 1. the handles and the range: no scene is packed and nothing launched on an error
-    int rc = ensure_device(ctx);
-    if (rc) return rc;
-    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
-    if (!rays || !hits || rays->ctx != ctx || hits->ctx != ctx) return RT_INVALID_MEM_OBJECT;
-    rc = flush_first(ctx);
+    int rc = queue_head(ctx, k, {rays, hits});
     if (rc) return rc;
     rtp::SurfaceIn in{};
     in.first = first, in.n = n;
@@ -1008,12 +782,12 @@ int rtEnqueueHitSurfaces(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem hits, 
     in.out_bytes = in.out_ok ? surfaces->size : 0;
     in.out_is_input = surfaces == rays || surfaces == hits;
     in.rays_is_hits = rays == hits;
-    in.scene_bound = k->set[RT_ARG_BUFFER_SCENE] && k->set[RT_ARG_BUFFER_NODE];
+    in.scene_bound = k->args.has({RT_ARG_BUFFER_SCENE, RT_ARG_BUFFER_NODE});
     rtp::SurfacePlan p;
     rc = rtp::surface_plan(in, &p);
     if (rc || p.nothing) return pending_error(ctx, rc);
     // 2. the scene, packed and validated as a query does (materials only when bound)
-    rc = prepare_scene(k);
+    rc = prepare_scene(k, k->args);
     if (rc) return rc;
     // 3. the arguments
     rtk::KernelArgs a;
@@ -1024,40 +798,27 @@ int rtEnqueueHitSurfaces(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem hits, 
     s.out = static_cast<float4*>(surfaces->dptr);
     s.first = p.first, s.count = p.count;
     // 4. the launch, on the context's stream after the pending accumulations and gathers
-    hipStream_t st = qs(ctx);
-    TimedLaunch timed{k, st, k->pending_events};
-    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
-    const hipError_t e = rtk::launch_surfaces(a, s, k->math, false, p.grid, st);
-    if (e != hipSuccess) return map_hip(e);
-    timed.end();
-    mark_device_write(surfaces, true);
-    rc = drain_if_many(k);
-    if (rc) return rc;
-    ++k->launches;
-    return pending_error(ctx, RT_SUCCESS);
+    return launch_on_queue(ctx, k, surfaces,
+                           [&](hipStream_t st) { return rtk::launch_surfaces(a, s, k->math, false, p.grid, st); });
 }
 
 int rtEnqueueFrameFeatures(rt_context ctx, rt_kernel k, size_t global_work_size, unsigned n_frames, rt_mem features) {
     // 1. the handles and the arguments: nothing is allocated or launched on an error
-    int rc = ensure_device(ctx);
-    if (rc) return rc;
-    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
-    if (!features || features->ctx != ctx) return RT_INVALID_MEM_OBJECT;
-    rc = flush_first(ctx);
+    int rc = queue_head(ctx, k, {features});
     if (rc) return rc;
     if (n_frames == 0 || n_frames > rtp::kMaxFeatureFrames) return RT_INVALID_VALUE;
-    for (int i : {RT_ARG_BUFFER_SCENE, RT_ARG_BUFFER_NODE, RT_ARG_BUFFER_MATERIAL, RT_ARG_WIDTH, RT_ARG_HEIGHT,
-                  RT_ARG_FRAME_COUNT, RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT, RT_ARG_CAMERA_UP})
-        if (!k->set[i]) return RT_INVALID_KERNEL_ARGS;
+    if (!k->args.has({RT_ARG_BUFFER_SCENE, RT_ARG_BUFFER_NODE, RT_ARG_BUFFER_MATERIAL, RT_ARG_WIDTH, RT_ARG_HEIGHT,
+                      RT_ARG_FRAME_COUNT, RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT, RT_ARG_CAMERA_UP}))
+        return RT_INVALID_KERNEL_ARGS;
     rtk::KernelArgs cam;
     std::memset(&cam, 0, sizeof(cam));
-    fill_camera(k, &cam);
+    fill_camera(k->args, k->args.frame_count(), &cam);
     if (cam.width == 0 || cam.height == 0) return RT_INVALID_KERNEL_ARGS;
     if (global_work_size == 0 || global_work_size > 0xffffffffull) return RT_INVALID_GLOBAL_WORK_SIZE;
     if (features->size / rtp::kFeatureBytes < global_work_size) return RT_INVALID_BUFFER_SIZE;
     // 2. the scene, and the plans of the frame's query and fold over the scratch (RT_INVALID_OPERATION:
     // a leaf of more than 127 triangles, as for queries)
-    rc = prepare_scene(k);
+    rc = prepare_scene(k, k->args);
     if (rc) return rc;
     const size_t gws = global_work_size;
     const rtp::QueryIn qin =
@@ -1081,7 +842,7 @@ int rtEnqueueFrameFeatures(rt_context ctx, rt_kernel k, size_t global_work_size,
     rtk::QueryArgs q;
     fill_query_args(k, qp, k->feat.rays(), k->feat.hits(), &qa, &q);
     fill_surface_args(k, &sa);
-    sa.materials = static_cast<const rt_cl_material*>(k->bufs[RT_ARG_BUFFER_MATERIAL]->dptr);
+    sa.materials = static_cast<const rt_cl_material*>(k->args.materials()->dptr);
     sa.nMats = k->scene.n_mats();
     rtk::SurfaceArgs s{};
     s.rays = k->feat.rays();
@@ -1090,25 +851,18 @@ int rtEnqueueFrameFeatures(rt_context ctx, rt_kernel k, size_t global_work_size,
     s.first = sp.first, s.count = sp.count;
     s.inv = 1.0f / (float)n_frames;
     // 5. per frame, in frame order on the context's stream: the camera's rays, their closest hits, the fold
-    hipStream_t st = qs(ctx);
     k->last_lds = qp.variant.lds();
-    TimedLaunch timed{k, st, k->pending_events};
-    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
-    hipError_t e = hipSuccess;
-    for (unsigned f = 0; f < n_frames && e == hipSuccess; ++f) {
-        cam.frameCount = k->u32[RT_ARG_FRAME_COUNT] + f;  // (uint32 wrap, as the render's)
-        s.accFirst = f == 0, s.accLast = f + 1 == n_frames;
-        e = rtk::launch_camera_rays(cam, k->feat.rays(), (uint32_t)gws, k->math, st);
-        if (e == hipSuccess) e = rtk::launch_query(qa, q, qp.variant, qp.grid, qp.smem, st);
-        if (e == hipSuccess) e = rtk::launch_surfaces(sa, s, k->math, true, sp.grid, st);
-    }
-    if (e != hipSuccess) return map_hip(e);
-    timed.end();
-    mark_device_write(features, true);
-    rc = drain_if_many(k);
-    if (rc) return rc;
-    ++k->launches;
-    return pending_error(ctx, RT_SUCCESS);
+    return launch_on_queue(ctx, k, features, [&](hipStream_t st) {
+        hipError_t e = hipSuccess;
+        for (unsigned f = 0; f < n_frames && e == hipSuccess; ++f) {
+            cam.frameCount = k->args.frame_count() + f;  // (uint32 wrap, as the render's)
+            s.accFirst = f == 0, s.accLast = f + 1 == n_frames;
+            e = rtk::launch_camera_rays(cam, k->feat.rays(), (uint32_t)gws, k->math, st);
+            if (e == hipSuccess) e = rtk::launch_query(qa, q, qp.variant, qp.grid, qp.smem, st);
+            if (e == hipSuccess) e = rtk::launch_surfaces(sa, s, k->math, true, sp.grid, st);
+        }
+        return e;
+    });
 }
 
 // ---- feature-guided a-trous denoise (rt_denoise.hip; the plan: rt_denoise_plan.cpp) ---------------
@@ -1116,10 +870,7 @@ int rtEnqueueFrameFeatures(rt_context ctx, rt_kernel k, size_t global_work_size,
 int rtEnqueueDenoise(rt_context ctx, rt_kernel k, rt_mem image, rt_mem features, unsigned width, unsigned height,
                      const rt_denoise_params* params, rt_mem out) {
     // 1. the handles and the plan: nothing is allocated or launched on an error
-    int rc = ensure_device(ctx);
-    if (rc) return rc;
-    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
-    rc = flush_first(ctx);
+    int rc = queue_head(ctx, k, {});
     if (rc) return rc;
     rtp::DenoiseIn in{};
     in.params_ok = params != nullptr;
@@ -1152,24 +903,17 @@ int rtEnqueueDenoise(rt_context ctx, rt_kernel k, rt_mem image, rt_mem features,
     a.width = p.width, a.height = p.height;
     a.terms = p.terms;
     a.invN = p.inv_n, a.invZ = p.inv_z, a.invA = p.inv_a;
-    hipStream_t st = qs(ctx);
-    TimedLaunch timed{k, st, k->pending_events};
-    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
-    hipError_t e = hipSuccess;
-    for (unsigned i = 0; i < p.iterations && e == hipSuccess; ++i) {
-        const rtp::DenoiseStep& t = p.it[i];
-        a.src = bufs[t.src], a.dst = bufs[t.dst];
-        a.tilesX = t.tiles_x, a.tilesPerClass = t.tiles_per_class;
-        a.invC = t.inv_c;
-        e = rtd::launch_denoise(a, t, st);
-    }
-    if (e != hipSuccess) return map_hip(e);
-    timed.end();
-    mark_device_write(out, true);
-    rc = drain_if_many(k);
-    if (rc) return rc;
-    ++k->launches;
-    return pending_error(ctx, RT_SUCCESS);
+    return launch_on_queue(ctx, k, out, [&](hipStream_t st) {
+        hipError_t e = hipSuccess;
+        for (unsigned i = 0; i < p.iterations && e == hipSuccess; ++i) {
+            const rtp::DenoiseStep& t = p.it[i];
+            a.src = bufs[t.src], a.dst = bufs[t.dst];
+            a.tilesX = t.tiles_x, a.tilesPerClass = t.tiles_per_class;
+            a.invC = t.inv_c;
+            e = rtd::launch_denoise(a, t, st);
+        }
+        return e;
+    });
 }
 
 // ---- temporal reprojection (rt_temporal.hip; the plan: rt_temporal_plan.cpp) -----------------------
@@ -1178,10 +922,7 @@ int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem 
                                 rt_mem hist_features, unsigned width, unsigned height,
                                 const rt_temporal_params* params, rt_mem out) {
     // 1. the handles and the plan: nothing is launched on an error
-    int rc = ensure_device(ctx);
-    if (rc) return rc;
-    if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
-    rc = flush_first(ctx);
+    int rc = queue_head(ctx, k, {});
     if (rc) return rc;
     rtp::TemporalIn in{};
     in.params_ok = params != nullptr;
@@ -1222,17 +963,7 @@ int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem 
     a.cur_frames = p.cur_frames, a.history_frames = p.history_frames, a.max_history = p.max_history;
     a.depth_tolerance = p.depth_tolerance, a.normal_threshold = p.normal_threshold;
     a.k = p.k;
-    hipStream_t st = qs(ctx);
-    TimedLaunch timed{k, st, k->pending_events};
-    if (!timed.begin()) return RT_OUT_OF_RESOURCES;
-    const hipError_t e = rtt::launch_temporal(a, p, st);
-    if (e != hipSuccess) return map_hip(e);
-    timed.end();
-    mark_device_write(out, true);
-    rc = drain_if_many(k);
-    if (rc) return rc;
-    ++k->launches;
-    return pending_error(ctx, RT_SUCCESS);
+    return launch_on_queue(ctx, k, out, [&](hipStream_t st) { return rtt::launch_temporal(a, p, st); });
 }
 
 int rtBuildBVH(rt_context ctx, rt_mem tris, size_t n_tris, unsigned max_prims_in_node, rt_mem nodes,
@@ -1245,7 +976,7 @@ int rtBuildBVHEx(rt_context ctx, rt_mem tris, size_t n_tris, unsigned max_prims_
     if (method != RT_BVH_LBVH && method != RT_BVH_PLOC) return RT_INVALID_VALUE;
     int rc = ensure_device(ctx);
     if (rc) return rc;
-    if (ctx->pend_k) (void)rti::flush_frames(ctx);
+    (void)rti::flush_frames(ctx);
     if (!tris || !nodes || tris->ctx != ctx || nodes->ctx != ctx) return RT_INVALID_MEM_OBJECT;
     if (tris == nodes) return RT_INVALID_MEM_OBJECT;  // the build would overwrite its own input
     if (!n_nodes || n_tris == 0 || n_tris >= (1u << 30)) return RT_INVALID_VALUE;
@@ -1298,11 +1029,10 @@ int rtRefitBVH(rt_context ctx, rt_kernel k) {
     int rc = ensure_device(ctx);
     if (rc) return rc;
     if (!k || k->ctx != ctx) return RT_INVALID_KERNEL;
-    if (!k->set[RT_ARG_BUFFER_SCENE] || !k->set[RT_ARG_BUFFER_NODE]) return RT_INVALID_KERNEL_ARGS;
+    if (!k->args.has({RT_ARG_BUFFER_SCENE, RT_ARG_BUFFER_NODE})) return RT_INVALID_KERNEL_ARGS;
     rc = flush_first(ctx);  // coalesced frames launch first, on the scene as it was
     if (rc) return rc;
-    rc = k->scene.refit(ctx, k->bufs[RT_ARG_BUFFER_SCENE], k->bufs[RT_ARG_BUFFER_NODE],
-                        k->bufs[RT_ARG_BUFFER_MATERIAL]);
+    rc = k->scene.refit(ctx, k->args.tris(), k->args.nodes(), k->args.materials());
     return rc ? rc : pending_error(ctx, RT_SUCCESS);
 }
 
@@ -1337,7 +1067,7 @@ int rtEnqueueWriteBuffer(rt_context ctx, rt_mem m, int blocking, size_t offset, 
     if (!m || m->ctx != ctx) return RT_INVALID_MEM_OBJECT;
     if (!src || offset > m->size || size > m->size - offset) return RT_INVALID_VALUE;
     // coalesced frames launch first, reading (and packing) the scene as it was
-    if (ctx->pend_k) (void)rti::flush_frames(ctx);
+    (void)rti::flush_frames(ctx);
     if (m->shadow_valid) std::memcpy(m->shadow.data() + offset, src, size);
     ++m->generation;
     ++m->structural;
@@ -1409,7 +1139,7 @@ int rtEnqueueCopyBufferRectToPointer(rt_context ctx, rt_mem src, size_t src_offs
                                      size_t width_bytes, size_t rows, void* dst, size_t dst_pitch) {
     int rc = ensure_device(ctx);
     if (rc) return rc;
-    if (ctx->pend_k) (void)rti::flush_frames(ctx);
+    (void)rti::flush_frames(ctx);
     if (!src || src->ctx != ctx || !dst) return RT_INVALID_MEM_OBJECT;
     if (rows == 0 || width_bytes == 0) return RT_SUCCESS;
     if (width_bytes > src_pitch || width_bytes > dst_pitch) return RT_INVALID_VALUE;
@@ -1438,7 +1168,7 @@ int rtEnqueueCopyBufferRectToPointer(rt_context ctx, rt_mem src, size_t src_offs
 int rtContextSetReadbackOnAccumStream(rt_context ctx, int enable) {
     int rc = ensure_device(ctx);
     if (rc) return rc;
-    if (ctx->pend_k) (void)rti::flush_frames(ctx);
+    (void)rti::flush_frames(ctx);
     ctx->readback_on_astream = enable != 0;
     return RT_SUCCESS;
 }
@@ -1448,7 +1178,7 @@ int rtContextGetAccumStream(rt_context ctx, void** s) {
     if (!s) return RT_INVALID_VALUE;
     if (!ctx->overlap) ctx->mexposed = true;  // the main stream leaves the library's view
     ctx->dexposed = true;  // the caller may synchronise with the stream outside the library
-    if (ctx->pend_k) (void)rti::flush_frames(ctx);
+    (void)rti::flush_frames(ctx);
     *s = ctx->overlap ? ctx->astream : qs(ctx);
     return RT_SUCCESS;
 }
@@ -1457,7 +1187,7 @@ int rtEnqueueCopyPointerRectToBuffer(rt_context ctx, const void* src, size_t src
                                      size_t dst_offset, size_t dst_pitch, size_t width_bytes, size_t rows) {
     int rc = ensure_device(ctx);
     if (rc) return rc;
-    if (ctx->pend_k) (void)rti::flush_frames(ctx);
+    (void)rti::flush_frames(ctx);
     if (!dst || dst->ctx != ctx || !src) return RT_INVALID_MEM_OBJECT;
     if (rows == 0 || width_bytes == 0) return RT_SUCCESS;
     if (width_bytes > src_pitch || width_bytes > dst_pitch) return RT_INVALID_VALUE;
@@ -1506,11 +1236,11 @@ int rtKernelGetStats(rt_kernel k, rt_stats* out) {
     flush_kernel(k);
     int rc = ensure_device(k->ctx);
     if (rc) return rc;
-    unsigned long long h[kStatWords] = {};
-    hipError_t e = hipMemcpyAsync(h, k->dstats, sizeof(h), hipMemcpyDeviceToHost, qs(k->ctx));
+    unsigned long long h[rti::WorkCounters::kStatWords] = {};
+    hipError_t e = hipMemcpyAsync(h, k->counters.stats(), sizeof(h), hipMemcpyDeviceToHost, qs(k->ctx));
     if (e == hipSuccess) e = hipStreamSynchronize(qs(k->ctx));
     if (e != hipSuccess) return map_hip(e);
-    rc = drain_events(k);
+    rc = k->timer.drain();
     if (rc) return rc;
     out->rays = h[0];
     out->node_visits = h[1];
@@ -1522,9 +1252,9 @@ int rtKernelGetStats(rt_kernel k, rt_stats* out) {
     out->cycles_total = h[7];
     for (int i = 0; i < 12; ++i) out->sched[i] = h[8 + i];
     out->launches = k->launches;
-    out->kernel_ms = k->kernel_ms;
-    out->accum_ms = k->accum_ms;
-    out->render_period_ms = k->period_intervals ? k->period_span_ms / (double)k->period_intervals : 0.0;
+    out->kernel_ms = k->timer.kernel_ms();
+    out->accum_ms = k->timer.accum_ms();
+    out->render_period_ms = k->timer.render_period_ms();
     return RT_SUCCESS;
 }
 
@@ -1533,13 +1263,11 @@ int rtKernelResetStats(rt_kernel k) {
     flush_kernel(k);
     int rc = ensure_device(k->ctx);
     if (rc) return rc;
-    rc = drain_events(k);
+    rc = k->timer.drain();
     if (rc) return rc;
     k->launches = 0;
-    k->kernel_ms = 0.0;
-    k->accum_ms = 0.0;
-    reset_period(k);
-    hipError_t e = hipMemsetAsync(k->dstats, 0, kStatWords * sizeof(unsigned long long), qs(k->ctx));
+    k->timer.reset();
+    hipError_t e = k->counters.zero_stats(qs(k->ctx));
     if (e == hipSuccess) e = hipStreamSynchronize(qs(k->ctx));
     return map_hip(e);
 }
@@ -1559,7 +1287,7 @@ int rtKernelForceGlobalScene(rt_kernel k, int force) {
 
 int rtBufferGetDevicePointer(rt_mem m, void** dptr) {
     if (!m || !dptr) return RT_INVALID_VALUE;
-    if (m->ctx && m->ctx->pend_k) (void)rti::flush_frames(m->ctx);  // the caller may touch the bytes
+    (void)rti::flush_frames(m->ctx);  // the caller may touch the bytes
     // ... at any later time, after synchronising outside the library: no more frame coalescing
     if (m->ctx) m->ctx->dexposed = true;
     *dptr = m->dptr;

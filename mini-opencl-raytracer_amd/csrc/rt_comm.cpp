@@ -985,7 +985,7 @@ int rtCommEnqueueGatherBands(const rt_comm* comms, const rt_mem* outs, int n_loc
     }
     if (int rc = check_loopback(comms, n_local)) return rc;
     for (int i = 0; i < n_local; ++i)  // coalesced per-frame launches first: the gather reads their output
-        if (comms[i]->ctx->pend_k) (void)rti::flush_frames(comms[i]->ctx);
+        (void)rti::flush_frames(comms[i]->ctx);
     // the plans (rebuilt, by every rank alike, when the size, the root or the transport changes).
     // The root's destination is part of a copy-engine plan: linked by address (every rank in this
     // call) a new one rebuilds it; linked by IPC handles the root cannot tell the other processes,

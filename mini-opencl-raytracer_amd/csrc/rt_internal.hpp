@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/rt_hip.h"
+#include "rt_launch_args.hpp"
 
 // fused frames: radiance sets used in rotation, so a render waits only for the accumulation of the
 // launch RT_RAD_SETS steps back; consecutive renders alternate between RT_RENDER_STREAMS streams, so
@@ -69,16 +70,10 @@ struct rt_context_s {
     // next accumulation -- which rewrites the output -- waits for those copies (oread_ev)
     hipEvent_t oread_ev = nullptr;
     bool oread = false;
-    // per-frame launches queued back to back and not launched yet (rt_capi.cpp, frame
-    // coalescing): frames pend_f0 .. pend_f0 + pend_n - 1 of pend_k with the arguments they were
-    // enqueued with; launched as one fused launch before anything else touches the context
+    // per-frame launches queued back to back and not launched yet (rt_capi.cpp, frame coalescing;
+    // rt_launch_args.hpp): launched as one fused launch before anything else touches the context
     // (flush_frames; qs() flushes, so every enqueue, read, write and wait does)
-    rt_kernel pend_k = nullptr;
-    size_t pend_gws = 0;
-    uint32_t pend_f0 = 0, pend_n = 0;
-    uint32_t pend_u32[RT_ARG_COUNT] = {};
-    float pend_f3[3][4] = {};
-    rt_mem pend_bufs[4] = {};
+    rti::HeldFrames held;
     int pend_error = RT_SUCCESS;  // a failed coalesced launch, reported by the next call that can
 };
 
@@ -166,8 +161,8 @@ inline void mark_device_write(rt_mem m, bool structural) {
     if (structural) ++m->structural;
 }
 
-// Launch the coalesced per-frame launches of `ctx`, if any (rt_capi.cpp).  Returns their error,
-// which is also kept in ctx->pend_error for the next call that reports one.
+// Launch the coalesced per-frame launches of `ctx` (rt_capi.cpp); returns at once when none are held.
+// Returns their error, which is also kept in ctx->pend_error for the next call that reports one.
 int flush_frames(rt_context ctx);
 
 // `s` waits for the root's pending gather arrivals (rt_comm.cpp; records gtail behind them)
@@ -196,7 +191,7 @@ inline hipError_t gather_wait(rt_context ctx, hipStream_t s) {
 // coalesced per-frame launches.  A failed wait is reported by the next call that returns a status
 // (ctx->pend_error).
 inline hipStream_t qs(rt_context ctx) {
-    if (ctx->pend_k) (void)flush_frames(ctx);
+    (void)flush_frames(ctx);
     if (ctx->apending) {
         (void)hipStreamWaitEvent(ctx->stream, ctx->atail, 0);
         ctx->apending = false;
