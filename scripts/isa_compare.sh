@@ -1,7 +1,8 @@
 #!/bin/bash
-# Compare the gfx950 ISA of every kernel between a saved snapshot and the current build (the
-# instruction text per function: addresses, encodings and branch-target labels stripped).  A code
-# change meant to leave the kernels' instruction streams alone must print "identical" for them.
+# Compare the gfx950 ISA of every kernel (the render objects' and rt_comm.o's) between a saved snapshot
+# and the current build (the instruction text per function: addresses, encodings and branch-target
+# labels stripped).  A code change meant to leave the kernels' instruction streams alone must print
+# "identical" for them.
 # (s_add_u32 / s_addc_u32 literals are PC-relative offsets after s_getpc_b64 -- they move with the
 # size of other kernels in the code object -- and are masked.)
 # (Zero padding between a function's end and the next function's alignment decodes as
@@ -13,7 +14,7 @@ B=${ISA_BUILD:-mini-opencl-raytracer_amd/build}  # (ISA_BUILD: a variant's objec
 LLVM=/opt/rocm/lib/llvm/bin
 dump() {  # dump OUTDIR
   mkdir -p $1
-  for o in rt_kernels_shipped rt_kernels; do
+  for o in rt_kernels_shipped rt_kernels rt_comm; do
     cp $B/$o.o $1/
     (cd $1 && $LLVM/llvm-objdump --offloading $o.o > /dev/null && mv $o.o.0.hipv4-amdgcn-amd-amdhsa--gfx950 $o.co && rm -f $o.o.0.host* $o.o)
     $LLVM/llvm-objdump -d --no-show-raw-insn $1/$o.co \
@@ -30,7 +31,7 @@ case $1 in
   compare)
     rm -rf /tmp/isa_now
     dump /tmp/isa_now
-    for o in rt_kernels_shipped rt_kernels; do
+    for o in rt_kernels_shipped rt_kernels rt_comm; do
       for f in $(cut -f1 $2/$o.isa | sort -u); do
         a=$(body "$f" $2/$o.isa | md5sum | cut -c1-12)
         b=$(body "$f" /tmp/isa_now/$o.isa | md5sum | cut -c1-12)

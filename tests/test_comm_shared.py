@@ -65,3 +65,33 @@ def test_shared_world_refuses_rccl_and_bad_arguments(tmp_path):
         mg.Comm.init_shared(ctx, 1, 0, str(tmp_path))
     assert e.value.code == -30
     ctx.release()
+
+
+def test_failed_link_leaves_no_plan(cornell, tmp_path):
+    """A plan is committed only when it is built and linked.  A shared world of one rank whose link
+    step is refused (the test hook: a status code, nothing faults) has no RCCL to fall back to, so
+    the gather fails -- and leaves no plan: no active transport, no pin on the destination.  The next
+    gather plans and links afresh and moves the rendered bytes."""
+    from clrt import multigpu as mg
+    W, H = 64, 40
+    r = HipRenderer(cornell, W, H, math=N.MATH_SHIPPED)
+    comm = mg.Comm.init_shared(r.ctx, 1, 0, str(tmp_path))
+    comm.set_transport(N.COMM_TRANSPORT_COPY_ENGINES_IPC)
+    comm.shard(r.k)
+    dst = r.ctx.create_buffer(N.MEM_READ_WRITE, W * H * 16)
+    r.frame(1, n_frames=2)
+    comm.set_option(N.COMM_OPT_FAIL_LINKS, 1)
+    with pytest.raises(N.RTError) as e:
+        mg.Comm.gather_bands([comm], [r.out], W, H, root=0, dst=dst)
+    assert e.value.code == -59  # RT_INVALID_OPERATION
+    assert comm.transport() == (N.COMM_TRANSPORT_COPY_ENGINES_IPC, -1)
+    comm.set_option(N.COMM_OPT_FAIL_LINKS, 0)
+    mg.Comm.gather_bands([comm], [r.out], W, H, root=0, dst=dst)
+    assert comm.transport() == (N.COMM_TRANSPORT_COPY_ENGINES_IPC, N.COMM_TRANSPORT_COPY_ENGINES_IPC)
+    got = np.zeros((W * H, 4), np.float32)
+    r.ctx.ReadBuffer(dst, got, blocking=True)
+    assert got.tobytes() == r.result().tobytes()
+    comm.destroy()
+    assert N.hip_lib().rtReleaseBuffer(dst.handle) == 0  # (no pin is left: freed here)
+    dst.handle = None
+    r.close()
