@@ -278,6 +278,62 @@ int rtEnqueueIntersectRays(rt_context ctx, rt_kernel k, rt_mem rays, size_t firs
                            rt_mem hits);
 int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem rays);
 
+/* ---- path tracing over caller rays -----------------------------------------------------------
+ * rtEnqueueTracePaths runs the reference's Render (kernel_bvh.cl:349-384) for records [first,
+ * first + n) of `rays` (rt_ray) and writes the same slots of `out` (rt_path_result); the other slots
+ * are not touched.  The scene, the material buffer, LIGHT_BOUNCES, LIGHT_TYPE and SKYBOX_INTENSITY
+ * are those bound to `k`; the scene is prepared exactly as a render launch prepares it (rtValidateBVH
+ * and the material check included).  The call runs in k's math mode and honours
+ * rtKernelForceGlobalScene.  WIDTH, HEIGHT, FRAME_COUNT, the camera slots and BUFFER_OUT are not read
+ * and need not be set.
+ * Per record i (the absolute index): seed = seeds ? seeds[i] : params->seed_base + (uint32_t)i, with
+ * uint32 wrap (seed_base is ignored when `seeds` is given); ray = InitRay(origin, dir), `dir`
+ * normalised as the query normalises it; then Render(&ray, &scene, &seed): every Intersect in the
+ * reference's node and triangle order, shading and RNG draws those of the render kernels.  One
+ * generalisation, for the first segment only and the query's: isect.t starts at the record's tmax and
+ * a triangle is accepted only if t >= tmin; later segments are the reference's Intersect.  With tmin =
+ * -INFINITY and tmax = 100000.0f the whole path is the reference's bit for bit.  A first segment that
+ * misses inside its window adds the sky term and ends the path, as a miss does.
+ *   radiance  RT_TRACE_LINEAR: max(radiance, 0) per channel, as Render returns it.  RT_TRACE_FRAME0:
+ *             that value as KernelEntry stores it at frameCount == 0, pow(., 0.45454545f) in k's
+ *             math mode.
+ *   prim      the first segment's hit primitive (as rtKernelSetHitBuffers' id), -1 on a miss and
+ *             when LIGHT_BOUNCES is 0 (radiance 0 then).
+ * Non-finite origins or directions may produce any radiance; every walk still ends, and no value
+ * from `rays` or `seeds` ever becomes an address.
+ * Ordering is a query's: asynchronous on the context's in-order queue, coalesced per-frame launches
+ * first, after the pending accumulations, "another call touching the context" for the deferral
+ * rules; `out` counts as written.  With rtKernelSetStats on it adds rays (one per Intersect), node
+ * visits, triangle tests and hits; with timing on, kernel_ms and launches.  After
+ * rtEnqueueUpdateVertices + rtRefitBVH it sees the moved geometry without a full preparation.
+ * Errors (nothing is launched), in this order after the context and the kernel: `params` NULL or an
+ * encoding other than the two RT_INVALID_VALUE; first + n > 2^31 RT_INVALID_VALUE; `rays` or `out`
+ * NULL or of another context, a non-NULL `seeds` of another context, or `out` the same buffer as
+ * `rays` or `seeds` RT_INVALID_MEM_OBJECT; the range beyond any buffer (32, 4 and 16 B per record)
+ * RT_INVALID_BUFFER_SIZE; scene, node or material slot unbound, or LIGHT_BOUNCES, LIGHT_TYPE or
+ * SKYBOX_INTENSITY unset RT_INVALID_KERNEL_ARGS; a BVH leaf of more than 127 triangles
+ * RT_INVALID_OPERATION; n == 0 RT_SUCCESS with no launch.
+ *
+ * rtEnqueueCameraPaths writes `rays` byte for byte as rtEnqueueCameraRays does (same errors) and
+ * seeds[gid], the RNG state after CreateRay's two draws: the reference's HashUInt32 applied twice to
+ * gid + frame_hash(FRAME_COUNT).  Feeding both buffers to rtEnqueueTracePaths continues exactly the
+ * path KernelEntry traces for that work-item.  Extra errors: `seeds` NULL, of another context or the
+ * same buffer as `rays` RT_INVALID_MEM_OBJECT; `seeds` smaller than 4 B per work-item
+ * RT_INVALID_BUFFER_SIZE. */
+typedef struct rt_path_result {
+    float radiance[3];
+    int32_t prim;
+} rt_path_result; /* 16 B */
+#define RT_TRACE_LINEAR 0 /* max(radiance, 0) as Render returns it */
+#define RT_TRACE_FRAME0 1 /* the value KernelEntry stores at frameCount == 0 */
+typedef struct rt_trace_params {
+    uint32_t seed_base;
+    int encoding;
+} rt_trace_params;
+int rtEnqueueTracePaths(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem seeds /* may be NULL */, size_t first,
+                        size_t n, const rt_trace_params* params, rt_mem out);
+int rtEnqueueCameraPaths(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem rays, rt_mem seeds);
+
 /* ---- surface records of ray hits, and first-hit feature buffers ----------------------------
  * rtEnqueueHitSurfaces writes, for records [first, first + n) of `rays` (rt_ray) and `hits`
  * (rt_ray_hit), the same slots of `surfaces` (rt_surface); the other slots are not touched.  The
@@ -616,7 +672,11 @@ int rtValidateBVH(const void* nodes, size_t n_nodes, size_t n_tris, int* depth);
  *                                     synchronise outside the library, so from then on every
  *                                     rtEnqueueKernel launches at once.
  *   QUERY_REFILL_MIN                  ray queries (rtEnqueueIntersectRays): take rays from the ring
- *                                     once this many lanes are free (1-64, default 32) */
+ *                                     once this many lanes are free (1-64, default 32)
+ *   TRACE_REFILL_MIN, TRACE_SHADE_MIN path tracing over caller rays (rtEnqueueTracePaths): take records
+ *                                     from the ring once this many lanes are free (1-64, default
+ *                                     8), and shade once this many walks have ended
+ *                                     (1-64, default 48, the step schedule's) */
 enum rt_tuning {
     RT_TUNE_REFILL_MIN = 0,
     RT_TUNE_SHADE_MIN = 1,
@@ -642,7 +702,10 @@ enum rt_tuning {
     RT_TUNE_PERFRAME_BATCH = 23,
     RT_TUNE_STEP_WEIGHT_NODE_GLOBAL = 24,
     RT_TUNE_STEP_WEIGHT_LEAF_GLOBAL = 25,
-    RT_TUNE_QUERY_REFILL_MIN = 26
+    RT_TUNE_QUERY_REFILL_MIN = 26,
+    /* 27: never assigned (RT_INVALID_VALUE) */
+    RT_TUNE_TRACE_REFILL_MIN = 28,
+    RT_TUNE_TRACE_SHADE_MIN = 29
 };
 int rtKernelSetTuning(rt_kernel k, int param, int value);
 int rtKernelGetTuning(rt_kernel k, int param, int* value);

@@ -67,6 +67,10 @@ RAY_DTYPE = np.dtype([("origin", np.float32, (3,)), ("tmin", np.float32), ("dir"
 RAY_HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32)])
 assert RAY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 16
 QUERY_CLOSEST, QUERY_ANY = 0, 1
+# rt_path_result / rt_trace_params (rt_hip.h): the records and parameters of rtEnqueueTracePaths
+PATH_RESULT_DTYPE = np.dtype([("radiance", np.float32, (3,)), ("prim", np.int32)])
+assert PATH_RESULT_DTYPE.itemsize == 16
+TRACE_LINEAR, TRACE_FRAME0 = 0, 1
 # rt_surface / rt_pixel_features (rt_hip.h): the records of rtEnqueueHitSurfaces and rtEnqueueFrameFeatures
 SURFACE_DTYPE = np.dtype([("position", np.float32, (3,)), ("t", np.float32),
                           ("normal", np.float32, (3,)), ("prim", np.int32),
@@ -97,6 +101,8 @@ TUNING = {"refill_min": 0, "shade_min": 1, "refill_min_global": 2, "shade_min_gl
           "wf_top_nodes": 17, "global_oct": 18, "perframe_defer": 19, "max_blocks": 20,
           "perframe_defer_min": 21, "perframe_batch": 23, "step_weight_node_global": 24,
           "step_weight_leaf_global": 25, "query_refill_min": 26}
+# ... of rtEnqueueTracePaths (27 was never assigned)
+TRACE_TUNING = {"trace_refill_min": 28, "trace_shade_min": 29}
 
 
 class Stats(ctypes.Structure):
@@ -107,6 +113,12 @@ class Stats(ctypes.Structure):
                 ("cycles_shade", ctypes.c_uint64), ("cycles_total", ctypes.c_uint64),
                 ("sched", ctypes.c_uint64 * 12), ("accum_ms", ctypes.c_double),
                 ("render_period_ms", ctypes.c_double)]
+
+
+class TRACE_PARAMS(ctypes.Structure):
+    """rt_trace_params (rt_hip.h): rtEnqueueTracePaths' seed base (used without a seed buffer) and the
+    encoding of the radiance it writes."""
+    _fields_ = [("seed_base", ctypes.c_uint32), ("encoding", ctypes.c_int)]
 
 
 class DENOISE_PARAMS(ctypes.Structure):
@@ -175,6 +187,9 @@ _HIP_PROTOS = {
     "rtEnqueueKernelFrames": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint]),
     "rtEnqueueIntersectRays": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, _vp]),
     "rtEnqueueCameraRays": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp]),
+    "rtEnqueueTracePaths": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t,
+                                           ctypes.POINTER(TRACE_PARAMS), _vp]),
+    "rtEnqueueCameraPaths": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp]),
     "rtEnqueueHitSurfaces": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtEnqueueFrameFeatures": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint, _vp]),
     "rtEnqueueDenoise": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,

@@ -15,6 +15,10 @@ from . import _native as N
 from ._native import RTError, check, hip_lib
 
 
+def _tuning_id(name: str) -> int:
+    return N.TUNING[name] if name in N.TUNING else N.TRACE_TUNING[name]
+
+
 class CLContext:
     """CLContext(platform) (CLutils.cpp:9-35): GPU `device` + one in-order HIP stream."""
 
@@ -91,6 +95,22 @@ class CLContext:
         records (work range and row interleave ignored)."""
         check(self._lib.rtEnqueueCameraRays(self.handle, kernel.handle, int(work_size), rays.handle),
               "Failed to enqueue camera rays")
+
+    def TracePaths(self, kernel: "CLKernel", rays: "Buffer", out: "Buffer", n: int, seeds: "Buffer | None" = None,
+                   seed_base: int = 0, encoding: int = N.TRACE_LINEAR, first: int = 0) -> None:
+        """rtEnqueueTracePaths: the reference's Render for records [first, first + n) of `rays` (N.RAY_DTYPE)
+        against the scene, materials and light slots bound to `kernel`, into the same slots of `out`
+        (N.PATH_RESULT_DTYPE).  Record i starts with seeds[i], or seed_base + i without `seeds`."""
+        params = N.TRACE_PARAMS(int(seed_base) & 0xffffffff, int(encoding))
+        check(self._lib.rtEnqueueTracePaths(self.handle, kernel.handle, rays.handle, seeds.handle if seeds else None,
+                                            int(first), int(n), ctypes.byref(params), out.handle),
+              "Failed to enqueue path trace")
+
+    def CameraPaths(self, kernel: "CLKernel", work_size: int, rays: "Buffer", seeds: "Buffer") -> None:
+        """rtEnqueueCameraPaths: CameraRays' records plus, per work-item, the RNG state after CreateRay's
+        two draws (uint32), so that TracePaths over both continues KernelEntry's path."""
+        check(self._lib.rtEnqueueCameraPaths(self.handle, kernel.handle, int(work_size), rays.handle, seeds.handle),
+              "Failed to enqueue camera paths")
 
     def HitSurfaces(self, kernel: "CLKernel", rays: "Buffer", hits: "Buffer", surfaces: "Buffer", n: int,
                     first: int = 0) -> None:
@@ -254,12 +274,13 @@ class CLKernel:
         check(self._lib.rtKernelSetSchedule(self.handle, int(sched)), "schedule")
 
     def set_tuning(self, name: str, value: int) -> None:
-        """rtKernelSetTuning: a scheduling parameter by name (N.TUNING); results are unchanged."""
-        check(self._lib.rtKernelSetTuning(self.handle, N.TUNING[name], int(value)), f"tuning {name}")
+        """rtKernelSetTuning: a scheduling parameter by name (N.TUNING, N.TRACE_TUNING); results are
+        unchanged."""
+        check(self._lib.rtKernelSetTuning(self.handle, _tuning_id(name), int(value)), f"tuning {name}")
 
     def get_tuning(self, name: str) -> int:
         v = ctypes.c_int()
-        check(self._lib.rtKernelGetTuning(self.handle, N.TUNING[name], ctypes.byref(v)), f"tuning {name}")
+        check(self._lib.rtKernelGetTuning(self.handle, _tuning_id(name), ctypes.byref(v)), f"tuning {name}")
         return int(v.value)
 
     def set_row_interleave(self, period: int, phase: int) -> None:

@@ -47,6 +47,7 @@ class Raytracer:
         self._scene_bufs: list = []
         self._cast_bufs: tuple | None = None  # (capacity in rays, ray buffer, hit buffer) of cast()
         self._surf_buf: tuple | None = None   # (capacity in records, surface buffer) of surfaces()
+        self._trace_bufs: tuple | None = None  # (capacity in records, ray, seed and result buffers) of trace()
         self._feat_buf: Buffer | None = None  # features(): width * height records
         self._denoise_buf: Buffer | None = None  # denoise(): the filtered image, width * height slots
         self._temporal_feat: list = [None, None]  # temporal(): this call's and the previous call's features
@@ -163,6 +164,67 @@ class Raytracer:
         self.ctx.ReadBuffer(hb, hits)
         self.ctx.ReadBuffer(sb, surf, blocking=True)
         return hits, surf
+
+    def _trace_buffers(self, n: int) -> tuple:
+        """The kept (ray, seed, result) buffers of trace() and camera_paths(), at least n records each."""
+        if self._trace_bufs is None or self._trace_bufs[0] < n:
+            if self._trace_bufs:
+                for b in self._trace_bufs[1:]:
+                    b.release()
+            self._trace_bufs = (n, self.ctx.create_buffer(N.MEM_READ_WRITE, n * N.RAY_DTYPE.itemsize),
+                                self.ctx.create_buffer(N.MEM_READ_WRITE, n * 4),
+                                self.ctx.create_buffer(N.MEM_READ_WRITE, n * N.PATH_RESULT_DTYPE.itemsize))
+        return self._trace_bufs[1:]
+
+    def trace(self, origins, dirs, seeds=None, seed_base: int = 0, tmin=-np.inf, tmax=100000.0,
+              encoding: str = "linear") -> tuple:
+        """Path-trace caller rays with the renderer's own path tracer (rtEnqueueTracePaths): `origins` and
+        `dirs` are (n, 3) arrays (directions need not be unit length), `tmin` / `tmax` scalars or (n,)
+        arrays bounding the first segment only.  Ray i starts the reference's Render with the RNG state
+        seeds[i] (uint32), or seed_base + i without `seeds`, under the current light_bounces, light_type
+        and skybox_intensity.  Returns (radiance float32[n, 3], prim int32[n]): with encoding "linear"
+        max(radiance, 0) -- sum these to average samples -- and with "frame0" the value a frame-0 render
+        stores; prim is the first segment's hit primitive, -1 on a miss."""
+        if encoding not in ("linear", "frame0"):
+            raise ValueError("encoding is 'linear' or 'frame0'")
+        origins = np.asarray(origins, np.float32).reshape(-1, 3)
+        dirs = np.asarray(dirs, np.float32).reshape(-1, 3)
+        n = len(origins)
+        if len(dirs) != n:
+            raise ValueError("origins and dirs differ in length")
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+            if len(seeds) != n:
+                raise ValueError("origins and seeds differ in length")
+        res = np.empty(n, N.PATH_RESULT_DTYPE)
+        if n == 0:
+            return res["radiance"].copy(), res["prim"].copy()
+        rays = np.empty(n, N.RAY_DTYPE)
+        rays["origin"], rays["dir"] = origins, dirs
+        rays["tmin"], rays["tmax"] = tmin, tmax
+        self.set_uniforms()
+        rb, sb, ob = self._trace_buffers(n)
+        self.ctx.WriteBuffer(rb, rays)
+        if seeds is not None:
+            self.ctx.WriteBuffer(sb, seeds)
+        self.ctx.TracePaths(self.kernel, rb, ob, n, seeds=sb if seeds is not None else None, seed_base=seed_base,
+                            encoding=N.TRACE_FRAME0 if encoding == "frame0" else N.TRACE_LINEAR)
+        self.ctx.ReadBuffer(ob, res, blocking=True)
+        return res["radiance"].copy(), res["prim"].copy()
+
+    def camera_paths(self) -> tuple:
+        """The camera's primary rays of frame frame_count with their RNG states (rtEnqueueCameraPaths):
+        (rays, seeds), width * height N.RAY_DTYPE records and uint32 seeds.  trace(rays["origin"],
+        rays["dir"], seeds) continues exactly the paths RenderFrame traces for that frame."""
+        self.set_uniforms()
+        work = self.width * self.height
+        rb, sb, _ = self._trace_buffers(work)
+        self.ctx.CameraPaths(self.kernel, work, rb, sb)
+        rays = np.empty(work, N.RAY_DTYPE)
+        seeds = np.empty(work, np.uint32)
+        self.ctx.ReadBuffer(rb, rays)
+        self.ctx.ReadBuffer(sb, seeds, blocking=True)
+        return rays, seeds
 
     def features(self, n_frames: int = 1) -> np.ndarray:
         """First-hit feature buffers for a denoiser (rtEnqueueFrameFeatures): an (H, W) array of
@@ -348,6 +410,10 @@ class Raytracer:
         if self._surf_buf:
             self._surf_buf[1].release()
             self._surf_buf = None
+        if self._trace_bufs:
+            for b in self._trace_bufs[1:]:
+                b.release()
+            self._trace_bufs = None
         if self._feat_buf:
             self._feat_buf.release()
             self._feat_buf = None

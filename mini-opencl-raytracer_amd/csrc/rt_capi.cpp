@@ -45,6 +45,7 @@
 #include "rt_scene_pack.hpp"
 #include "rt_temporal.hpp"
 #include "rt_temporal_plan.hpp"
+#include "rt_trace_plan.hpp"
 #include "rt_tuning.hpp"
 
 namespace {
@@ -755,6 +756,101 @@ int rtEnqueueCameraRays(rt_context ctx, rt_kernel k, size_t global_work_size, rt
         rtk::launch_camera_rays(a, static_cast<float4*>(rays->dptr), (uint32_t)global_work_size, k->math, qs(ctx));
     if (e != hipSuccess) return map_hip(e);
     mark_device_write(rays, true);
+    return pending_error(ctx, RT_SUCCESS);
+}
+
+// ---- path tracing over caller rays (rt_trace.hpp; the plan: rt_trace_plan.cpp) -------------------
+
+// a planned trace's arguments: the packed scene of k with its shading and material records, the three
+// light slots, the range and the arrays
+static void fill_trace_args(rt_kernel k, const rtp::TracePlan& p, rtk::KernelArgs* args) {
+    rtk::KernelArgs& a = *args;
+    std::memset(&a, 0, sizeof(a));
+    const rti::DeviceScene& sc = k->scene;
+    a.packedTris = sc.packed_tris();
+    a.octNodes = p.regrouped ? sc.goct() : sc.oct_nodes();
+    a.shadeTris = sc.shade_tris();
+    a.shadeMats = sc.shade_mats() + (k->math == RT_MATH_SHIPPED ? 4 * (size_t)sc.n_mats() : 0);
+    a.nTris = sc.n_tris(), a.nMats = sc.n_mats();
+    a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords;
+    a.lightBounces = k->args.light_bounces(), a.lightType = k->args.light_type();
+    a.skyboxIntensity = k->args.skybox_intensity();
+    a.stepWeightNode = p.stepWeightNode, a.stepWeightLeaf = p.stepWeightLeaf;
+    a.stats = k->counters.stats();
+}
+
+int rtEnqueueTracePaths(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem seeds, size_t first, size_t n,
+                        const rt_trace_params* params, rt_mem out) {
+    // 1. the handles, then the coalesced frames: another call touches the context
+    int rc = queue_head(ctx, k, {});
+    if (rc) return rc;
+    // 2. the arguments, in the plan's order: no scene is packed and nothing launched on an error
+    rtp::TraceIn in{};
+    in.params_given = params != nullptr;
+    in.encoding = params ? params->encoding : 0;
+    in.first = first, in.n = n;
+    in.rays_ok = rays && rays->ctx == ctx, in.out_ok = out && out->ctx == ctx;
+    in.seeds_given = seeds != nullptr, in.seeds_ok = seeds && seeds->ctx == ctx;
+    in.out_is_input = out && (out == rays || out == seeds);
+    in.rays_bytes = in.rays_ok ? rays->size : 0, in.out_bytes = in.out_ok ? out->size : 0;
+    in.seeds_bytes = in.seeds_ok ? seeds->size : 0;
+    in.scene_bound = k->args.has({RT_ARG_BUFFER_SCENE, RT_ARG_BUFFER_NODE, RT_ARG_BUFFER_MATERIAL});
+    in.lights_set = k->args.has({RT_ARG_LIGHT_BOUNCES, RT_ARG_LIGHT_TYPE, RT_ARG_SKYBOX_INTENSITY});
+    in.oct_ok = true;
+    rc = rtp::trace_check(in);
+    if (rc) return pending_error(ctx, rc);
+    // 3. the scene, packed and validated as a render launch does
+    rc = prepare_scene(k, k->args);
+    if (rc) return rc;
+    // 4. the plan, with the kernel's occupancy at the LDS size it chose
+    in.math = k->math, in.stats = k->stats;
+    const rti::DeviceScene& sc = k->scene;
+    in.n_nodes = sc.n_nodes(), in.n_tris = sc.n_tris(), in.n_mats = sc.n_mats();
+    in.oct_ok = sc.oct_ok();
+    in.goct_available = sc.goct() != nullptr, in.goct_b = sc.goct_b();
+    in.force_global = k->force_global;
+    in.tune = k->tune;
+    in.num_cus = ctx->num_cus;
+    rtp::TracePlan p;
+    rc = rtp::trace_shape(in, &p);
+    if (rc || p.nothing) return pending_error(ctx, rc);
+    rtp::trace_grid(in, k->occ.get(rtk::Family::Trace, p.variant, p.smem), &p);
+    // 5. the arguments
+    rtk::KernelArgs a;
+    fill_trace_args(k, p, &a);
+    rtk::TraceArgs q{};
+    q.rays = static_cast<const float4*>(rays->dptr);
+    q.seeds = seeds ? static_cast<const uint32_t*>(seeds->dptr) : nullptr;
+    q.out = static_cast<float4*>(out->dptr);
+    q.first = p.first, q.count = p.count, q.nUnits = p.nUnits;
+    q.refillMin = p.refillMin, q.shadeMin = p.shadeMin;
+    q.seedBase = params->seed_base, q.encoding = params->encoding;
+    // 6. the launch, on the context's stream after the pending accumulations and gathers
+    k->last_lds = p.variant.lds();
+    return launch_on_queue(ctx, k, out,
+                           [&](hipStream_t st) { return rtk::launch_trace(a, q, p.variant, p.grid, p.smem, st); });
+}
+
+int rtEnqueueCameraPaths(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem rays, rt_mem seeds) {
+    // (rtEnqueueCameraRays' checks in its order, the seeds' where the rays' are)
+    const int rc = queue_head(ctx, k, {rays, seeds});
+    if (rc) return rc;
+    if (rays == seeds) return RT_INVALID_MEM_OBJECT;
+    if (!k->args.has({RT_ARG_WIDTH, RT_ARG_HEIGHT, RT_ARG_FRAME_COUNT, RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT,
+                      RT_ARG_CAMERA_UP}))
+        return RT_INVALID_KERNEL_ARGS;
+    if (global_work_size == 0 || global_work_size > 0xffffffffull) return RT_INVALID_GLOBAL_WORK_SIZE;
+    rtk::KernelArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_camera(k->args, k->args.frame_count(), &a);
+    if (a.width == 0 || a.height == 0) return RT_INVALID_KERNEL_ARGS;
+    if (rays->size / sizeof(rt_ray) < global_work_size || seeds->size / 4 < global_work_size)
+        return RT_INVALID_BUFFER_SIZE;
+    const hipError_t e = rtk::launch_camera_paths(a, static_cast<float4*>(rays->dptr), static_cast<uint32_t*>(seeds->dptr),
+                                                  (uint32_t)global_work_size, k->math, qs(ctx));
+    if (e != hipSuccess) return map_hip(e);
+    mark_device_write(rays, true);
+    mark_device_write(seeds, true);
     return pending_error(ctx, RT_SUCCESS);
 }
 

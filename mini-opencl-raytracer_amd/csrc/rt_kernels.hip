@@ -113,11 +113,13 @@ static const Policy& policy(int math) {
     static const Policy devicelib = {pick_entry<MathDeviceLib>,   wf_pick<MathDeviceLib>,  query_pick<MathDeviceLib>,
                                      accum_frames<MathDeviceLib>, accum_key<MathDeviceLib>, camera_rays<MathDeviceLib>,
                                      pack_mats,
-                                     hit_surfaces<MathDeviceLib, false>, hit_surfaces<MathDeviceLib, true>};
+                                     hit_surfaces<MathDeviceLib, false>, hit_surfaces<MathDeviceLib, true>,
+                                     trace_pick<MathDeviceLib>, camera_paths<MathDeviceLib>};
     static const Policy pinned = {pick_entry<MathPinned>,   wf_pick<MathPinned>,  query_pick<MathPinned>,
                                   accum_frames<MathPinned>, accum_key<MathPinned>, camera_rays<MathPinned>,
                                   pack_mats,
-                                  hit_surfaces<MathPinned, false>, hit_surfaces<MathPinned, true>};
+                                  hit_surfaces<MathPinned, false>, hit_surfaces<MathPinned, true>,
+                                     trace_pick<MathPinned>, camera_paths<MathPinned>};
     return math == MathShipped::kId ? shipped_policy() : math == MathDeviceLib::kId ? devicelib : pinned;
 }
 
@@ -163,6 +165,20 @@ hipError_t launch_camera_rays(const KernelArgs& a, float4* rays, uint32_t n, int
     return hipGetLastError();
 }
 
+// ---- path tracing over caller rays (rt_trace.hpp) -------------------------------------------------
+hipError_t launch_trace(const KernelArgs& a, const TraceArgs& q, const Variant& v, unsigned grid, size_t smem,
+                        hipStream_t st) {
+    hipLaunchKernelGGL(policy(v.math).trace(v), dim3(grid), dim3(kTraceThreads), smem, st, a, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_camera_paths(const KernelArgs& a, float4* rays, uint32_t* seeds, uint32_t n, int math,
+                               hipStream_t st) {
+    const dim3 grid((unsigned)(((uint64_t)n + 255u) / 256u));
+    hipLaunchKernelGGL(policy(math).camera_paths, grid, dim3(256), 0, st, a, rays, seeds, n);
+    return hipGetLastError();
+}
+
 // ---- surface records (rt_surface.hpp) ------------------------------------------------------------
 hipError_t launch_surfaces(const KernelArgs& a, const SurfaceArgs& s, int math, bool accumulate, unsigned grid,
                            hipStream_t st) {
@@ -183,6 +199,7 @@ int OccupancyCache::get(Family f, const Variant& v, size_t smem) {
         case Family::WfExtend: fn = reinterpret_cast<const void*>(p.wavefront(v).extend), threads = kWfExtendThreads; break;
         case Family::WfShade: fn = reinterpret_cast<const void*>(p.wavefront(v).shade), threads = kWfShadeThreads; break;
         case Family::Query: fn = reinterpret_cast<const void*>(p.query(v)), threads = kQueryThreads; break;
+        case Family::Trace: fn = reinterpret_cast<const void*>(p.trace(v)), threads = kTraceThreads; break;
     }
     int blocks = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, threads, smem) != hipSuccess) blocks = 1;

@@ -113,6 +113,28 @@ hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, const Variant& 
 // rtEnqueueCameraRays: width, height, frameCount and the camera slots of `a`; one rt_ray per work-item
 hipError_t launch_camera_rays(const KernelArgs& a, float4* rays, uint32_t n, int math, hipStream_t st);
 
+// ---- path tracing over caller rays (rt_trace.hpp) -------------------------------------------------
+// rtEnqueueTracePaths: KernelArgs carries the packed scene with its shading and material records
+// (packedTris, octNodes, shadeTris, shadeMats, nNodes, nTris, nMats, octStride, octB, octRecords),
+// lightBounces, lightType, skyboxIntensity, the step weights and the stats pointer; the rest is unused.
+struct TraceArgs {
+    const float4* rays;       // rt_ray records as 2 x float4: {origin, tmin}, {dir, tmax}
+    const uint32_t* seeds;    // the RNG state each record's Render starts with; null: seedBase + index
+    float4* out;              // rt_path_result records: {radiance.xyz, first prim bits}
+    uint32_t first, count;    // the range [first, first + count) of the arrays
+    uint32_t nUnits;          // 64-record units of the range (the last one may be partial)
+    uint32_t refillMin;       // take new records once this many lanes are free
+    uint32_t shadeMin;        // shade once this many lanes' walks have ended
+    uint32_t seedBase;
+    int32_t encoding;         // RT_TRACE_LINEAR / RT_TRACE_FRAME0
+};
+using TraceKernelFn = void (*)(KernelArgs, TraceArgs);
+hipError_t launch_trace(const KernelArgs& a, const TraceArgs& q, const Variant& v, unsigned grid, size_t smem,
+                        hipStream_t st);
+// rtEnqueueCameraPaths: launch_camera_rays' records plus each work-item's seed after CreateRay
+hipError_t launch_camera_paths(const KernelArgs& a, float4* rays, uint32_t* seeds, uint32_t n, int math,
+                               hipStream_t st);
+
 // ---- surface records of ray hits (rt_surface.hpp) ------------------------------------------------
 // rtEnqueueHitSurfaces / rtEnqueueFrameFeatures: KernelArgs carries trisFull (uvs), packedTris (e1, e2),
 // shadeTris (normals, mtlIndex), nTris and -- accumulating variant only -- materials; the rest is unused.
@@ -140,13 +162,13 @@ hipError_t launch_pack(const rt_cl_triangle* tris, uint32_t n_tris, float4* pt, 
 // Workgroups per CU of a kernel at a dynamic LDS size, remembered per (kernel family, variant): the
 // runtime is asked on the first use and again when the LDS size differs.  The kernel is picked as
 // the launch picks it, from the same Variant.
-enum class Family : int { Entry, WfExtend, WfShade, Query };
+enum class Family : int { Entry, WfExtend, WfShade, Query, Trace };
 struct OccupancyCache {
     struct Entry {
         int blocks;   // 0: not asked yet
         size_t smem;
     };
-    Entry e[(int)Family::Query + 1][kVariantSlots] = {};
+    Entry e[(int)Family::Trace + 1][kVariantSlots] = {};
     int get(Family f, const Variant& v, size_t smem);
 };
 
@@ -162,6 +184,8 @@ struct Policy {
     void (*camera_rays)(KernelArgs, float4*, uint32_t);
     void (*pack_mats)(const rt_cl_material*, float4*, uint32_t);  // the policy's material records
     SurfaceKernelFn surfaces, surfaces_accum;  // hit_surfaces<M, false / true>
+    TraceKernelFn (*trace)(const Variant&);
+    void (*camera_paths)(KernelArgs, float4*, uint32_t*, uint32_t);
 };
 const Policy& shipped_policy();
 // the step schedule's entry points are specialised per launch kind (step_body kMode: 1 fused, 2

@@ -62,7 +62,8 @@ const Policy& shipped_policy() {
     static const Policy shipped = {pick_entry<MathShipped>, wf_pick<MathShipped>, query_pick<MathShipped>,
                                    accum_frames_shipped,    accum_key_shipped,    camera_rays<MathShipped>,
                                    pack_mats_shipped,
-                                   hit_surfaces<MathShipped, false>, hit_surfaces<MathShipped, true>};
+                                   hit_surfaces<MathShipped, false>, hit_surfaces<MathShipped, true>,
+                                   trace_pick<MathShipped>, camera_paths<MathShipped>};
     return shipped;
 }
 

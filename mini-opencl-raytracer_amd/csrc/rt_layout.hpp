@@ -74,6 +74,10 @@ constexpr uint32_t kWfRingBytes = 64u * 32u;  // extend: per-wave ray ring ({o, 
 constexpr unsigned kQueryThreads = 512;          // query workgroup: 8 waves (LDS scene staged once per 8)
 constexpr uint32_t kQueryRingBytes = 64u * 32u;  // per-wave ring of 64 rt_ray records
 
+// ---- path tracing over caller rays (rt_trace.hpp) ----
+constexpr unsigned kTraceThreads = 256;          // trace workgroup: 4 waves, as the step schedule's
+constexpr uint32_t kTraceRingBytes = 64u * 32u + 64u * 4u;  // per-wave ring of 64 {rt_ray, seed} records
+
 // ---- surface records (rt_surface.hpp) ----
 constexpr unsigned kSurfaceThreads = 256;        // one record per lane, no LDS
 

@@ -41,6 +41,8 @@ constexpr Knob kKnobs[] = {
     {RT_TUNE_PERFRAME_DEFER_MIN, &Tuning::pf_defer_min, nullptr, 0, INT_MAX, 1},  // any value >= 0
     {RT_TUNE_PERFRAME_BATCH, &Tuning::pf_batch, nullptr, 1, (int)rtk::kMaxFusedFrames, 1},
     {RT_TUNE_QUERY_REFILL_MIN, &Tuning::query_refill_min, nullptr, 1, 64, 1},
+    {RT_TUNE_TRACE_REFILL_MIN, &Tuning::trace_refill_min, nullptr, 1, 64, 1},
+    {RT_TUNE_TRACE_SHADE_MIN, &Tuning::trace_shade_min, nullptr, 1, 64, 1},
 };
 
 const Knob* find(int param) {

@@ -41,6 +41,10 @@ struct Tuning {
     // profiles/r02/wavefront/sweep_bunny.txt)
     uint32_t wf_refill_min = 32, wf_streams_per_cu = 0, wf_top_limit = 256;  // streams 0: auto
     uint32_t query_refill_min = 32;    // ray queries: RT_TUNE_QUERY_REFILL_MIN
+    // path tracing over caller rays (rt_trace.hpp), swept on MI355X at 4K, 9 bounces: refill at 8 free
+    // lanes against the query's 32 (Cornell 2.17 -> 1.81 ms, bunny proxy 2.57 -> 2.54 ms); shading keeps
+    // the step schedule's 48 (32 is 2 % faster on Cornell, 5 % slower on the proxy) -- profiles/trace/
+    uint32_t trace_refill_min = 8, trace_shade_min = 48;
 };
 
 // RT_SUCCESS, or RT_INVALID_VALUE for an id the table does not hold (the retired ones and
