@@ -110,6 +110,17 @@ public:
     inline void TemporalAccumulate(std::shared_ptr<CLKernel> kernel, const Buffer& cur, const Buffer& curFeatures,
                                    const Buffer* hist, const Buffer* histFeatures, unsigned width, unsigned height,
                                    const rt_temporal_params& params, const Buffer& out) const;
+    // extensions: adaptive sampling (rt_hip.h): per-pixel sample statistics from linear path results (ids null:
+    // record i is pixel i), the ordered list of pixels that still need samples, camera paths for such a list,
+    // and the statistics resolved into an {r, g, b, sample count} image
+    inline void AccumulateSamples(std::shared_ptr<CLKernel> kernel, const Buffer* ids, const Buffer& results, size_t first,
+                                  size_t n, size_t nPixels, const Buffer& stats) const;
+    inline void SelectPixels(std::shared_ptr<CLKernel> kernel, const Buffer& stats, unsigned width, unsigned height,
+                             const rt_adaptive_params& params, const Buffer& ids, const Buffer& result) const;
+    inline void CameraPathsFor(std::shared_ptr<CLKernel> kernel, const Buffer& ids, size_t first, size_t n,
+                               const Buffer& rays, const Buffer& seeds) const;
+    inline void ResolveSamples(std::shared_ptr<CLKernel> kernel, const Buffer& stats, unsigned width, unsigned height,
+                               const Buffer& out) const;
     // extensions: moving geometry (rtEnqueueUpdateVertices, rtRefitBVH); normals may be null
     void UpdateVertices(const Buffer& tris, size_t firstTri, size_t nTris, const Buffer& positions,
                         const Buffer* normals = nullptr) const {
@@ -187,6 +198,27 @@ inline void CLContext::TemporalAccumulate(std::shared_ptr<CLKernel> kernel, cons
                                       hist ? hist->get() : nullptr, histFeatures ? histFeatures->get() : nullptr, width,
                                       height, &params, out.get()),
           "Failed to enqueue temporal accumulate");
+}
+inline void CLContext::AccumulateSamples(std::shared_ptr<CLKernel> kernel, const Buffer* ids, const Buffer& results,
+                                         size_t first, size_t n, size_t nPixels, const Buffer& stats) const {
+    check(rtEnqueueAccumulateSamples(ctx_, kernel->GetKernel(), ids ? ids->get() : nullptr, results.get(), first, n,
+                                     nPixels, stats.get()),
+          "Failed to enqueue sample accumulation");
+}
+inline void CLContext::SelectPixels(std::shared_ptr<CLKernel> kernel, const Buffer& stats, unsigned width, unsigned height,
+                                    const rt_adaptive_params& params, const Buffer& ids, const Buffer& result) const {
+    check(rtEnqueueSelectPixels(ctx_, kernel->GetKernel(), stats.get(), width, height, &params, ids.get(), result.get()),
+          "Failed to enqueue pixel selection");
+}
+inline void CLContext::CameraPathsFor(std::shared_ptr<CLKernel> kernel, const Buffer& ids, size_t first, size_t n,
+                                      const Buffer& rays, const Buffer& seeds) const {
+    check(rtEnqueueCameraPathsFor(ctx_, kernel->GetKernel(), ids.get(), first, n, rays.get(), seeds.get()),
+          "Failed to enqueue camera paths");
+}
+inline void CLContext::ResolveSamples(std::shared_ptr<CLKernel> kernel, const Buffer& stats, unsigned width,
+                                      unsigned height, const Buffer& out) const {
+    check(rtEnqueueResolveSamples(ctx_, kernel->GetKernel(), stats.get(), width, height, out.get()),
+          "Failed to enqueue sample resolve");
 }
 inline void CLContext::RefitBVH(std::shared_ptr<CLKernel> kernel) const {
     check(rtRefitBVH(ctx_, kernel->GetKernel()), "Failed to refit BVH");

@@ -334,6 +334,107 @@ int rtEnqueueTracePaths(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem seeds /
                         size_t n, const rt_trace_params* params, rt_mem out);
 int rtEnqueueCameraPaths(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem rays, rt_mem seeds);
 
+/* ---- adaptive sampling: per-pixel sample statistics and selection (extension) ------------------
+ * Four calls that let a progressive renderer put its paths where the noise is: per-pixel statistics
+ * of linear path results, the selection of the pixels that still need samples as a compacted list in
+ * ascending order, camera paths for such a list, and the resolve of the statistics into the
+ * {r, g, b, w} image rtEnqueueDenoise and rtEnqueueTemporalAccumulate take.  One round is
+ *   rtEnqueueSelectPixels -> read `result` -> rtEnqueueCameraPathsFor -> rtEnqueueTracePaths
+ *   (RT_TRACE_LINEAR) -> rtEnqueueAccumulateSamples, each over records [0, selected).
+ *
+ * Every operation below is one correctly rounded fp32 operation; nothing is contracted, denormals are
+ * kept, `/` is the IEEE division, comparisons are IEEE comparisons (false for a NaN).  The definition
+ * is the same in every math mode of `k`, except where rtEnqueueCameraPathsFor says otherwise.
+ *
+ * rt_pixel_stats, 32 B per pixel, all zero = no samples: the sum of the samples' linear radiance, the
+ * sample count n (an integer value held as a float, exact to 2^24), and Welford's running mean and sum
+ * of squared deviations of the samples' luminance.  reserved[2] is kept as found.
+ *
+ * 1. rtEnqueueAccumulateSamples, for records i in [first, first + n): p = ids[i] (uint32; `ids` may be
+ *    NULL, then p = i), s = results[i].radiance (an rt_path_result as RT_TRACE_LINEAR writes it).  The
+ *    record is skipped and stats[p] left untouched when p >= n_pixels (a value from `ids` becomes an
+ *    address only after this test) or a channel c of s is not finite, !(fabsf(c) <= FLT_MAX).
+ *    Otherwise, on stats[p]:
+ *      y       = (0.2126f * s.r + 0.7152f * s.g) + 0.0722f * s.b
+ *      n'      = n + 1.0f
+ *      d       = y - mean_y
+ *      mean_y' = mean_y + d / n'
+ *      m2_y'   = m2_y + d * (y - mean_y')
+ *      sum'    = sum + s            per channel
+ *    The ids of one call are meant to be distinct; if they are not, the record of a repeated pixel ends
+ *    as some mixture of its duplicates' updates and nothing outside that record is touched.  Several
+ *    samples per pixel are several calls; the in-order queue fixes their order.
+ *    Errors, in this order after the context and the kernel: first + n > 2^31, n_pixels 0 or above 2^31
+ *    RT_INVALID_VALUE; `results` or `stats` NULL or of another context, a non-NULL `ids` of another
+ *    context, or `stats` the same buffer as `ids` or `results` RT_INVALID_MEM_OBJECT; the range beyond
+ *    `ids` (4 B per record) or `results` (16 B), or `stats` under 32 * n_pixels bytes
+ *    RT_INVALID_BUFFER_SIZE; n == 0 RT_SUCCESS with no launch.
+ *
+ * 2. rtEnqueueSelectPixels.  Pixel p = (x, y) is record y * width + x of `stats`, which is only read.
+ *    A pixel q with n >= 2.0f is hot exactly when
+ *      v = (m2_y / (n - 1.0f)) / n
+ *      b = threshold * (mean_y + floor_y)
+ *      v > b * b
+ *    (the variance of the mean luminance above the square of the allowed error); a pixel with fewer than
+ *    two samples is not hot.  Pixel p is selected when n_p < (float)min_samples, not selected when n_p >=
+ *    (float)max_samples, and otherwise selected exactly when some q with |dx|, |dy| <= radius inside the
+ *    image is hot.  ids[0 .. selected) receives the selected pixel indices in ascending order, the slots
+ *    from `selected` on keep their bytes, and `result` receives {selected, number of hot pixels, 0, 0}.
+ *    The result is a function of the inputs alone: the compaction is an ordered one (per-block counts, a
+ *    scan of the block counts, ballot / lane-prefix ranks inside a wave), no atomic append.  Its scratch
+ *    belongs to the kernel object, grown before anything is enqueued and freed at release.
+ *    Errors: `params` NULL, threshold or floor_y negative, not finite or above 2^20, min_samples >
+ *    max_samples, max_samples 0 or above 2^20, radius > 2, width or height zero, width * height > 2^31
+ *    RT_INVALID_VALUE; a buffer NULL or of another context, or `ids` or `result` the same buffer as
+ *    `stats` or as each other RT_INVALID_MEM_OBJECT; `stats` under 32 B per pixel, `ids` under 4 B per
+ *    pixel or `result` under 16 B RT_INVALID_BUFFER_SIZE.
+ *
+ * 3. rtEnqueueCameraPathsFor: for records i in [first, first + n), rays[i] and seeds[i] receive exactly
+ *    the bytes rtEnqueueCameraPaths writes to rays[gid] and seeds[gid] for gid = ids[i], from k's current
+ *    WIDTH, HEIGHT, FRAME_COUNT and camera slots, in k's math mode.  Any uint32 is a valid gid: it only
+ *    enters arithmetic, as get_global_id(0) does in CreateRay.
+ *    Errors, in this order: one of those slots unset, or WIDTH or HEIGHT zero RT_INVALID_KERNEL_ARGS;
+ *    first + n > 2^31 RT_INVALID_VALUE; a buffer NULL or of another context, or `rays` or `seeds` the
+ *    same buffer as `ids` or as each other RT_INVALID_MEM_OBJECT; the range beyond any buffer (4, 32 and
+ *    4 B per record) RT_INVALID_BUFFER_SIZE; n == 0 RT_SUCCESS with no launch.
+ *
+ * 4. rtEnqueueResolveSamples: out[p] = {g(sum.r / n), g(sum.g / n), g(sum.b / n), n} with g(x) =
+ *    pm_pow(x, 0.45454545f) of rt_pinned_math.h in every math mode; a pixel with n == 0 gets sixteen
+ *    zero bytes.  The layout is BUFFER_OUT's with w the sample count, so the result feeds
+ *    rtEnqueueDenoise and rtEnqueueTemporalAccumulate (history_frames = 0) as it is.  Bytes of `out` past
+ *    width * height * 16 are not touched.  Behaviour is specified for finite, non-negative sums; other
+ *    values may propagate in any way, but none becomes an address.
+ *    Errors: width or height zero, width * height > 2^31 RT_INVALID_VALUE; a buffer NULL or of another
+ *    context, or `out` the same buffer as `stats` RT_INVALID_MEM_OBJECT; `stats` under 32 B per pixel or
+ *    `out` under 16 B RT_INVALID_BUFFER_SIZE.
+ *
+ * Ordering of all four is a query's: asynchronous on the context's in-order queue, coalesced per-frame
+ * launches first, after the pending accumulations, "another call touching the context" for the
+ * deferral rules; `stats` (call 1), `ids` and `result`, `rays` and `seeds`, and `out` count as written.
+ * With timing on each call adds to kernel_ms and counts as one launch.  No scene need be bound for
+ * calls 1, 2 and 4. */
+typedef struct rt_pixel_stats {
+    float sum[3];   /* sum of the samples' linear radiance */
+    float n;        /* samples taken */
+    float mean_y;   /* running mean of the luminance */
+    float m2_y;     /* running sum of squared deviations of the luminance */
+    uint32_t reserved[2];
+} rt_pixel_stats; /* 32 B */
+typedef struct rt_adaptive_params {
+    float threshold;      /* relative standard error of the mean luminance above which a pixel is hot */
+    float floor_y;        /* added to the mean luminance, so that dark pixels do not dominate */
+    uint32_t min_samples; /* a pixel below this count is always selected */
+    uint32_t max_samples; /* a pixel at or above this count is never selected */
+    uint32_t radius;      /* 0..2: Chebyshev distance within which a hot pixel selects its neighbours */
+} rt_adaptive_params; /* 20 B */
+typedef struct rt_select_result { uint32_t selected, hot, reserved[2]; } rt_select_result; /* 16 B */
+int rtEnqueueAccumulateSamples(rt_context ctx, rt_kernel k, rt_mem ids /* may be NULL */, rt_mem results, size_t first,
+                               size_t n, size_t n_pixels, rt_mem stats);
+int rtEnqueueSelectPixels(rt_context ctx, rt_kernel k, rt_mem stats, unsigned width, unsigned height,
+                          const rt_adaptive_params* params, rt_mem ids, rt_mem result);
+int rtEnqueueCameraPathsFor(rt_context ctx, rt_kernel k, rt_mem ids, size_t first, size_t n, rt_mem rays, rt_mem seeds);
+int rtEnqueueResolveSamples(rt_context ctx, rt_kernel k, rt_mem stats, unsigned width, unsigned height, rt_mem out);
+
 /* ---- surface records of ray hits, and first-hit feature buffers ----------------------------
  * rtEnqueueHitSurfaces writes, for records [first, first + n) of `rays` (rt_ray) and `hits`
  * (rt_ray_hit), the same slots of `surfaces` (rt_surface); the other slots are not touched.  The

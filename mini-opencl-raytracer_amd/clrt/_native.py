@@ -71,6 +71,11 @@ QUERY_CLOSEST, QUERY_ANY = 0, 1
 PATH_RESULT_DTYPE = np.dtype([("radiance", np.float32, (3,)), ("prim", np.int32)])
 assert PATH_RESULT_DTYPE.itemsize == 16
 TRACE_LINEAR, TRACE_FRAME0 = 0, 1
+# rt_pixel_stats / rt_select_result (rt_hip.h): the records of the adaptive-sampling calls
+PIXEL_STATS_DTYPE = np.dtype([("sum", np.float32, (3,)), ("n", np.float32), ("mean_y", np.float32),
+                              ("m2_y", np.float32), ("reserved", np.uint32, (2,))])
+SELECT_RESULT_DTYPE = np.dtype([("selected", np.uint32), ("hot", np.uint32), ("reserved", np.uint32, (2,))])
+assert PIXEL_STATS_DTYPE.itemsize == 32 and SELECT_RESULT_DTYPE.itemsize == 16
 # rt_surface / rt_pixel_features (rt_hip.h): the records of rtEnqueueHitSurfaces and rtEnqueueFrameFeatures
 SURFACE_DTYPE = np.dtype([("position", np.float32, (3,)), ("t", np.float32),
                           ("normal", np.float32, (3,)), ("prim", np.int32),
@@ -119,6 +124,13 @@ class TRACE_PARAMS(ctypes.Structure):
     """rt_trace_params (rt_hip.h): rtEnqueueTracePaths' seed base (used without a seed buffer) and the
     encoding of the radiance it writes."""
     _fields_ = [("seed_base", ctypes.c_uint32), ("encoding", ctypes.c_int)]
+
+
+class ADAPTIVE_PARAMS(ctypes.Structure):
+    """rt_adaptive_params (rt_hip.h): rtEnqueueSelectPixels' error threshold, luminance floor, the two
+    sample-count caps and the dilation radius."""
+    _fields_ = [("threshold", ctypes.c_float), ("floor_y", ctypes.c_float), ("min_samples", ctypes.c_uint32),
+                ("max_samples", ctypes.c_uint32), ("radius", ctypes.c_uint32)]
 
 
 class DENOISE_PARAMS(ctypes.Structure):
@@ -190,6 +202,12 @@ _HIP_PROTOS = {
     "rtEnqueueTracePaths": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t,
                                            ctypes.POINTER(TRACE_PARAMS), _vp]),
     "rtEnqueueCameraPaths": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp]),
+    "rtEnqueueAccumulateSamples": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                                  _vp]),
+    "rtEnqueueSelectPixels": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
+                                             ctypes.POINTER(ADAPTIVE_PARAMS), _vp, _vp]),
+    "rtEnqueueCameraPathsFor": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
+    "rtEnqueueResolveSamples": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint, _vp]),
     "rtEnqueueHitSurfaces": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtEnqueueFrameFeatures": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint, _vp]),
     "rtEnqueueDenoise": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,

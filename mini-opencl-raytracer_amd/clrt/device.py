@@ -112,6 +112,39 @@ class CLContext:
         check(self._lib.rtEnqueueCameraPaths(self.handle, kernel.handle, int(work_size), rays.handle, seeds.handle),
               "Failed to enqueue camera paths")
 
+    def AccumulateSamples(self, kernel: "CLKernel", ids: "Buffer | None", results: "Buffer", n: int, n_pixels: int,
+                          stats: "Buffer", first: int = 0) -> None:
+        """rtEnqueueAccumulateSamples: the linear radiances of records [first, first + n) of `results`
+        (N.PATH_RESULT_DTYPE) added to the statistics (N.PIXEL_STATS_DTYPE) of pixels ids[i] (uint32; without
+        `ids`, of pixel i); out-of-range ids and non-finite samples are skipped."""
+        check(self._lib.rtEnqueueAccumulateSamples(self.handle, kernel.handle, ids.handle if ids is not None else None,
+                                                   results.handle, int(first), int(n), int(n_pixels), stats.handle),
+              "Failed to enqueue sample accumulation")
+
+    def SelectPixels(self, kernel: "CLKernel", stats: "Buffer", width: int, height: int, ids: "Buffer",
+                     result: "Buffer", threshold: float = 0.05, floor_y: float = 0.01, min_samples: int = 4,
+                     max_samples: int = 64, radius: int = 1) -> None:
+        """rtEnqueueSelectPixels: the pixels of the width x height statistics that still need samples, as
+        ascending uint32 indices at the head of `ids`; `result` (N.SELECT_RESULT_DTYPE) receives their
+        number and the number of hot pixels."""
+        params = N.ADAPTIVE_PARAMS(float(threshold), float(floor_y), int(min_samples), int(max_samples), int(radius))
+        check(self._lib.rtEnqueueSelectPixels(self.handle, kernel.handle, stats.handle, int(width), int(height),
+                                              ctypes.byref(params), ids.handle, result.handle),
+              "Failed to enqueue pixel selection")
+
+    def CameraPathsFor(self, kernel: "CLKernel", ids: "Buffer", n: int, rays: "Buffer", seeds: "Buffer",
+                       first: int = 0) -> None:
+        """rtEnqueueCameraPathsFor: CameraPaths' ray and seed of work-item ids[i] into records i of
+        [first, first + n)."""
+        check(self._lib.rtEnqueueCameraPathsFor(self.handle, kernel.handle, ids.handle, int(first), int(n), rays.handle,
+                                                seeds.handle), "Failed to enqueue camera paths")
+
+    def ResolveSamples(self, kernel: "CLKernel", stats: "Buffer", width: int, height: int, out: "Buffer") -> None:
+        """rtEnqueueResolveSamples: the statistics as a gamma-encoded {r, g, b, sample count} image, the
+        layout rtEnqueueDenoise and rtEnqueueTemporalAccumulate take."""
+        check(self._lib.rtEnqueueResolveSamples(self.handle, kernel.handle, stats.handle, int(width), int(height),
+                                                out.handle), "Failed to enqueue sample resolve")
+
     def HitSurfaces(self, kernel: "CLKernel", rays: "Buffer", hits: "Buffer", surfaces: "Buffer", n: int,
                     first: int = 0) -> None:
         """rtEnqueueHitSurfaces: the surface (N.SURFACE_DTYPE: position, shading and geometric normal,

@@ -48,6 +48,8 @@ class Raytracer:
         self._cast_bufs: tuple | None = None  # (capacity in rays, ray buffer, hit buffer) of cast()
         self._surf_buf: tuple | None = None   # (capacity in records, surface buffer) of surfaces()
         self._trace_bufs: tuple | None = None  # (capacity in records, ray, seed and result buffers) of trace()
+        self._adaptive: dict | None = None    # render_adaptive(): statistics, selected list, result, image
+        self._sample_frame = 1                # render_adaptive(): FRAME_COUNT of the next sample
         self._feat_buf: Buffer | None = None  # features(): width * height records
         self._denoise_buf: Buffer | None = None  # denoise(): the filtered image, width * height slots
         self._temporal_feat: list = [None, None]  # temporal(): this call's and the previous call's features
@@ -225,6 +227,80 @@ class Raytracer:
         self.ctx.ReadBuffer(rb, rays)
         self.ctx.ReadBuffer(sb, seeds, blocking=True)
         return rays, seeds
+
+    def _adaptive_buffers(self) -> dict:
+        """The kept buffers of render_adaptive(): statistics (zeroed when created), the selected list, the
+        select's result and the resolved image."""
+        if self._adaptive is None:
+            work = self.width * self.height
+            mk = self.ctx.create_buffer
+            self._adaptive = {"stats": mk(N.MEM_READ_WRITE, work * N.PIXEL_STATS_DTYPE.itemsize),
+                              "ids": mk(N.MEM_READ_WRITE, work * 4),
+                              "result": mk(N.MEM_READ_WRITE, N.SELECT_RESULT_DTYPE.itemsize),
+                              "image": mk(N.MEM_READ_WRITE, work * 16)}
+            self.ctx.WriteBuffer(self._adaptive["stats"], np.zeros(work, N.PIXEL_STATS_DTYPE))
+        return self._adaptive
+
+    def render_adaptive(self, rounds: int, samples_per_round: int = 1, threshold: float = 0.05, floor_y: float = 0.01,
+                        min_samples: int = 4, max_samples: int = 64, radius: int = 1, on_sample=None) -> tuple:
+        """Progressive rendering that puts its paths where the noise is.  Per round the device selects the
+        pixels that still need samples (rtEnqueueSelectPixels: fewer than min_samples, or within `radius`
+        of a pixel whose mean luminance has a relative standard error above `threshold`, and fewer than
+        max_samples), the host reads the 16-B result and stops when nothing is selected; then
+        samples_per_round times the selected pixels get one more path each: FRAME_COUNT is set to a kept
+        sample-frame counter (1, 2, ...), and rtEnqueueCameraPathsFor, rtEnqueueTracePaths (linear) and
+        rtEnqueueAccumulateSamples run over the list.  At the end the statistics are resolved
+        (rtEnqueueResolveSamples) into a kept buffer.  Returns the (H, W, 4) image, whose w slot is the
+        pixel's sample count, and a dict: rounds run, paths traced, and the last select's selected / hot.
+        The statistics persist across calls: reset_samples() after a camera move or move_vertices().
+        frame_count and BUFFER_OUT are left as they are.  `on_sample(round, sample_frame, n, buffers)` is
+        called after each sample's calls are enqueued (buffers: ids, results, stats; for tools and tests)."""
+        b = self._adaptive_buffers()
+        work = self.width * self.height
+        rb, sb, ob = self._trace_buffers(work)
+        res = np.zeros(1, N.SELECT_RESULT_DTYPE)
+        info = {"rounds": 0, "paths": 0, "selected": 0, "hot": 0}
+        at = self.frame_count
+        try:
+            for rnd in range(int(rounds)):
+                self.ctx.SelectPixels(self.kernel, b["stats"], self.width, self.height, b["ids"], b["result"], threshold,
+                                      floor_y, min_samples, max_samples, radius)
+                self.ctx.ReadBuffer(b["result"], res, blocking=True)
+                n = int(res["selected"][0])
+                info["selected"], info["hot"] = n, int(res["hot"][0])
+                if n == 0:
+                    break
+                info["rounds"] += 1
+                for _ in range(int(samples_per_round)):
+                    self.frame_count = self._sample_frame
+                    self.set_uniforms()
+                    self.ctx.CameraPathsFor(self.kernel, b["ids"], n, rb, sb)
+                    self.ctx.TracePaths(self.kernel, rb, ob, n, seeds=sb, encoding=N.TRACE_LINEAR)
+                    self.ctx.AccumulateSamples(self.kernel, b["ids"], ob, n, work, b["stats"])
+                    if on_sample is not None:
+                        on_sample(rnd, self._sample_frame, n, {"ids": b["ids"], "results": ob, "stats": b["stats"]})
+                    self._sample_frame += 1
+                    info["paths"] += n
+        finally:
+            self.frame_count = at
+            self.kernel.set_uint(N.FRAME_COUNT, at)
+        self.ctx.ResolveSamples(self.kernel, b["stats"], self.width, self.height, b["image"])
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self.ctx.ReadBuffer(b["image"], out, blocking=True)
+        return out, info
+
+    def sample_stats(self) -> np.ndarray:
+        """render_adaptive()'s per-pixel statistics as an (H, W) array of N.PIXEL_STATS_DTYPE."""
+        out = np.empty((self.height, self.width), N.PIXEL_STATS_DTYPE)
+        self.ctx.ReadBuffer(self._adaptive_buffers()["stats"], out, blocking=True)
+        return out
+
+    def reset_samples(self) -> None:
+        """Zero render_adaptive()'s statistics and restart its sample frames at 1: after a camera move or
+        move_vertices() the samples taken so far are of another image."""
+        work = self.width * self.height
+        self.ctx.WriteBuffer(self._adaptive_buffers()["stats"], np.zeros(work, N.PIXEL_STATS_DTYPE))
+        self._sample_frame = 1
 
     def features(self, n_frames: int = 1) -> np.ndarray:
         """First-hit feature buffers for a denoiser (rtEnqueueFrameFeatures): an (H, W) array of
@@ -414,6 +490,10 @@ class Raytracer:
             for b in self._trace_bufs[1:]:
                 b.release()
             self._trace_bufs = None
+        if self._adaptive:
+            for b in self._adaptive.values():
+                b.release()
+            self._adaptive = None
         if self._feat_buf:
             self._feat_buf.release()
             self._feat_buf = None

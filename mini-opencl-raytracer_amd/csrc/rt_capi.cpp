@@ -32,6 +32,8 @@
 
 #include "../../include/rt_cl_types.h"
 #include "../../include/rt_hip.h"
+#include "rt_adaptive.hpp"
+#include "rt_adaptive_plan.hpp"
 #include "rt_bvh.hpp"
 #include "rt_denoise.hpp"
 #include "rt_denoise_plan.hpp"
@@ -88,6 +90,7 @@ struct rt_kernel_s {
     rti::WorkCounters counters;  // chunk counters, sky keys, rt_stats words
     rti::FeatureScratch feat;  // rtEnqueueFrameFeatures: a frame's camera rays and hits
     rti::DenoiseScratch denoise;  // rtEnqueueDenoise: the ping-pong image
+    rti::AdaptiveScratch adaptive;  // rtEnqueueSelectPixels: flag planes and block counts
     rtk::OccupancyCache occ;  // workgroups per CU of the kernels launched so far
 
     // (the caller has drained the context's streams, or nothing was ever launched)
@@ -99,6 +102,7 @@ struct rt_kernel_s {
         scene.release();
         feat.release();
         denoise.release();
+        adaptive.release();
     }
 };
 
@@ -1060,6 +1064,116 @@ int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem 
     a.depth_tolerance = p.depth_tolerance, a.normal_threshold = p.normal_threshold;
     a.k = p.k;
     return launch_on_queue(ctx, k, out, [&](hipStream_t st) { return rtt::launch_temporal(a, p, st); });
+}
+
+// ---- adaptive sampling (rt_adaptive.hip, rt_trace.hpp; the plans: rt_adaptive_plan.cpp) -------------
+
+int rtEnqueueAccumulateSamples(rt_context ctx, rt_kernel k, rt_mem ids, rt_mem results, size_t first, size_t n,
+                               size_t n_pixels, rt_mem stats) {
+    // 1. the handles and the plan: nothing is launched on an error
+    int rc = queue_head(ctx, k, {});
+    if (rc) return rc;
+    rtp::AccumIn in{};
+    in.first = first, in.n = n, in.n_pixels = n_pixels;
+    in.ids_given = ids != nullptr, in.ids_ok = ids && ids->ctx == ctx;
+    in.results_ok = results && results->ctx == ctx, in.stats_ok = stats && stats->ctx == ctx;
+    in.stats_is_input = stats && (stats == ids || stats == results);
+    in.ids_bytes = in.ids_ok ? ids->size : 0, in.results_bytes = in.results_ok ? results->size : 0;
+    in.stats_bytes = in.stats_ok ? stats->size : 0;
+    rtp::AccumPlan p;
+    rc = rtp::accumulate_plan(in, &p);
+    if (rc || p.nothing) return pending_error(ctx, rc);
+    // 2. one launch, in order on the context's stream after the pending accumulations and gathers
+    rta::AccumArgs a{};
+    a.ids = ids ? static_cast<const uint32_t*>(ids->dptr) : nullptr;
+    a.results = static_cast<const float4*>(results->dptr);
+    a.stats = static_cast<float4*>(stats->dptr);
+    a.first = p.first, a.count = p.count, a.n_pixels = p.n_pixels;
+    return launch_on_queue(ctx, k, stats, [&](hipStream_t st) { return rta::launch_accumulate(a, p, st); });
+}
+
+int rtEnqueueSelectPixels(rt_context ctx, rt_kernel k, rt_mem stats, unsigned width, unsigned height,
+                          const rt_adaptive_params* params, rt_mem ids, rt_mem result) {
+    // 1. the handles and the plan: nothing is allocated or launched on an error
+    int rc = queue_head(ctx, k, {});
+    if (rc) return rc;
+    rtp::SelectIn in{};
+    in.params_ok = params != nullptr;
+    if (params) {
+        in.threshold = params->threshold, in.floor_y = params->floor_y;
+        in.min_samples = params->min_samples, in.max_samples = params->max_samples, in.radius = params->radius;
+    }
+    in.width = width, in.height = height;
+    in.stats_ok = stats && stats->ctx == ctx, in.ids_ok = ids && ids->ctx == ctx;
+    in.result_ok = result && result->ctx == ctx;
+    in.aliased = (ids && (ids == stats || ids == result)) || (result && result == stats);
+    in.stats_bytes = in.stats_ok ? stats->size : 0, in.ids_bytes = in.ids_ok ? ids->size : 0;
+    in.result_bytes = in.result_ok ? result->size : 0;
+    rtp::SelectPlan p;
+    rc = rtp::select_plan(in, &p);
+    if (rc) return pending_error(ctx, rc);
+    // 2. the scratch, before anything is enqueued (growing it waits for nothing: rt_internal.hpp)
+    const hipError_t me = k->adaptive.reserve((size_t)p.scratch_bytes);
+    if (me != hipSuccess) return map_hip(me);
+    // 3. flags, count, scan, scatter: in order on the context's stream after the pending accumulations
+    rta::SelectArgs a{};
+    a.stats = static_cast<const float4*>(stats->dptr);
+    a.ids = static_cast<uint32_t*>(ids->dptr);
+    a.result = static_cast<uint4*>(result->dptr);
+    a.scratch = k->adaptive.bytes();
+    return launch_on_queue(ctx, k, ids, [&](hipStream_t st) {
+        const hipError_t e = rta::launch_select(a, p, st);
+        if (e == hipSuccess) mark_device_write(result, true);
+        return e;
+    });
+}
+
+int rtEnqueueCameraPathsFor(rt_context ctx, rt_kernel k, rt_mem ids, size_t first, size_t n, rt_mem rays, rt_mem seeds) {
+    // 1. the handles and the plan: nothing is launched on an error
+    int rc = queue_head(ctx, k, {});
+    if (rc) return rc;
+    rtp::PathsForIn in{};
+    in.slots_set = k->args.has({RT_ARG_WIDTH, RT_ARG_HEIGHT, RT_ARG_FRAME_COUNT, RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT,
+                                RT_ARG_CAMERA_UP});
+    rtk::KernelArgs a;
+    std::memset(&a, 0, sizeof(a));
+    if (in.slots_set) fill_camera(k->args, k->args.frame_count(), &a);
+    in.width = a.width, in.height = a.height;
+    in.first = first, in.n = n;
+    in.ids_ok = ids && ids->ctx == ctx, in.rays_ok = rays && rays->ctx == ctx, in.seeds_ok = seeds && seeds->ctx == ctx;
+    in.aliased = (rays && (rays == ids || rays == seeds)) || (seeds && seeds == ids);
+    in.ids_bytes = in.ids_ok ? ids->size : 0, in.rays_bytes = in.rays_ok ? rays->size : 0;
+    in.seeds_bytes = in.seeds_ok ? seeds->size : 0;
+    rtp::PathsForPlan p;
+    rc = rtp::paths_for_plan(in, &p);
+    if (rc || p.nothing) return pending_error(ctx, rc);
+    // 2. one launch in k's math mode, in order on the context's stream
+    return launch_on_queue(ctx, k, rays, [&](hipStream_t st) {
+        const hipError_t e = rtk::launch_camera_paths_for(a, static_cast<const uint32_t*>(ids->dptr), p.first, p.count,
+                                                          static_cast<float4*>(rays->dptr),
+                                                          static_cast<uint32_t*>(seeds->dptr), p.grid, k->math, st);
+        if (e == hipSuccess) mark_device_write(seeds, true);
+        return e;
+    });
+}
+
+int rtEnqueueResolveSamples(rt_context ctx, rt_kernel k, rt_mem stats, unsigned width, unsigned height, rt_mem out) {
+    // 1. the handles and the plan: nothing is launched on an error
+    int rc = queue_head(ctx, k, {});
+    if (rc) return rc;
+    rtp::ResolveIn in{};
+    in.width = width, in.height = height;
+    in.stats_ok = stats && stats->ctx == ctx, in.out_ok = out && out->ctx == ctx;
+    in.out_is_input = out && out == stats;
+    in.stats_bytes = in.stats_ok ? stats->size : 0, in.out_bytes = in.out_ok ? out->size : 0;
+    rtp::ResolvePlan p;
+    rc = rtp::resolve_plan(in, &p);
+    if (rc) return pending_error(ctx, rc);
+    // 2. one launch, in order on the context's stream after the pending accumulations and gathers
+    rta::ResolveArgs a{};
+    a.stats = static_cast<const float4*>(stats->dptr);
+    a.out = static_cast<float4*>(out->dptr);
+    return launch_on_queue(ctx, k, out, [&](hipStream_t st) { return rta::launch_resolve(a, p, st); });
 }
 
 int rtBuildBVH(rt_context ctx, rt_mem tris, size_t n_tris, unsigned max_prims_in_node, rt_mem nodes,

@@ -141,6 +141,12 @@ struct DenoiseScratch : ScratchBlock {
     float4* image() const { return static_cast<float4*>(block); }
 };
 
+// rtEnqueueSelectPixels' scratch: the two byte planes and the block counts (rtp::SelectPlan), in bytes.
+struct AdaptiveScratch : ScratchBlock {
+    hipError_t reserve(size_t bytes) { return ScratchBlock::reserve(bytes, 1); }
+    uint8_t* bytes() const { return static_cast<uint8_t*>(block); }
+};
+
 inline int map_hip(hipError_t e) {
     switch (e) {
         case hipSuccess: return RT_SUCCESS;

@@ -114,12 +114,14 @@ static const Policy& policy(int math) {
                                      accum_frames<MathDeviceLib>, accum_key<MathDeviceLib>, camera_rays<MathDeviceLib>,
                                      pack_mats,
                                      hit_surfaces<MathDeviceLib, false>, hit_surfaces<MathDeviceLib, true>,
-                                     trace_pick<MathDeviceLib>, camera_paths<MathDeviceLib>};
+                                     trace_pick<MathDeviceLib>, camera_paths<MathDeviceLib>,
+                                     camera_paths_for<MathDeviceLib>};
     static const Policy pinned = {pick_entry<MathPinned>,   wf_pick<MathPinned>,  query_pick<MathPinned>,
                                   accum_frames<MathPinned>, accum_key<MathPinned>, camera_rays<MathPinned>,
                                   pack_mats,
                                   hit_surfaces<MathPinned, false>, hit_surfaces<MathPinned, true>,
-                                     trace_pick<MathPinned>, camera_paths<MathPinned>};
+                                     trace_pick<MathPinned>, camera_paths<MathPinned>,
+                                     camera_paths_for<MathPinned>};
     return math == MathShipped::kId ? shipped_policy() : math == MathDeviceLib::kId ? devicelib : pinned;
 }
 
@@ -176,6 +178,13 @@ hipError_t launch_camera_paths(const KernelArgs& a, float4* rays, uint32_t* seed
                                hipStream_t st) {
     const dim3 grid((unsigned)(((uint64_t)n + 255u) / 256u));
     hipLaunchKernelGGL(policy(math).camera_paths, grid, dim3(256), 0, st, a, rays, seeds, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_camera_paths_for(const KernelArgs& a, const uint32_t* ids, uint32_t first, uint32_t n, float4* rays,
+                                   uint32_t* seeds, unsigned grid, int math, hipStream_t st) {
+    if ((uint64_t)grid * 256u < n) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(policy(math).camera_paths_for, dim3(grid), dim3(256), 0, st, a, ids, first, n, rays, seeds);
     return hipGetLastError();
 }
 

@@ -134,6 +134,9 @@ hipError_t launch_trace(const KernelArgs& a, const TraceArgs& q, const Variant& 
 // rtEnqueueCameraPaths: launch_camera_rays' records plus each work-item's seed after CreateRay
 hipError_t launch_camera_paths(const KernelArgs& a, float4* rays, uint32_t* seeds, uint32_t n, int math,
                                hipStream_t st);
+// rtEnqueueCameraPathsFor: records [first, first + n) of `rays` and `seeds` for the work-items ids[first ...]
+hipError_t launch_camera_paths_for(const KernelArgs& a, const uint32_t* ids, uint32_t first, uint32_t n, float4* rays,
+                                   uint32_t* seeds, unsigned grid, int math, hipStream_t st);
 
 // ---- surface records of ray hits (rt_surface.hpp) ------------------------------------------------
 // rtEnqueueHitSurfaces / rtEnqueueFrameFeatures: KernelArgs carries trisFull (uvs), packedTris (e1, e2),
@@ -186,6 +189,7 @@ struct Policy {
     SurfaceKernelFn surfaces, surfaces_accum;  // hit_surfaces<M, false / true>
     TraceKernelFn (*trace)(const Variant&);
     void (*camera_paths)(KernelArgs, float4*, uint32_t*, uint32_t);
+    void (*camera_paths_for)(KernelArgs, const uint32_t*, uint32_t, uint32_t, float4*, uint32_t*);
 };
 const Policy& shipped_policy();
 // the step schedule's entry points are specialised per launch kind (step_body kMode: 1 fused, 2

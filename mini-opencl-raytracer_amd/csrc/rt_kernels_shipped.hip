@@ -63,7 +63,8 @@ const Policy& shipped_policy() {
                                    accum_frames_shipped,    accum_key_shipped,    camera_rays<MathShipped>,
                                    pack_mats_shipped,
                                    hit_surfaces<MathShipped, false>, hit_surfaces<MathShipped, true>,
-                                   trace_pick<MathShipped>, camera_paths<MathShipped>};
+                                   trace_pick<MathShipped>, camera_paths<MathShipped>,
+                                   camera_paths_for<MathShipped>};
     return shipped;
 }
 

@@ -1,5 +1,6 @@
 // rt_trace.hpp -- path tracing over caller-supplied rays (rtEnqueueTracePaths) and the camera's
-// primary rays with their RNG state as such records (rtEnqueueCameraPaths).  Included at the end of
+// primary rays with their RNG state as such records (rtEnqueueCameraPaths; for a list of work-item
+// ids, rtEnqueueCameraPathsFor).  Included at the end of
 // rt_kernels_body.hpp; instantiated per math policy by the two kernel TUs, like rt_query.hpp.
 //
 // Per record the trace is the reference's InitRay(origin, dir) followed by Render
@@ -221,6 +222,28 @@ void trace_paths(KernelArgs a, TraceArgs q) {
 template <class M>
 __global__ __launch_bounds__(256) void camera_paths(KernelArgs a, float4* rays, uint32_t* seeds, uint32_t n) {
     camera_paths_body<M>(a, rays, seeds, n);
+}
+
+// rtEnqueueCameraPathsFor: records [first, first + n) receive camera_paths_body's bytes for gid = ids[i].
+// Any uint32 is a gid: like get_global_id(0) in CreateRay it only enters arithmetic, never an address.
+template <class M>
+__global__ __launch_bounds__(256) void camera_paths_for(KernelArgs a, const uint32_t* ids, uint32_t first, uint32_t n,
+                                                        float4* rays, uint32_t* seeds) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t r = (size_t)first + i;
+    const uint32_t gid = ids[r];
+    const F3 pos{a.camPos[0], a.camPos[1], a.camPos[2]};
+    const F3 front{a.camFront[0], a.camFront[1], a.camFront[2]};
+    const F3 up{a.camUp[0], a.camUp[1], a.camUp[2]};
+    const float angle = M::tan(0.5f * (45.0f * 3.1415f / 180.0f));  // kernel_bvh.cl:392
+    const uint32_t W = a.width, H = a.height;
+    const uint32_t py = gid / W, px = gid - py * W;
+    uint32_t seed = gid + frame_hash(a.frameCount);
+    const F3 d = camera_dir<M>(px, py, W, H, front, up, angle, seed);
+    rays[2 * r] = make_float4(pos.x, pos.y, pos.z, -__builtin_inff());
+    rays[2 * r + 1] = make_float4(d.x, d.y, d.z, kMaxDist);
+    seeds[r] = seed;
 }
 
 template <class M, bool S>
