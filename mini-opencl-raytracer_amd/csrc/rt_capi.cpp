@@ -468,6 +468,9 @@ static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, const LaunchArgs& la
     in.force_global = k->force_global;
     in.tune = k->tune;
     in.num_cus = ctx->num_cus;
+    // the tiles that can see the scene, from this launch's own camera slots and the root bounds as they
+    // are now (held frames share one argument copy, so one rectangle serves a fused launch)
+    if (const float* rb = sc.root_bounds()) in.view = rtp::view_cull_rect(in.W, in.H, la.f3[0], la.f3[1], la.f3[2], rb, rb + 3);
     return in;
 }
 
@@ -494,6 +497,7 @@ static void fill_args(rt_kernel k, const LaunchArgs& la, uint32_t first_frame, c
     a.gidBegin = p.gidBegin, a.gidEnd = p.gidEnd;
     a.rowBegin = p.rowBegin, a.rowCount = p.rowCount, a.tilesX = p.tilesX, a.nTiles = p.nTiles;
     a.bandPeriod = p.bandPeriod, a.bandPhase = p.bandPhase;
+    a.visTx0 = p.visTx0, a.visTy0 = p.visTy0, a.visW = p.visW, a.visH = p.visH, a.visTiles = p.visTiles;
     a.chunkPixels = p.chunkPixels, a.tailChunk = p.tailChunk, a.chunkSplit = p.chunkSplit, a.tailBase = p.tailBase;
     a.staticFirst = p.staticFirst, a.nParts = p.nParts, a.partLen = p.partLen;
     a.refillMin = p.refillMin, a.shadeMin = p.shadeMin;

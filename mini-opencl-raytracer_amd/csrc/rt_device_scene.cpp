@@ -2,6 +2,7 @@
 // uploads, the pack and refit launches) around the pure host half, rtp::pack_scene_host.
 #include "rt_device_scene.hpp"
 
+#include <cstring>
 #include <vector>
 
 #include "rt_kernels.hpp"
@@ -92,6 +93,14 @@ int DeviceScene::prepare(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     if (e != hipSuccess) return map_hip(e);
     n_nodes_ = p.n_nodes, n_tris_ = p.n_tris, n_mats_ = p.n_mats, n_top_ = p.n_top;
     oct_ok_ = p.oct_ok, goct_b_ = p.goct_b;
+    root_known_ = p.n_nodes > 0 && in.nodes_size >= sizeof(rt_cl_bvh_node);
+    if (root_known_) {
+        rt_cl_bvh_node root;
+        std::memcpy(&root, in.nodes, sizeof(root));
+        const float b[6] = {root.bounds.pmin.x, root.bounds.pmin.y, root.bounds.pmin.z,
+                            root.bounds.pmax.x, root.bounds.pmax.y, root.bounds.pmax.z};
+        std::memcpy(root_bounds_, b, sizeof(b));
+    }
     for_tris_ = tm, tris_gen_ = tm->generation, tris_struct_ = tm->structural;
     for_nodes_ = nm, nodes_gen_ = nm->generation, nodes_struct_ = nm->structural;
     for_mats_ = mm, mats_gen_ = mm ? mm->generation : 0;
@@ -120,6 +129,7 @@ int DeviceScene::refit(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     a.goct = goct_b_ ? goct_nodes_ : nullptr;
     a.goct_b = goct_b_, a.goct_group = RT_GOCT_GROUP ? RT_GOCT_GROUP : 1;
     a.g_nodes = g_nodes_;
+    root_known_ = false;  // the refit moves the root's bounds on the device
     hipStream_t st = qs(ctx);
     hipError_t e = rtr::launch_refit(a, st);
     // the triangle and shading records from the moved vertices; materials stay as packed

@@ -44,6 +44,10 @@ public:
     const float4* g_nodes() const { return g_nodes_; }        // 64-B node records, top of the tree first
     // regrouped octant records for the HBM/L2 walk (RT_GOCT_GROUP), null when this scene has none
     const float4* goct() const { return goct_b_ ? goct_nodes_ : nullptr; }
+    // The root node's bounds (nodes[0]: min xyz, max xyz) as the host last saw them: read at every full
+    // preparation, so a launch after a vertex or node write sees the new ones.  Null after a device
+    // refit, which moves them without the host looking: such launches do without the view cull.
+    const float* root_bounds() const { return root_known_ ? root_bounds_ : nullptr; }
     // rtDiagScenePrepares
     uint64_t full_prepares() const { return full_prepares_; }
     uint64_t refits() const { return refits_; }
@@ -70,6 +74,8 @@ private:
     uint64_t tris_struct_ = 0, nodes_struct_ = 0;
     uint32_t n_nodes_ = 0, n_tris_ = 0, n_mats_ = 0, n_top_ = 0, goct_b_ = 0;
     bool oct_ok_ = false;
+    bool root_known_ = false;
+    float root_bounds_[6] = {};
     uint64_t full_prepares_ = 0, refits_ = 0;
     // device records and their capacities (float4s)
     float4 *packed_tris_ = nullptr, *shade_tris_ = nullptr, *shade_mats_ = nullptr;

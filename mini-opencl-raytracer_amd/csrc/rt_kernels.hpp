@@ -68,6 +68,12 @@ struct KernelArgs {
     // counter partitions (per-frame launches without a bulk region): nParts (a power of two) contiguous
     // ranges of partLen work items, each with its tail counter at workCounter[kPartStride * q + 1]
     uint32_t nParts, partLen;
+    // the view cull (rt_view_cull.hpp; fused step launches): the work items are the frames of the
+    // visW x visH tiles from (visTx0, visTy0) of the launch's tile grid, visTiles = visW * visH; the
+    // tiles outside are not rendered, and accum_frames takes every frame of theirs as a primary miss.
+    // Without a cull: (0, 0, tilesX, tile rows, nTiles).  radStride, the flag words and the
+    // accumulation's grid stay in the full grid's numbering.
+    uint32_t visTx0, visTy0, visW, visH, visTiles;
 };
 
 using KernelFn = void (*)(KernelArgs);

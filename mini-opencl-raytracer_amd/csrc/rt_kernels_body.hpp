@@ -864,6 +864,21 @@ __device__ __forceinline__ bool next_chunk(const KernelArgs& a, uint32_t total, 
     return true;
 }
 
+// Fused launches hand out the tiles that can see the scene (the view cull, rt_view_cull.hpp): tile `t`
+// of those a.visW x a.visH as (tx, ty) and as the tile id of the launch's full grid, which the flag
+// words and the accumulation use.  Wave-uniform scalar arithmetic; the identity without a cull.
+constexpr bool kViewCull = RT_VIEW_CULL != 0;
+__device__ __forceinline__ uint32_t vis_tile(const KernelArgs& a, uint32_t t, uint32_t& tx, uint32_t& ty) {
+    const uint32_t w = kViewCull ? a.visW : a.tilesX;
+    ty = t / w;
+    tx = t - ty * w;
+    if (kViewCull) {
+        ty += a.visTy0;
+        tx += a.visTx0;
+    }
+    return ty * a.tilesX + tx;
+}
+
 // ---- step schedule: a per-wave state machine ------------------------------------------------
 // Every lane is in one of four states:
 //   IDLE  -- no path; refilled (new pixel -> camera ray) when enough lanes are idle
@@ -1120,7 +1135,9 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
     const F3 camUp{a.camUp[0], a.camUp[1], a.camUp[2]};
     const float angle = M::tan(0.5f * (45.0f * 3.1415f / 180.0f));  // kernel_bvh.cl:392
     const uint32_t bounces = (uint32_t)a.lightBounces;
-    const uint32_t total = a.nTiles * 64u * (fused ? a.nFrames : 1u);
+    // (fused: the tiles the launch hands out, a.visTiles of the a.nTiles -- vis_tile)
+    const uint32_t nVis = fused && kViewCull ? a.visTiles : a.nTiles;
+    const uint32_t total = nVis * 64u * (fused ? a.nFrames : 1u);
     // the radiance of a primary miss, max(1 * 0.5*skybox + 0, 0) per component (kernel_bvh.cl:360, :383)
     const float krad = M::max(madd<M>(1.0f, 0.5f * a.skyboxIntensity, 0.0f), 0.0f);
     // per-frame launches: a finished path with radiance (K_rad, K_rad, K_rad) over a stored value
@@ -1290,9 +1307,14 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                     }
                     // one 8x8 tile, one work item per lane (chunks are whole tiles)
                     uint32_t tile = unit >> 6;  // wave-uniform
-                    const uint32_t slot = fused ? tile / a.nTiles : 0u;  // frame-major (LDS scenes)
-                    tile -= slot * a.nTiles;
-                    const uint32_t ty = tile / a.tilesX, tx = tile - ty * a.tilesX;
+                    const uint32_t slot = fused ? tile / nVis : 0u;  // frame-major (LDS scenes)
+                    tile -= slot * nVis;
+                    uint32_t tx, ty;
+                    if (fused) {
+                        tile = vis_tile(a, tile, tx, ty);
+                    } else {
+                        ty = tile / a.tilesX, tx = tile - ty * a.tilesX;
+                    }
                     const uint32_t x = tx * 8u + ((uint32_t)lane & 7u),
                                    row = a.rowBegin + (ty * a.bandPeriod + a.bandPhase) * 8u + ((uint32_t)lane >> 3);
                     const uint64_t g64 = (uint64_t)row * a.width + x;
@@ -1342,13 +1364,13 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                     }
                     // fused: the tile's frame flags, all written here, at once, as one 64-bit
                     // word per (frame slot, tile) -- bit = lane, 1: decided as a primary miss
-                    // above -- at [unit / 64] (frame-major order: slot * nTiles + tile).  A flag
+                    // above -- at [slot * nTiles + tile], the tile's id in the full grid.  A flag
                     // byte per path written at its end, then 8 flag bytes per tile row here, went
                     // out as partial lines: 4K Cornell writes 0.94 -> 0.81 -> 0.69 GB per launch
                     // (profiles/r03/write_traffic.txt)
                     const unsigned long long skym = __ballot(valid && !keep);
                     if (fused && lane == 0)
-                        reinterpret_cast<unsigned long long*>(a.frameFlags)[unit >> 6] = skym;
+                        reinterpret_cast<unsigned long long*>(a.frameFlags)[slot * a.nTiles + tile] = skym;
                     const unsigned long long vm = __ballot(keep);
                     if (keep) {
                         const uint32_t pos = lane_rank(vm);
@@ -1429,12 +1451,17 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                     slot = tile % a.nFrames;
                     tile /= a.nFrames;
                 } else if (fused) {
-                    slot = tile / a.nTiles;
-                    tile -= slot * a.nTiles;
+                    slot = tile / nVis;
+                    tile -= slot * nVis;
+                }
+                uint32_t tx, ty;  // wave-uniform
+                if (fused) {
+                    (void)vis_tile(a, tile, tx, ty);
+                } else {
+                    ty = tile / a.tilesX, tx = tile - ty * a.tilesX;
                 }
                 if (state == kIdle && rank < take) {
                     const uint32_t w = used + rank;  // chunks are whole 8x8 tiles
-                    const uint32_t ty = tile / a.tilesX, tx = tile - ty * a.tilesX;
                     uint32_t pix = w;  // pixel in the tile
                     if (pxMajor) {
                         slot = w & (a.nFrames - 1u);
@@ -1856,7 +1883,12 @@ __device__ __forceinline__ void accum_frames_body(const KernelArgs& a, const uin
     if (a.frameCount != 0u) o = a.result[gid];
     const bool old_sky = a.frameCount == 0u ||
                          (__float_as_uint(o.x) == kold && __float_as_uint(o.y) == kold && __float_as_uint(o.z) == kold);
-    const uint32_t fl = a.flagTiles == 1u ? load_tile_flags(a, tile, lane)
+    // a tile the render left out (the view cull): every frame a primary miss.  Its flag words and
+    // radiance slots were not written by this render -- they hold what an earlier launch left -- and
+    // are not read.  (wave-uniform: one tile per wave)
+    const bool culled = kViewCull && (tx - a.visTx0 >= a.visW || ty - a.visTy0 >= a.visH);
+    const uint32_t fl = culled              ? (1u << a.nFrames) - 1u
+                        : a.flagTiles == 1u ? load_tile_flags(a, tile, lane)
                         : a.flagTiles == 2u ? (old_sky ? scan_sky_frames(a, gid, krf) : 0u)
                                             : load_flags(a, gid);
     if (fl == (1u << a.nFrames) - 1u && old_sky) {

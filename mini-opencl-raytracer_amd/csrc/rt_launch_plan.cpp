@@ -35,6 +35,9 @@ constexpr size_t kLdsBudget = 64 * 1024;       // per-workgroup LDS the scene pa
 #define RT_TAIL_SHARE_WAVES 4
 #endif
 
+// floor(a / b), b > 0
+int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
 }  // namespace
 
 uint32_t counter_parts() { return RT_COUNTER_PARTS; }
@@ -81,6 +84,29 @@ int plan_shape(const PlanIn& in, LaunchPlan* out) {
     if (n_tiles * 64 > 0xfff00000ull) return RT_INVALID_GLOBAL_WORK_SIZE;
     a.nTiles = (uint32_t)n_tiles;
     a.nFrames = n_frames;
+    a.visTx0 = 0u, a.visTy0 = 0u, a.visW = a.tilesX, a.visH = (uint32_t)tilesY, a.visTiles = a.nTiles;
+    // The view cull: a fused step launch leaves the tiles outside in.view out of its work -- every
+    // sample there is a primary miss, which the accumulation knows without the render (accum_frames_body).
+    // Not with stats (the counters see every tile), not with hit buffers bound (each pixel's id and t are
+    // written by its path), not with 0 bounces (a sample is then 0, not the sky constant).
+    if (RT_VIEW_CULL && !in.view.all() && fused && si == rtk::kSchedStep && !in.stats && !in.hit_bound &&
+        in.light_bounces > 0) {
+        const uint32_t tx0 = std::min(in.view.tx0, a.tilesX), tx1 = std::min(in.view.tx1, a.tilesX);
+        // tile row ty of this launch covers image rows [r, r + 8), r = rowBegin + (ty * period + phase) * 8;
+        // the rectangle covers rows [8 * view.ty0, 8 * view.ty1): the bands b = ty * period + phase with
+        // r + 8 > 8 * ty0 and r < 8 * ty1, then the ty among them -- an interval
+        const int64_t period = std::max<uint32_t>(in.band_period, 1u), phase = in.band_phase;
+        const int64_t b0 = floor_div(8 * (int64_t)in.view.ty0 - 8 - (int64_t)row0, 8) + 1;
+        const int64_t b1 = floor_div(8 * (int64_t)in.view.ty1 - (int64_t)row0 + 7, 8) - 1;  // inclusive
+        const int64_t ty0 = std::max<int64_t>(floor_div(b0 - phase + period - 1, period), 0);
+        const int64_t ty1 = std::min<int64_t>(floor_div(b1 - phase, period), (int64_t)tilesY - 1);  // inclusive
+        // (no tile of this launch in the rectangle -- a rank whose rows are all sky: it keeps all its tiles)
+        if (tx0 < tx1 && ty0 <= ty1) {
+            a.visTx0 = tx0, a.visW = tx1 - tx0;
+            a.visTy0 = (uint32_t)ty0, a.visH = (uint32_t)(ty1 - ty0 + 1);
+            a.visTiles = a.visW * a.visH;
+        }
+    }
     a.radStride = (uint32_t)g1;
     if (fused) {
         // fused frames: radiance slots indexed by global work-item id (the lane packs
@@ -168,7 +194,7 @@ void plan_handout(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out) {
     const int si = a.variant.sched;
     const bool wf = a.wf(), lds = a.variant.lds(), fused = in.fused;
     const uint32_t n_frames = in.n_frames;
-    const uint64_t n_tiles = a.nTiles;
+    const uint64_t n_tiles = a.visTiles;  // the tiles handed out (all of them unless the view cull applies)
     uint64_t grid = (uint64_t)(in.tune.max_blocks ? std::min(occ, in.tune.max_blocks) : occ) * (uint64_t)in.num_cus;
     // tiles: one workgroup per 16x16 tile at most; persistent schedules: one 8x8 tile per wave
     // (wavefront extend: 8 waves per workgroup)
@@ -180,7 +206,7 @@ void plan_handout(const PlanIn& in, int occ, int occ_shade, LaunchPlan* out) {
     {
         // bulk chunks only when every resident wave gets at least two of them; a small frame
         // (512x512: ~40 pixels per wave) is handed out 64 pixels at a time
-        const uint64_t tot = (uint64_t)a.nTiles * 64u * n_frames, waves = grid * 4u;
+        const uint64_t tot = n_tiles * 64u * n_frames, waves = grid * 4u;
         // fused work order (step_body) on the HBM/L2 scene path: pixel-major when F is a power of two
         // -- a pixel's frames side by side in a wave, so a step's lanes read fewer records: bunny
         // proxy 1.352 -> 1.282 ms/frame, emulated N = 8 rank 1.637 -> 1.535 ms

@@ -10,6 +10,7 @@
 
 #include "rt_layout.hpp"
 #include "rt_tuning.hpp"
+#include "rt_view_cull.hpp"
 
 namespace rtp {
 
@@ -31,6 +32,7 @@ struct PlanIn {
     bool force_global;
     Tuning tune;                            // rtKernelSetTuning
     int num_cus;
+    ViewRect view;                          // tiles that can see the scene (rt_view_cull.hpp); zero: all
 };
 
 struct LaunchPlan {
@@ -51,6 +53,9 @@ struct LaunchPlan {
     bool own_stream;                        // fused: the render goes to a render stream of its own
     bool pf_slots;                          // per-frame step launch: takes a counter slot, zeroes the other
     bool clear_counter_here;                // the launch's counters are cleared in front of it
+    // the tiles the hand-out covers: visW x visH of them from (visTx0, visTy0) of this launch's tile
+    // grid -- all of it (0, 0, tilesX, tilesY) unless the view cull applies; visTiles = visW * visH
+    uint32_t visTx0, visTy0, visW, visH, visTiles;
     // ---- plan_handout ----
     uint64_t grid;
     uint32_t tileMajor, chunkPixels, tailChunk, chunkSplit, tailBase, staticFirst, nParts, partLen;

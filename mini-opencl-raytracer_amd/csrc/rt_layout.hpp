@@ -31,6 +31,12 @@ constexpr uint32_t kEndWalk = 0xff000000u;
 #define RT_GOCT_END_WORD 1  // the HBM/L2 octant walk's END as kEndWalk (0: its sentinel's word, visited)
 #endif
 
+// the view cull (rt_view_cull.hpp): fused step launches hand out only the tiles that can see the scene,
+// the accumulation takes the others as primary misses (0: every tile is rendered, for A/B builds)
+#ifndef RT_VIEW_CULL
+#define RT_VIEW_CULL 1
+#endif
+
 // LDS node records of trees with at most kOctBMaxStride records per plane keep their B planes at
 // the fixed float4 offset kOctB, so a node step reads B with an immediate offset from A's address
 constexpr uint32_t kOctBMaxStride = 64;
