@@ -207,7 +207,9 @@ typedef struct rt_stats {
     /* diagnostic (step schedule, stats on): node steps, lanes served by node steps,
      * triangle steps, lanes served, shading rounds, lanes shaded, refill rounds, lanes freed,
      * then summed over all steps: lanes of the other traversal kind, lanes waiting to shade,
-     * free lanes, reserved */
+     * free lanes; last, in the default stats build only, the refill's pop iterations (launches with
+     * the camera-ray ring; the RT_TIMELINE and RT_LDS_CONFLICTS diagnostic builds keep other
+     * things in these words) */
     uint64_t sched[12];
     double accum_ms;   /* sum of the fused frames' accumulation launches (rtEnqueueKernelFrames);
                         * when overlapped (default) the spans include the wait for the render */

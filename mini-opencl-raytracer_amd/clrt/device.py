@@ -344,14 +344,18 @@ class CLKernel:
     def stats(self) -> dict:
         s = N.Stats()
         check(self._lib.rtKernelGetStats(self.handle, ctypes.byref(s)), "stats")
+        sched = dict(zip(("node_steps", "node_lanes", "tri_steps", "tri_lanes", "shade_rounds",
+                          "shade_lanes", "refill_rounds", "refill_lanes", "other_lanes",
+                          "shade_wait", "free_wait", "reserved"), list(s.sched)))
+        # the last word by what it holds in the default stats build: the refill's pop iterations (the
+        # diagnostic RT_TIMELINE / RT_LDS_CONFLICTS builds keep other things in these words: "reserved")
+        sched["refill_pops"] = sched["reserved"]
         return {"rays": s.rays, "node_visits": s.node_visits, "tri_tests": s.tri_tests,
                 "hits": s.hits, "launches": s.launches, "kernel_ms": s.kernel_ms, "accum_ms": s.accum_ms,
                 "render_period_ms": s.render_period_ms,
                 "cycles": {"refill": s.cycles_refill, "traverse": s.cycles_traverse,
                            "shade": s.cycles_shade, "total": s.cycles_total},
-                "sched": dict(zip(("node_steps", "node_lanes", "tri_steps", "tri_lanes", "shade_rounds",
-                                   "shade_lanes", "refill_rounds", "refill_lanes", "other_lanes",
-                                   "shade_wait", "free_wait", "reserved"), list(s.sched)))}
+                "sched": sched}
 
     def scene_prepares(self) -> tuple:
         """rtDiagScenePrepares: (full host-side scene preparations, device refits) since creation."""

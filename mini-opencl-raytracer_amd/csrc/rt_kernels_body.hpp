@@ -333,6 +333,9 @@ typedef float sv4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ sv4f lds_v4_at(uint32_t byte_addr) {
     return *reinterpret_cast<__attribute__((address_space(3))) const sv4f*>((size_t)byte_addr);
 }
+__device__ __forceinline__ uint32_t lds_u32_at(uint32_t byte_addr) {
+    return *reinterpret_cast<__attribute__((address_space(3))) const uint32_t*>((size_t)byte_addr);
+}
 __device__ __forceinline__ float lds_f32_at(uint32_t byte_addr) {
     return *reinterpret_cast<__attribute__((address_space(3))) const float*>((size_t)byte_addr);
 }
@@ -1174,6 +1177,7 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                      (uint32_t)(tid >> 6) * (fused ? kRingWaveBytes / 16u : kRingWaveBytesPf / 16u);
     float4* ring_i = ring_d + kRingSlots;
     uint32_t* ring_g = reinterpret_cast<uint32_t*>(ring_d + (fused ? 2u : 1u) * kRingSlots);
+    const uint32_t ring_b = (uint32_t)(size_t)(__attribute__((address_space(3))) float4*)ring_d;  // LDS byte address
     uint32_t rc_head = 0, rc_n = 0;  // wave-uniform: ring entries [rc_head, rc_head + rc_n)
     // The wave-uniform flags that steer the loops below (dry, chunk_tail, exhausted) are 32-bit
     // words fed from scalar sources only (ballots, kernel arguments, lane0): as `bool`s fed from a
@@ -1216,7 +1220,7 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
 #endif
     // diagnostic lane-utilisation counters (wave-uniform): steps / rounds and lanes served
     [[maybe_unused]] uint64_t u_nsteps = 0, u_nlanes = 0, u_tsteps = 0, u_tlanes = 0, u_srounds = 0, u_slanes = 0,
-             u_rrounds = 0, u_rlanes = 0, u_other = 0, u_shadew = 0, u_freew = 0, u_pad = 0;
+             u_rrounds = 0, u_rlanes = 0, u_other = 0, u_shadew = 0, u_freew = 0, u_pops = 0;
     // RT_LDS_CONFLICTS: modelled (ideal, actual) LDS cycles per read site -- [0,1] a node visit's A
     // read (its B read has the same addresses + a constant: the same cycles), [2..5] the A read if
     // the octant planes had strides 43, 48 instead, [6,7] a triangle test's 16-B reads (each),
@@ -1292,10 +1296,17 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                 }
                 if (state == kDone) state = kIdle;
             }
-            while (kRing && !exhausted) {
-                const unsigned long long idle = __ballot(state == kIdle);
-                if (idle == 0ull) break;
-                if (rc_n == 0u) {
+            // The refill is two parts, repeated by a loop with one exit at its bottom: a scalar loop
+            // that fills the empty ring (it changes the ring and the wave-uniform cursors, no lane's
+            // path state), then one straight-line predicated pop.  Written as one loop with the
+            // fill, the pop and three exits in it, the per-lane update sat inside a multi-exit loop
+            // and every live path variable was copied through a second register set on each
+            // iteration (profiles/r09/refill_isa.txt).  Same order of fills and pops as that loop:
+            // a fill whenever the ring is empty and a lane is idle, else a pop.
+            uint32_t n_idle = kRing ? popc_ballot(state == kIdle) : 0u;
+            if (kRing && n_idle != 0u) {
+              do {
+                while (rc_n == 0u && !exhausted) {
                     uint32_t unit = 0;  // the tile's first work item in the work order (wave-uniform)
                     if (!take_tile<kMode == 1>(a, steal, wave, (uint32_t)lane, total, chunk_base, chunk_len,
                                    chunk_tail, dry, unit)) {
@@ -1380,16 +1391,22 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                     }
                     rc_head = 0;
                     rc_n = (uint32_t)__popcll(vm);
-                    continue;
                 }
-                const uint32_t rank = lane_rank(idle);
-                const uint32_t take = min((uint32_t)__popcll(idle), rc_n);
+                // (`exhausted` is only ever set by a fill that found the ring empty and no tile to
+                // take, and nothing fills the ring afterwards: `exhausted` implies rc_n == 0.  So an
+                // empty ring here means `exhausted`: take is 0, no lane pops, and the loop ends.)
+                const uint32_t rank = lane_rank(__ballot(state == kIdle));
+                const uint32_t take = min(n_idle, rc_n);
+                if (kStats && take != 0u) ++u_pops;  // pop iterations (ring launches)
                 if (state == kIdle && rank < take) {
-                    const float4 e = ring_d[rc_head + rank];
-                    gid = ring_g[rc_head + rank];
+                    // (the slot's LDS byte addresses: ds_reads at one address plus constants, where
+                    // the indexed pointers cost two 64-bit multiply-adds)
+                    const uint32_t sb = ring_b + 16u * (rc_head + rank);
+                    const sv4f e = lds_v4_at(sb);
+                    gid = lds_u32_at(ring_b + 16u * (fused ? 2u : 1u) * kRingSlots + 4u * (rc_head + rank));
                     seed = __float_as_uint(e.w);
                     if (fused) {
-                        const float4 iv = ring_i[rc_head + rank];
+                        const sv4f iv = lds_v4_at(sb + 16u * kRingSlots);
                         ray.o = camPos;
                         ray.d = F3{e.x, e.y, e.z};
                         ray.inv = F3{iv.x, iv.y, iv.z};
@@ -1416,6 +1433,8 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                 }
                 rc_head += take;
                 rc_n -= take;
+                n_idle -= take;  // (every popped lane leaves IDLE: for TRAV, or DONE without bounces)
+              } while (n_idle != 0u && !exhausted);
             }
             while (!kRing && !exhausted) {
                 const unsigned long long idle = __ballot(state == kIdle);
@@ -1748,7 +1767,7 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
             atomicAdd(&a.stats[16], (unsigned long long)u_other);
             atomicAdd(&a.stats[17], (unsigned long long)u_shadew);
             atomicAdd(&a.stats[18], (unsigned long long)u_freew);
-            atomicAdd(&a.stats[19], (unsigned long long)u_pad);
+            atomicAdd(&a.stats[19], (unsigned long long)u_pops);
 #endif
 #endif  // RT_LDS_CONFLICTS
         }

@@ -41,7 +41,7 @@ for name in scheds:
               f"| lanes/step node {u['node_lanes']/max(1,u['node_steps']):.1f} ({u['node_steps']}) "
               f"tri {u['tri_lanes']/max(1,u['tri_steps']):.1f} ({u['tri_steps']}) "
               f"shade {u['shade_lanes']/max(1,u['shade_rounds']):.1f} ({u['shade_rounds']}) "
-              f"refill {u['refill_lanes']/max(1,u['refill_rounds']):.1f} ({u['refill_rounds']}) "
+              f"refill {u['refill_lanes']/max(1,u['refill_rounds']):.1f} ({u['refill_rounds']}, pops {u['refill_pops']}) "
               f"| per step: other {u['other_lanes']/max(1,u['node_steps']+u['tri_steps']):.1f} "
               f"shade-wait {u['shade_wait']/max(1,u['node_steps']+u['tri_steps']):.1f} "
               f"free {u['free_wait']/max(1,u['node_steps']+u['tri_steps']):.1f}")
