@@ -223,6 +223,22 @@ int rtKernelSetTiming(rt_kernel k, int enable);
 int rtKernelGetStats(rt_kernel k, rt_stats* out);
 int rtKernelResetStats(rt_kernel k);
 
+/* The path kill (step schedule).  A path whose throughput (the reference's `beta`) has become exactly
+ * (0, 0, 0) can add nothing but +-0 to its pixel; a launch that is certified -- the scene's materials,
+ * normals and vertices and the launch's lightType, skyboxIntensity and lightBounces pass a host rule
+ * under which no later segment can turn that into NaN -- ends such a path at once, as if its bounces
+ * had run out: the same bits, fewer segments.  Launches with stats on are never certified (the
+ * counters stay the reference's); they count the segments that reach shading with zero throughput
+ * instead, hits and misses apart (together: the segments a certified launch does not walk).
+ * scene_certified: the scene half of the rule for the kernel's math mode as of the last launch
+ * (0 also after rtRefitBVH, until the next full preparation); launch_certified: whether the last
+ * render launch carried the kill.  Synchronises like rtKernelGetStats. */
+typedef struct rt_path_kill_info {
+    uint64_t zero_hits, zero_misses;
+    int32_t scene_certified, launch_certified;
+} rt_path_kill_info;
+int rtKernelGetPathKill(rt_kernel k, rt_path_kill_info* out);
+
 /* ---- batched ray queries over caller rays ------------------------------------------------
  * The scene is the one bound to `k` (BUFFER_SCENE, BUFFER_NODE), packed and validated exactly as
  * a render launch does (rtValidateBVH first: RT_INVALID_MEM_OBJECT on a bad tree).  A query runs
@@ -779,7 +795,11 @@ int rtValidateBVH(const void* nodes, size_t n_nodes, size_t n_tris, int* depth);
  *   TRACE_REFILL_MIN, TRACE_SHADE_MIN path tracing over caller rays (rtEnqueueTracePaths): take records
  *                                     from the ring once this many lanes are free (1-64, default
  *                                     8), and shade once this many walks have ended
- *                                     (1-64, default 48, the step schedule's) */
+ *                                     (1-64, default 48, the step schedule's)
+ *   PATH_KILL                         step schedule: 1 (default) = a launch whose scene and arguments
+ *                                     pass the path-kill certificate ends a path once its throughput
+ *                                     is exactly zero (rtKernelGetPathKill); 0 = every segment is
+ *                                     walked.  Results never change. */
 enum rt_tuning {
     RT_TUNE_REFILL_MIN = 0,
     RT_TUNE_SHADE_MIN = 1,
@@ -808,7 +828,8 @@ enum rt_tuning {
     RT_TUNE_QUERY_REFILL_MIN = 26,
     /* 27: never assigned (RT_INVALID_VALUE) */
     RT_TUNE_TRACE_REFILL_MIN = 28,
-    RT_TUNE_TRACE_SHADE_MIN = 29
+    RT_TUNE_TRACE_SHADE_MIN = 29,
+    RT_TUNE_PATH_KILL = 30
 };
 int rtKernelSetTuning(rt_kernel k, int param, int value);
 int rtKernelGetTuning(rt_kernel k, int param, int* value);

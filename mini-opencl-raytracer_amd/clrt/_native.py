@@ -108,6 +108,8 @@ TUNING = {"refill_min": 0, "shade_min": 1, "refill_min_global": 2, "shade_min_gl
           "step_weight_leaf_global": 25, "query_refill_min": 26}
 # ... of rtEnqueueTracePaths (27 was never assigned)
 TRACE_TUNING = {"trace_refill_min": 28, "trace_shade_min": 29}
+# ... of the path kill (rtKernelGetPathKill): 1 = certified step launches drop paths of zero throughput
+PATH_KILL_TUNING = {"path_kill": 30}
 
 
 class Stats(ctypes.Structure):
@@ -118,6 +120,12 @@ class Stats(ctypes.Structure):
                 ("cycles_shade", ctypes.c_uint64), ("cycles_total", ctypes.c_uint64),
                 ("sched", ctypes.c_uint64 * 12), ("accum_ms", ctypes.c_double),
                 ("render_period_ms", ctypes.c_double)]
+
+
+class PathKillInfo(ctypes.Structure):
+    """rt_path_kill_info (rt_hip.h)."""
+    _fields_ = [("zero_hits", ctypes.c_uint64), ("zero_misses", ctypes.c_uint64),
+                ("scene_certified", ctypes.c_int32), ("launch_certified", ctypes.c_int32)]
 
 
 class TRACE_PARAMS(ctypes.Structure):
@@ -234,6 +242,7 @@ _HIP_PROTOS = {
     "rtKernelSetTiming": (ctypes.c_int, [_vp, ctypes.c_int]),
     "rtKernelGetStats": (ctypes.c_int, [_vp, ctypes.POINTER(Stats)]),
     "rtKernelResetStats": (ctypes.c_int, [_vp]),
+    "rtKernelGetPathKill": (ctypes.c_int, [_vp, ctypes.POINTER(PathKillInfo)]),
     "rtKernelGetSceneInLDS": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "rtKernelForceGlobalScene": (ctypes.c_int, [_vp, ctypes.c_int]),
     "rtBuildBVH": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint, _vp, ctypes.POINTER(ctypes.c_size_t)]),

@@ -16,7 +16,10 @@ from ._native import RTError, check, hip_lib
 
 
 def _tuning_id(name: str) -> int:
-    return N.TUNING[name] if name in N.TUNING else N.TRACE_TUNING[name]
+    for table in (N.TUNING, N.TRACE_TUNING):
+        if name in table:
+            return table[name]
+    return N.PATH_KILL_TUNING[name]
 
 
 class CLContext:
@@ -356,6 +359,15 @@ class CLKernel:
                 "cycles": {"refill": s.cycles_refill, "traverse": s.cycles_traverse,
                            "shade": s.cycles_shade, "total": s.cycles_total},
                 "sched": sched}
+
+    def path_kill(self) -> dict:
+        """rtKernelGetPathKill: the segments the stats launches shaded with zero throughput (hits, misses),
+        whether the scene passes the path-kill certificate, and whether the last render launch carried
+        the kill."""
+        s = N.PathKillInfo()
+        check(self._lib.rtKernelGetPathKill(self.handle, ctypes.byref(s)), "path kill")
+        return {"zero_hits": int(s.zero_hits), "zero_misses": int(s.zero_misses),
+                "scene_certified": bool(s.scene_certified), "launch_certified": bool(s.launch_certified)}
 
     def scene_prepares(self) -> tuple:
         """rtDiagScenePrepares: (full host-side scene preparations, device refits) since creation."""

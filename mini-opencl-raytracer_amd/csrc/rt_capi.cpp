@@ -81,6 +81,7 @@ struct rt_kernel_s {
     uint64_t launches = 0;
     uint64_t pf_waits = ~0ull;         // ctx->host_waits at the previous per-frame step launch
     bool last_lds = false;
+    bool last_kill = false;            // the last render launch carried the path kill (rtKernelGetPathKill)
     // the device resources, each with its own invariant (rt_device_scene.hpp, rt_kernel_state.hpp,
     // rt_internal.hpp, rt_kernels.hpp)
     rti::DeviceScene scene;  // the derived packed scene
@@ -471,6 +472,10 @@ static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, const LaunchArgs& la
     // the tiles that can see the scene, from this launch's own camera slots and the root bounds as they
     // are now (held frames share one argument copy, so one rectangle serves a fused launch)
     if (const float* rb = sc.root_bounds()) in.view = rtp::view_cull_rect(in.W, in.H, la.f3[0], la.f3[1], la.f3[2], rb, rb + 3);
+    // the path kill: the scene's cached certificate for this math's material table, and the launch's own
+    // arguments for the plan's half of it
+    in.kill_scene_ok = sc.path_kill_ok(k->math == RT_MATH_SHIPPED);
+    in.light_type = la.light_type(), in.skybox_intensity = la.skybox_intensity();
     return in;
 }
 
@@ -498,6 +503,7 @@ static void fill_args(rt_kernel k, const LaunchArgs& la, uint32_t first_frame, c
     a.rowBegin = p.rowBegin, a.rowCount = p.rowCount, a.tilesX = p.tilesX, a.nTiles = p.nTiles;
     a.bandPeriod = p.bandPeriod, a.bandPhase = p.bandPhase;
     a.visTx0 = p.visTx0, a.visTy0 = p.visTy0, a.visW = p.visW, a.visH = p.visH, a.visTiles = p.visTiles;
+    a.pathKill = p.pathKill;
     a.chunkPixels = p.chunkPixels, a.tailChunk = p.tailChunk, a.chunkSplit = p.chunkSplit, a.tailBase = p.tailBase;
     a.staticFirst = p.staticFirst, a.nParts = p.nParts, a.partLen = p.partLen;
     a.refillMin = p.refillMin, a.shadeMin = p.shadeMin;
@@ -635,6 +641,7 @@ static int enqueue(rt_context ctx, rt_kernel k, const LaunchArgs& args, size_t g
     // overlapped) goes to rstr: the main stream unless a render stream was taken above
     if (rstr == ctx->stream) ctx->mdirty = true;
     k->last_lds = v.lds();
+    k->last_kill = p.pathKill != 0u;
 
     // 7. wavefront: the ray queues
     rtk::WfArgs wa{};
@@ -1469,6 +1476,23 @@ int rtKernelGetStats(rt_kernel k, rt_stats* out) {
     out->kernel_ms = k->timer.kernel_ms();
     out->accum_ms = k->timer.accum_ms();
     out->render_period_ms = k->timer.render_period_ms();
+    return RT_SUCCESS;
+}
+
+int rtKernelGetPathKill(rt_kernel k, rt_path_kill_info* out) {
+    if (!k || !out) return RT_INVALID_VALUE;
+    flush_kernel(k);
+    int rc = ensure_device(k->ctx);
+    if (rc) return rc;
+    unsigned long long h[2] = {};
+    hipError_t e = hipMemcpyAsync(h, k->counters.stats() + rti::WorkCounters::kZeroBetaWord, sizeof(h),
+                                  hipMemcpyDeviceToHost, qs(k->ctx));
+    if (e == hipSuccess) e = hipStreamSynchronize(qs(k->ctx));
+    if (e != hipSuccess) return map_hip(e);
+    out->zero_hits = h[0];
+    out->zero_misses = h[1];
+    out->scene_certified = k->scene.path_kill_ok(k->math == RT_MATH_SHIPPED) ? 1 : 0;
+    out->launch_certified = k->last_kill ? 1 : 0;
     return RT_SUCCESS;
 }
 

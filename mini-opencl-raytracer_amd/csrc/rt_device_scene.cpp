@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "rt_kernels.hpp"
+#include "rt_path_kill.hpp"
 #include "rt_refit.hpp"
 #include "rt_scene_pack.hpp"
 
@@ -101,6 +102,19 @@ int DeviceScene::prepare(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
                             root.bounds.pmax.x, root.bounds.pmax.y, root.bounds.pmax.z};
         std::memcpy(root_bounds_, b, sizeof(b));
     }
+    // the path-kill certificate, on the material records as the device just formed them (both tables)
+    kill_known_ = false;
+    if (mm && p.n_mats > 0) {
+        std::vector<float> recs((size_t)p.n_mats * 32);
+        e = hipMemcpyAsync(recs.data(), shade_mats_, recs.size() * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return map_hip(e);
+        const rt_cl_triangle* ht = reinterpret_cast<const rt_cl_triangle*>(in.tris);
+        for (int t = 0; t < 2; ++t)
+            kill_ok_[t] = rtp::path_kill_scene_ok(recs.data() + (size_t)t * 16 * p.n_mats, p.n_mats, ht, p.n_tris,
+                                                  root_bounds());
+        kill_known_ = true;
+    }
     for_tris_ = tm, tris_gen_ = tm->generation, tris_struct_ = tm->structural;
     for_nodes_ = nm, nodes_gen_ = nm->generation, nodes_struct_ = nm->structural;
     for_mats_ = mm, mats_gen_ = mm ? mm->generation : 0;
@@ -130,6 +144,7 @@ int DeviceScene::refit(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     a.goct_b = goct_b_, a.goct_group = RT_GOCT_GROUP ? RT_GOCT_GROUP : 1;
     a.g_nodes = g_nodes_;
     root_known_ = false;  // the refit moves the root's bounds on the device
+    kill_known_ = false;  // ... and reads vertices and normals the host has not seen
     hipStream_t st = qs(ctx);
     hipError_t e = rtr::launch_refit(a, st);
     // the triangle and shading records from the moved vertices; materials stay as packed

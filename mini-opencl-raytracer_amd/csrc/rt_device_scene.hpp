@@ -48,6 +48,11 @@ public:
     // preparation, so a launch after a vertex or node write sees the new ones.  Null after a device
     // refit, which moves them without the host looking: such launches do without the view cull.
     const float* root_bounds() const { return root_known_ ? root_bounds_ : nullptr; }
+    // The path-kill certificate's scene half (rt_path_kill.hpp) for the material table of `shipped`
+    // math or the IEEE one, evaluated at every full preparation with materials.  False where it was
+    // refused and where it is unknown: after a device refit, which moves vertices and normals without
+    // the host looking, like root_bounds().
+    bool path_kill_ok(bool shipped) const { return kill_known_ && kill_ok_[shipped ? 1 : 0]; }
     // rtDiagScenePrepares
     uint64_t full_prepares() const { return full_prepares_; }
     uint64_t refits() const { return refits_; }
@@ -76,6 +81,8 @@ private:
     bool oct_ok_ = false;
     bool root_known_ = false;
     float root_bounds_[6] = {};
+    bool kill_known_ = false;
+    bool kill_ok_[2] = {false, false};  // [0] the IEEE material table, [1] the shipped policy's
     uint64_t full_prepares_ = 0, refits_ = 0;
     // device records and their capacities (float4s)
     float4 *packed_tris_ = nullptr, *shade_tris_ = nullptr, *shade_mats_ = nullptr;

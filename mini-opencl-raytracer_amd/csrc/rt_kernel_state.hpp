@@ -129,7 +129,10 @@ private:
 // in turn.
 class WorkCounters {
 public:
-    static constexpr int kStatWords = 20;  // rt_stats counters kept on the device
+    // rt_stats counters kept on the device, then rt_path_kill_info's two (step_body: segments shaded
+    // with zero throughput, hits and misses)
+    static constexpr int kStatWords = 22;
+    static constexpr int kZeroBetaWord = 20;
 
     // allocated and zeroed through `st`, which is synchronised
     hipError_t create(hipStream_t st);

@@ -74,6 +74,9 @@ struct KernelArgs {
     // Without a cull: (0, 0, tilesX, tile rows, nTiles).  radStride, the flag words and the
     // accumulation's grid stay in the full grid's numbering.
     uint32_t visTx0, visTy0, visW, visH, visTiles;
+    // the path kill (rt_path_kill.hpp; step launches without stats): 1 = the launch is certified, and a
+    // path whose beta is (+-0, +-0, +-0) after a bounce ends there as if its bounces had run out
+    uint32_t pathKill;
 };
 
 using KernelFn = void (*)(KernelArgs);

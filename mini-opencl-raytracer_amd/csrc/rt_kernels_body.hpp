@@ -1187,7 +1187,12 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
     uint32_t dry = 0u;               // wave-uniform: the work counter is exhausted
     const uint32_t wave = __builtin_amdgcn_readfirstlane((uint32_t)tid >> 6);  // wave in the workgroup
 
+    // the path kill's switch as a word OR-ed into the test of beta's bits (0: the launch is certified) --
+    // a 32-bit scalar, where a `bool` tested beside the lanes' compare lived in a 64-bit lane mask
+    [[maybe_unused]] const uint32_t kill_off = a.pathKill != 0u ? 0u : 1u;
     LaneStats st;
+    // (stats variant) segments that reach shading with beta already (+-0, +-0, +-0): hits, misses
+    [[maybe_unused]] uint32_t zero_hit = 0, zero_miss = 0;
     uint32_t state = kIdle;
     uint32_t gid = 0, seed = 0, bounce = 0;
     Ray ray{};
@@ -1707,8 +1712,17 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                     a.hitT[gid - (fused ? last : 0u)] = h.t;
                 }
             }
-            const bool more = shade_bounce<M, kStats, kGlobalOct>(h, ray, radiance, beta, seed, sc, a, st);
+            // the three components' bits: zero iff beta is (+-0, +-0, +-0) -- no NaN, no denormal
+            if (kStats && ((__float_as_uint(beta.x) | __float_as_uint(beta.y) | __float_as_uint(beta.z)) << 1) == 0u)
+                ++(h.prim < 0 ? zero_miss : zero_hit);
+            bool more = shade_bounce<M, kStats, kGlobalOct>(h, ray, radiance, beta, seed, sc, a, st);
             ++bounce;
+            // The path kill (rt_path_kill.cpp): in a certified launch (a.pathKill, wave-uniform; never with
+            // stats) a path that goes on with zero throughput can add nothing but +-0 to its pixel and
+            // ends here as one out of bounces does -- the same bits.
+            if (RT_PATH_KILL && !kStats &&
+                (((__float_as_uint(beta.x) | __float_as_uint(beta.y) | __float_as_uint(beta.z)) << 1) | kill_off) == 0u)
+                more = false;
             if (!more || bounce >= bounces) {
                 radiance = F3{M::max(radiance.x, 0.0f), M::max(radiance.y, 0.0f), M::max(radiance.z, 0.0f)};
                 state = kDone;
@@ -1725,7 +1739,10 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
     finish_queued<M>(a, fq, fq_n, lane);
     if (kStats) {
         flush_stats(a, st, lane);
+        const unsigned long long zh = wave_sum(zero_hit), zm = wave_sum(zero_miss);
         if (lane == 0) {
+            atomicAdd(&a.stats[20], zh);  // rt_path_kill_info (WorkCounters::kZeroBetaWord)
+            atomicAdd(&a.stats[21], zm);
             atomicAdd(&a.stats[4], (unsigned long long)cyc_refill);
             atomicAdd(&a.stats[5], (unsigned long long)cyc_trav);
             atomicAdd(&a.stats[6], (unsigned long long)cyc_shade);

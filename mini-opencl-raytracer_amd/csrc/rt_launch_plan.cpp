@@ -107,6 +107,13 @@ int plan_shape(const PlanIn& in, LaunchPlan* out) {
             a.visTiles = a.visW * a.visH;
         }
     }
+    // The path kill: a step launch ends a path once its throughput is exactly zero -- exact when both
+    // halves of the certificate hold (rt_path_kill.cpp).  Not with stats: the counters are the
+    // reference's, every segment walked.
+    a.pathKill = RT_PATH_KILL && in.tune.path_kill && si == rtk::kSchedStep && !in.stats && in.kill_scene_ok &&
+                         path_kill_launch_ok(in.light_type, in.skybox_intensity, in.light_bounces)
+                     ? 1u
+                     : 0u;
     a.radStride = (uint32_t)g1;
     if (fused) {
         // fused frames: radiance slots indexed by global work-item id (the lane packs

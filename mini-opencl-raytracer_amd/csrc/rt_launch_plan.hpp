@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "rt_layout.hpp"
+#include "rt_path_kill.hpp"
 #include "rt_tuning.hpp"
 #include "rt_view_cull.hpp"
 
@@ -33,6 +34,11 @@ struct PlanIn {
     Tuning tune;                            // rtKernelSetTuning
     int num_cus;
     ViewRect view;                          // tiles that can see the scene (rt_view_cull.hpp); zero: all
+    // the path kill (rt_path_kill.hpp): the scene half of its certificate as the packed scene caches it
+    // for this launch's math, and the launch arguments its other half reads
+    bool kill_scene_ok;
+    int32_t light_type;
+    float skybox_intensity;
 };
 
 struct LaunchPlan {
@@ -56,6 +62,7 @@ struct LaunchPlan {
     // the tiles the hand-out covers: visW x visH of them from (visTx0, visTy0) of this launch's tile
     // grid -- all of it (0, 0, tilesX, tilesY) unless the view cull applies; visTiles = visW * visH
     uint32_t visTx0, visTy0, visW, visH, visTiles;
+    uint32_t pathKill;                      // 1: the launch is certified to drop paths of zero throughput
     // ---- plan_handout ----
     uint64_t grid;
     uint32_t tileMajor, chunkPixels, tailChunk, chunkSplit, tailBase, staticFirst, nParts, partLen;

@@ -37,6 +37,12 @@ constexpr uint32_t kEndWalk = 0xff000000u;
 #define RT_VIEW_CULL 1
 #endif
 
+// the path kill (rt_path_kill.hpp): certified step launches end a path whose throughput has reached
+// exactly zero instead of walking its remaining segments (0: every segment is walked, for A/B builds)
+#ifndef RT_PATH_KILL
+#define RT_PATH_KILL 1
+#endif
+
 // LDS node records of trees with at most kOctBMaxStride records per plane keep their B planes at
 // the fixed float4 offset kOctB, so a node step reads B with an immediate offset from A's address
 constexpr uint32_t kOctBMaxStride = 64;

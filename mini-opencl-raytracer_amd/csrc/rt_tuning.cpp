@@ -43,6 +43,7 @@ constexpr Knob kKnobs[] = {
     {RT_TUNE_QUERY_REFILL_MIN, &Tuning::query_refill_min, nullptr, 1, 64, 1},
     {RT_TUNE_TRACE_REFILL_MIN, &Tuning::trace_refill_min, nullptr, 1, 64, 1},
     {RT_TUNE_TRACE_SHADE_MIN, &Tuning::trace_shade_min, nullptr, 1, 64, 1},
+    {RT_TUNE_PATH_KILL, nullptr, &Tuning::path_kill, 0, 1, 1},
 };
 
 const Knob* find(int param) {

@@ -45,6 +45,9 @@ struct Tuning {
     // lanes against the query's 32 (Cornell 2.17 -> 1.81 ms, bunny proxy 2.57 -> 2.54 ms); shading keeps
     // the step schedule's 48 (32 is 2 % faster on Cornell, 5 % slower on the proxy) -- profiles/trace/
     uint32_t trace_refill_min = 8, trace_shade_min = 48;
+    // RT_TUNE_PATH_KILL: certified step launches drop paths of zero throughput (rt_path_kill.hpp);
+    // 0 walks every segment -- same bits either way
+    int path_kill = 1;
 };
 
 // RT_SUCCESS, or RT_INVALID_VALUE for an id the table does not hold (the retired ones and

@@ -45,4 +45,9 @@ for name in scheds:
               f"| per step: other {u['other_lanes']/max(1,u['node_steps']+u['tri_steps']):.1f} "
               f"shade-wait {u['shade_wait']/max(1,u['node_steps']+u['tri_steps']):.1f} "
               f"free {u['free_wait']/max(1,u['node_steps']+u['tri_steps']):.1f}")
+        # segments shaded with zero throughput (rtKernelGetPathKill): what a certified launch does not walk
+        z = r.k.path_kill()
+        zero = z["zero_hits"] + z["zero_misses"]
+        print(f"  zero-throughput segments: hits {z['zero_hits']} misses {z['zero_misses']} = {zero} "
+              f"({zero/max(1,s['rays']):.4f} of rays), scene certified: {z['scene_certified']}")
         r.close()
