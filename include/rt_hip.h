@@ -239,6 +239,23 @@ typedef struct rt_path_kill_info {
 } rt_path_kill_info;
 int rtKernelGetPathKill(rt_kernel k, rt_path_kill_info* out);
 
+/* The node collapse (octant-record walks: every schedule on LDS-resident scenes, and the HBM/L2 walk of
+ * the regrouped records).  Where a node's near child is interior and has bitwise the node's own box,
+ * the child's box test repeats the one just passed; the packed scene keeps a second set of records
+ * whose links lead past such children, and launches walk it: the same leaves and triangles in the same
+ * order, the same results, fewer node visits.  Launches with stats on walk the plain records (the
+ * counters stay the reference's), and so does every launch after rtRefitBVH until the next full
+ * preparation, since the refit moves boxes and no links.
+ * collapsed_links: link words the second set changes (0: the scene has no such pair);
+ * scene_collapsible: the set may be walked as of the last preparation (0 after rtRefitBVH, and in builds
+ * with RT_NODE_COLLAPSE=0); launch_collapsed: whether the kernel's last launch -- render, ray query or
+ * path trace -- walked it.  Flushes coalesced frames; does not wait for the device. */
+typedef struct rt_node_collapse_info {
+    uint32_t collapsed_links;
+    int32_t scene_collapsible, launch_collapsed;
+} rt_node_collapse_info;
+int rtKernelGetNodeCollapse(rt_kernel k, rt_node_collapse_info* out);
+
 /* ---- batched ray queries over caller rays ------------------------------------------------
  * The scene is the one bound to `k` (BUFFER_SCENE, BUFFER_NODE), packed and validated exactly as
  * a render launch does (rtValidateBVH first: RT_INVALID_MEM_OBJECT on a bad tree).  A query runs

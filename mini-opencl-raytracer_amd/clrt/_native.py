@@ -128,6 +128,12 @@ class PathKillInfo(ctypes.Structure):
                 ("scene_certified", ctypes.c_int32), ("launch_certified", ctypes.c_int32)]
 
 
+class NodeCollapseInfo(ctypes.Structure):
+    """rt_node_collapse_info (rt_hip.h)."""
+    _fields_ = [("collapsed_links", ctypes.c_uint32), ("scene_collapsible", ctypes.c_int32),
+                ("launch_collapsed", ctypes.c_int32)]
+
+
 class TRACE_PARAMS(ctypes.Structure):
     """rt_trace_params (rt_hip.h): rtEnqueueTracePaths' seed base (used without a seed buffer) and the
     encoding of the radiance it writes."""
@@ -243,6 +249,7 @@ _HIP_PROTOS = {
     "rtKernelGetStats": (ctypes.c_int, [_vp, ctypes.POINTER(Stats)]),
     "rtKernelResetStats": (ctypes.c_int, [_vp]),
     "rtKernelGetPathKill": (ctypes.c_int, [_vp, ctypes.POINTER(PathKillInfo)]),
+    "rtKernelGetNodeCollapse": (ctypes.c_int, [_vp, ctypes.POINTER(NodeCollapseInfo)]),
     "rtKernelGetSceneInLDS": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "rtKernelForceGlobalScene": (ctypes.c_int, [_vp, ctypes.c_int]),
     "rtBuildBVH": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint, _vp, ctypes.POINTER(ctypes.c_size_t)]),

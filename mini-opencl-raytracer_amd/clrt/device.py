@@ -369,6 +369,14 @@ class CLKernel:
         return {"zero_hits": int(s.zero_hits), "zero_misses": int(s.zero_misses),
                 "scene_certified": bool(s.scene_certified), "launch_certified": bool(s.launch_certified)}
 
+    def node_collapse(self) -> dict:
+        """rtKernelGetNodeCollapse: the link words the scene's collapsed record set changes, whether the
+        set may be walked (not after a device refit), and whether the last launch walked it."""
+        s = N.NodeCollapseInfo()
+        check(self._lib.rtKernelGetNodeCollapse(self.handle, ctypes.byref(s)), "node collapse")
+        return {"collapsed_links": int(s.collapsed_links), "scene_collapsible": bool(s.scene_collapsible),
+                "launch_collapsed": bool(s.launch_collapsed)}
+
     def scene_prepares(self) -> tuple:
         """rtDiagScenePrepares: (full host-side scene preparations, device refits) since creation."""
         full, refits = ctypes.c_uint64(), ctypes.c_uint64()

@@ -60,6 +60,12 @@ constexpr uint64_t kKnownFlags =
 // diagnostic timeline builds (-DRT_TIMELINE=1, scripts/timeline.py) write three 64-bin histograms after
 // the primary hit ids: such a build requires hit buffers that long
 constexpr size_t kHitPad = RT_TIMELINE ? 192 : 0;
+// diagnostic count builds (-DRT_NODE_COLLAPSE_STATS=1): stats launches walk the collapsed links too, so
+// their node_visits against the default build's is the exact number of visits the collapse removes
+// (the other counters stay; such a build's visits are not the reference's)
+#ifndef RT_NODE_COLLAPSE_STATS
+#define RT_NODE_COLLAPSE_STATS 0
+#endif
 
 }  // namespace
 
@@ -82,6 +88,7 @@ struct rt_kernel_s {
     uint64_t pf_waits = ~0ull;         // ctx->host_waits at the previous per-frame step launch
     bool last_lds = false;
     bool last_kill = false;            // the last render launch carried the path kill (rtKernelGetPathKill)
+    bool last_collapsed = false;       // the last launch walked the collapsed links (rtKernelGetNodeCollapse)
     // the device resources, each with its own invariant (rt_device_scene.hpp, rt_kernel_state.hpp,
     // rt_internal.hpp, rt_kernels.hpp)
     rti::DeviceScene scene;  // the derived packed scene
@@ -479,6 +486,18 @@ static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, const LaunchArgs& la
     return in;
 }
 
+// The octant records a launch of walk `w` reads: the collapsed link set (rt_scene_pack.cpp,
+// collapse_oct_links) unless the launch reports traversal counters -- a stats launch's visits stay the
+// reference's -- or the scene's boxes were moved by a device refit since they were packed.  The kernels
+// are the same either way: only this pointer differs.  Remembers the choice for rtKernelGetNodeCollapse.
+static const float4* oct_records(rt_kernel k, rtk::Walk w, bool regrouped) {
+    const rti::DeviceScene& sc = k->scene;
+    const bool collapsed = sc.collapse_ok() && (!k->stats || RT_NODE_COLLAPSE_STATS);
+    k->last_collapsed = collapsed && w != rtk::Walk::GlobalNodes;
+    if (collapsed) return regrouped ? sc.goct_collapsed() : sc.oct_nodes_collapsed();
+    return regrouped ? sc.goct() : sc.oct_nodes();
+}
+
 // KernelEntry's arguments: the plan's scalars plus the kernel's pointers (the radiance set and the
 // work counters follow, once their resources are there)
 static void fill_args(rt_kernel k, const LaunchArgs& la, uint32_t first_frame, const rtp::LaunchPlan& p,
@@ -490,7 +509,7 @@ static void fill_args(rt_kernel k, const LaunchArgs& la, uint32_t first_frame, c
     a.materials = static_cast<const rt_cl_material*>(la.materials()->dptr);
     const rti::DeviceScene& sc = k->scene;
     a.packedTris = sc.packed_tris();
-    a.octNodes = p.regrouped ? sc.goct() : sc.oct_nodes();
+    a.octNodes = oct_records(k, p.variant.walk, p.regrouped);
     a.gNodes = sc.g_nodes();
     a.shadeTris = sc.shade_tris();
     a.shadeMats = sc.shade_mats() + (k->math == RT_MATH_SHIPPED ? 4 * (size_t)sc.n_mats() : 0);
@@ -716,7 +735,7 @@ static void fill_query_args(rt_kernel k, const rtp::QueryPlan& p, const float4* 
     rtk::KernelArgs& a = *args;
     std::memset(&a, 0, sizeof(a));
     a.packedTris = k->scene.packed_tris();
-    a.octNodes = p.regrouped ? k->scene.goct() : k->scene.oct_nodes();
+    a.octNodes = oct_records(k, p.variant.walk, p.regrouped);
     a.nTris = k->scene.n_tris();
     a.nNodes = p.nNodes, a.octStride = p.octStride, a.octB = p.octB, a.octRecords = p.octRecords;
     a.stepWeightNode = p.stepWeightNode, a.stepWeightLeaf = p.stepWeightLeaf;
@@ -783,7 +802,7 @@ static void fill_trace_args(rt_kernel k, const rtp::TracePlan& p, rtk::KernelArg
     std::memset(&a, 0, sizeof(a));
     const rti::DeviceScene& sc = k->scene;
     a.packedTris = sc.packed_tris();
-    a.octNodes = p.regrouped ? sc.goct() : sc.oct_nodes();
+    a.octNodes = oct_records(k, p.variant.walk, p.regrouped);
     a.shadeTris = sc.shade_tris();
     a.shadeMats = sc.shade_mats() + (k->math == RT_MATH_SHIPPED ? 4 * (size_t)sc.n_mats() : 0);
     a.nTris = sc.n_tris(), a.nMats = sc.n_mats();
@@ -1493,6 +1512,15 @@ int rtKernelGetPathKill(rt_kernel k, rt_path_kill_info* out) {
     out->zero_misses = h[1];
     out->scene_certified = k->scene.path_kill_ok(k->math == RT_MATH_SHIPPED) ? 1 : 0;
     out->launch_certified = k->last_kill ? 1 : 0;
+    return RT_SUCCESS;
+}
+
+int rtKernelGetNodeCollapse(rt_kernel k, rt_node_collapse_info* out) {
+    if (!k || !out) return RT_INVALID_VALUE;
+    flush_kernel(k);
+    out->collapsed_links = k->scene.collapsed_links();
+    out->scene_collapsible = k->scene.collapse_ok() ? 1 : 0;
+    out->launch_collapsed = k->last_collapsed ? 1 : 0;
     return RT_SUCCESS;
 }
 

@@ -47,12 +47,14 @@ hipError_t upload(void* dst, const std::vector<uint32_t>& src, hipStream_t st) {
 
 }  // namespace
 
-int DeviceScene::allocate(uint32_t nn, uint32_t nt, uint32_t nmat, size_t goct_words) {
+int DeviceScene::allocate(uint32_t nn, uint32_t nt, uint32_t nmat, size_t goct_words, bool collapsed) {
     int rc = ensure_dev(g_nodes_, g_nodes_cap_, (size_t)nn * 4);
     if (!rc) rc = ensure_dev(refit_links_, refit_links_cap_, (size_t)nn * 2);
     if (!rc) rc = ensure_dev(refit_arrivals_, refit_arrivals_cap_, (size_t)nn);
     if (!rc) rc = ensure_dev(oct_nodes_, oct_nodes_cap_, (size_t)rtp::oct_records(nn));
     if (!rc) rc = ensure_dev(goct_nodes_, goct_nodes_cap_, goct_words / 4);
+    if (!rc && collapsed) rc = ensure_dev(oct_collapsed_, oct_collapsed_cap_, (size_t)rtp::oct_records(nn));
+    if (!rc && collapsed) rc = ensure_dev(goct_collapsed_, goct_collapsed_cap_, goct_words / 4);
     if (!rc) rc = ensure_dev(packed_tris_, packed_tris_cap_, (size_t)nt * 3);
     if (!rc) rc = ensure_dev(shade_tris_, shade_tris_cap_, (size_t)nt * 3);
     // two material tables: IEEE divisions (pinned, devicelib), then the shipped policy's
@@ -78,13 +80,15 @@ int DeviceScene::prepare(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     if (rc) return rc;
     // the device half: from here on the records are no longer those of the scene remembered
     invalidate();
-    rc = allocate(p.n_nodes, p.n_tris, p.n_mats, p.goct_nodes.size());
+    rc = allocate(p.n_nodes, p.n_tris, p.n_mats, p.goct_nodes.size(), p.collapsed_links != 0);
     if (rc) return rc;
     hipStream_t st = qs(ctx);
     hipError_t e = upload(g_nodes_, p.global_nodes, st);
     if (e == hipSuccess) e = upload(refit_links_, p.refit_links, st);
     if (e == hipSuccess) e = upload(oct_nodes_, p.oct_nodes, st);
     if (e == hipSuccess && !p.goct_nodes.empty()) e = upload(goct_nodes_, p.goct_nodes, st);
+    if (e == hipSuccess && p.collapsed_links) e = upload(oct_collapsed_, p.oct_nodes_collapsed, st);
+    if (e == hipSuccess && !p.goct_nodes_collapsed.empty()) e = upload(goct_collapsed_, p.goct_nodes_collapsed, st);
     if (e == hipSuccess)
         e = rtk::launch_pack(static_cast<const rt_cl_triangle*>(tm->dptr), p.n_tris, packed_tris_, shade_tris_,
                              mm ? static_cast<const rt_cl_material*>(mm->dptr) : nullptr, p.n_mats, shade_mats_, st);
@@ -94,6 +98,7 @@ int DeviceScene::prepare(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     if (e != hipSuccess) return map_hip(e);
     n_nodes_ = p.n_nodes, n_tris_ = p.n_tris, n_mats_ = p.n_mats, n_top_ = p.n_top;
     oct_ok_ = p.oct_ok, goct_b_ = p.goct_b;
+    collapsed_links_ = p.collapsed_links, collapse_known_ = RT_NODE_COLLAPSE != 0;
     root_known_ = p.n_nodes > 0 && in.nodes_size >= sizeof(rt_cl_bvh_node);
     if (root_known_) {
         rt_cl_bvh_node root;
@@ -144,6 +149,7 @@ int DeviceScene::refit(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     a.goct_b = goct_b_, a.goct_group = RT_GOCT_GROUP ? RT_GOCT_GROUP : 1;
     a.g_nodes = g_nodes_;
     root_known_ = false;  // the refit moves the root's bounds on the device
+    collapse_known_ = false;  // ... and every box, in the plain records only: equal boxes may now differ
     kill_known_ = false;  // ... and reads vertices and normals the host has not seen
     hipStream_t st = qs(ctx);
     hipError_t e = rtr::launch_refit(a, st);
@@ -162,7 +168,8 @@ int DeviceScene::refit(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
 
 void DeviceScene::release() {
     for (void* p : {(void*)packed_tris_, (void*)shade_tris_, (void*)shade_mats_, (void*)oct_nodes_, (void*)goct_nodes_,
-                    (void*)g_nodes_, (void*)refit_links_, (void*)refit_arrivals_})
+                    (void*)oct_collapsed_, (void*)goct_collapsed_, (void*)g_nodes_, (void*)refit_links_,
+                    (void*)refit_arrivals_})
         if (p) (void)hipFree(p);
     *this = DeviceScene();
 }

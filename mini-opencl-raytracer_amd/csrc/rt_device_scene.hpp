@@ -44,6 +44,17 @@ public:
     const float4* g_nodes() const { return g_nodes_; }        // 64-B node records, top of the tree first
     // regrouped octant records for the HBM/L2 walk (RT_GOCT_GROUP), null when this scene has none
     const float4* goct() const { return goct_b_ ? goct_nodes_ : nullptr; }
+    // The collapsed link set (rtp::collapse_oct_links): the same records with the octant walk's links
+    // past near children whose box is bitwise their parent's.  collapse_ok(): the set may be walked --
+    // the boxes are as the host packed them.  False after a device refit, which rewrites planes and no
+    // links and leaves the equality unknown, like root_bounds(), until the next full preparation; false
+    // throughout in a build with RT_NODE_COLLAPSE=0.  A launch that reports traversal counters walks
+    // the plain set whatever this says.  The two accessors return the plain records where the set
+    // changes no link word.
+    bool collapse_ok() const { return collapse_known_; }
+    uint32_t collapsed_links() const { return collapsed_links_; }  // link words the set changes
+    const float4* oct_nodes_collapsed() const { return collapsed_links_ ? oct_collapsed_ : oct_nodes_; }
+    const float4* goct_collapsed() const { return collapsed_links_ && goct_b_ ? goct_collapsed_ : goct(); }
     // The root node's bounds (nodes[0]: min xyz, max xyz) as the host last saw them: read at every full
     // preparation, so a launch after a vertex or node write sees the new ones.  Null after a device
     // refit, which moves them without the host looking: such launches do without the view cull.
@@ -70,7 +81,7 @@ private:
         return for_tris_ == tris && for_nodes_ == nodes && tris_struct_ == tris->structural &&
                nodes_struct_ == nodes->structural;
     }
-    int allocate(uint32_t n_nodes, uint32_t n_tris, uint32_t n_mats, size_t goct_words);
+    int allocate(uint32_t n_nodes, uint32_t n_tris, uint32_t n_mats, size_t goct_words, bool collapsed);
 
     // provenance: the buffers packed from, their generations then, their structural generations at
     // the last full preparation
@@ -81,6 +92,8 @@ private:
     bool oct_ok_ = false;
     bool root_known_ = false;
     float root_bounds_[6] = {};
+    bool collapse_known_ = false;
+    uint32_t collapsed_links_ = 0;
     bool kill_known_ = false;
     bool kill_ok_[2] = {false, false};  // [0] the IEEE material table, [1] the shipped policy's
     uint64_t full_prepares_ = 0, refits_ = 0;
@@ -89,6 +102,9 @@ private:
     float4 *oct_nodes_ = nullptr, *goct_nodes_ = nullptr, *g_nodes_ = nullptr;
     size_t packed_tris_cap_ = 0, shade_tris_cap_ = 0, shade_mats_cap_ = 0;
     size_t oct_nodes_cap_ = 0, goct_nodes_cap_ = 0, g_nodes_cap_ = 0;
+    // the collapsed copies of the two octant layouts (allocated for scenes whose set changes a link)
+    float4 *oct_collapsed_ = nullptr, *goct_collapsed_ = nullptr;
+    size_t oct_collapsed_cap_ = 0, goct_collapsed_cap_ = 0;
     // device refit: node -> parent, then node -> g_nodes record (n_nodes words each), uploaded by the
     // full preparation; the climb's arrival counters
     uint32_t *refit_links_ = nullptr, *refit_arrivals_ = nullptr;

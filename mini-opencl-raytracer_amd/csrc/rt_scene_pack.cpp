@@ -145,6 +145,64 @@ bool build_oct_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uin
     return ok;
 }
 
+// The collapsed link set: a copy of build_oct_nodes' records `oct` (n nodes, every leaf inline: the
+// caller passes records whose build returned true) that differs only in hit_next words of interior
+// records, and the number of words it changes.  For node i and octant o the plain hit_next is the near
+// child c.  While c is interior and its box is bitwise i's, the link moves on to c's own near child
+// under o; the chain ends at the first node whose box differs, or at a leaf.
+//
+// Why a walk over these links computes what the plain walk computes.  A walk that follows i's hit_next
+// has just passed i's box test for its ray and its current t.  Its next step is c's box test: no
+// triangle is tested between the two node steps, so t is the same word, and the ray is the same ray.
+// The test reads the six planes the record holds for the ray's octant; when c's six words equal i's it
+// is the same arithmetic on the same operands as the test just passed -- comparisons against t and NaN
+// slabs of axis-aligned rays included, whatever their outcome rule -- so it passes, every time, and the
+// plain walk goes on to c's hit_next.  Going there at once leaves out a step whose result was known
+// when the scene was packed, and nothing else: c's miss_next is never taken (its test cannot fail), and
+// the nodes below c keep their own records, whose miss_next words already lead to c's far child and
+// from there out of c's subtree.  By induction over the chain, every leaf entered, every triangle
+// tested and the final {t, prim} are the plain walk's, in its order; only the visit count is smaller,
+// by one per skipped node per passage.  That holds for closest-hit and any-hit walks alike, which differ
+// in what a triangle step does, not in the node steps.
+//   * Words are compared as uint32_t.  +0.0 and -0.0 planes differ as words and do not collapse:
+//     (plane - o) * invDir may differ in sign or be NaN for one and not the other, and the argument
+//     above needs the same operands, not equal values.  (Two NaN planes with the same word would
+//     collapse, rightly: the same operands again.)
+//   * For one octant the near/far selection is the same for i and c, so comparing the record's six
+//     plane words under o is comparing pmin and pmax, all six words.
+//   * A leaf is never skipped, identical box or not: on entering a leaf the kernels take the walk's
+//     continuation from the visited record's miss_next, and i's is not the leaf's.  The leaf keeps its
+//     own visit.
+//   * The END sentinel and every word other than an interior hit_next -- A planes, the far planes in B,
+//     leaf codes, miss_next -- are the plain set's, word for word.
+// The equality is a property of the planes as packed: a device refit rewrites planes and no links, so
+// after one only the plain set may be walked until the next full preparation (rti::DeviceScene).
+uint32_t collapse_oct_links(const std::vector<uint32_t>& oct, uint32_t n, std::vector<uint32_t>& out) {
+    const uint32_t stride = oct_stride(n), bofs = oct_b(n);
+    out = oct;
+    uint32_t changed = 0;
+    for (uint32_t o = 0; o < 8; ++o) {
+        const uint32_t* pa = &oct[(size_t)o * stride * 4];
+        const uint32_t* pb = &oct[((size_t)bofs + (size_t)o * stride) * 4];
+        auto same_box = [&](uint32_t x, uint32_t y) {
+            return std::memcmp(pa + (size_t)x * 4, pa + (size_t)y * 4, 16) == 0 &&
+                   std::memcmp(pb + (size_t)x * 4, pb + (size_t)y * 4, 8) == 0;
+        };
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t near0 = pb[(size_t)i * 4 + 2];
+            if (near0 >= kLeafMin) continue;  // i is a leaf: its code stays
+            // (children have larger indices than their parent: the chain is finite)
+            uint32_t c = near0;
+            while (pb[(size_t)c * 4 + 2] < kLeafMin && same_box(i, c)) c = pb[(size_t)c * 4 + 2];
+            if (c != near0) {
+                out[((size_t)bofs + (size_t)o * stride + i) * 4 + 2] = c;
+                ++changed;
+            }
+        }
+    }
+    return changed;
+}
+
 // The same octant records regrouped for the walk over HBM/L2 (RT_GOCT_GROUP = G > 0): blocks of G
 // consecutive nodes, each block laid out octant-major ([block][octant][G nodes], A planes then B
 // planes), so G = 1 puts the eight octants' records of a node in one 128-B line (lanes of different
@@ -275,6 +333,16 @@ int pack_scene_host(const SceneBytes& in, uint32_t top_limit, HostPack* out) {
     p.oct_ok = build_oct_nodes(nd, nn, skips, p.oct_nodes);
     if (RT_GOCT_GROUP && p.oct_ok && (uint64_t)(nn + RT_GOCT_GROUP) * 8u < kLeafMin)
         build_oct_nodes_grouped(p.oct_nodes, nn, RT_GOCT_GROUP, p.goct_nodes, &p.goct_b);
+    // the collapsed link set of both layouts, kept only where it differs from the plain one
+    if (RT_NODE_COLLAPSE && p.oct_ok) {
+        p.collapsed_links = collapse_oct_links(p.oct_nodes, nn, p.oct_nodes_collapsed);
+        if (p.collapsed_links == 0) {
+            p.oct_nodes_collapsed.clear();
+        } else if (!p.goct_nodes.empty()) {
+            uint32_t b = 0;
+            build_oct_nodes_grouped(p.oct_nodes_collapsed, nn, RT_GOCT_GROUP, p.goct_nodes_collapsed, &b);
+        }
+    }
     return RT_SUCCESS;
 }
 

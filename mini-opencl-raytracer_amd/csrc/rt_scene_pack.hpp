@@ -27,6 +27,9 @@ inline uint32_t oct_b(uint32_t n) {
 }
 inline uint32_t oct_records(uint32_t n) { return oct_b(n) + 8u * oct_stride(n); }
 
+#ifndef RT_NODE_COLLAPSE
+#define RT_NODE_COLLAPSE 1  // launches without counters walk the collapsed links (collapse_oct_links)
+#endif
 #ifndef RT_GOCT_GROUP
 #define RT_GOCT_GROUP 1  // node-major: bunny proxy fused 1.405 -> 1.393 ms/frame (profiles/r03/goct_layout_ab.txt)
 #endif
@@ -40,6 +43,7 @@ bool build_oct_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uin
                      std::vector<uint32_t>& out);
 void build_oct_nodes_grouped(const std::vector<uint32_t>& oct, uint32_t n, uint32_t G, std::vector<uint32_t>& out,
                              uint32_t* b_ofs);
+uint32_t collapse_oct_links(const std::vector<uint32_t>& oct, uint32_t n, std::vector<uint32_t>& out);
 void build_global_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
                         uint32_t top, std::vector<uint32_t>& out, uint32_t* n_top,
                         std::vector<uint32_t>* slot_of = nullptr);
@@ -65,6 +69,10 @@ struct HostPack {
     uint32_t goct_b = 0;  // float4 offset of the regrouped records' B planes (0: none)
     std::vector<uint32_t> global_nodes, refit_links, oct_nodes;
     std::vector<uint32_t> goct_nodes;  // empty when the scene has none
+    // the collapsed link set (collapse_oct_links) of both octant layouts: empty when it changes no link
+    // word (collapsed_links 0) -- the plain records then serve as both sets
+    uint32_t collapsed_links = 0;
+    std::vector<uint32_t> oct_nodes_collapsed, goct_nodes_collapsed;
 };
 
 // Validate the scene and pack every record (top_limit: build_global_nodes' `top`).  On an error

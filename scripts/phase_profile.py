@@ -50,4 +50,9 @@ for name in scheds:
         zero = z["zero_hits"] + z["zero_misses"]
         print(f"  zero-throughput segments: hits {z['zero_hits']} misses {z['zero_misses']} = {zero} "
               f"({zero/max(1,s['rays']):.4f} of rays), scene certified: {z['scene_certified']}")
+        # the node collapse (rtKernelGetNodeCollapse): stats launches walk the plain links, except in a
+        # -DRT_NODE_COLLAPSE_STATS=1 build, whose visits against the default build's are the removed ones
+        nc = r.k.node_collapse()
+        print(f"  node collapse: {nc['collapsed_links']} link words, scene collapsible: {nc['scene_collapsible']}, "
+              f"this launch walked the collapsed links: {nc['launch_collapsed']}")
         r.close()
