@@ -105,6 +105,11 @@ public:
     // extension: the feature-guided a-trous denoiser over an image of 16-B slots (rtEnqueueDenoise)
     inline void Denoise(std::shared_ptr<CLKernel> kernel, const Buffer& image, const Buffer& features, unsigned width,
                         unsigned height, const rt_denoise_params& params, const Buffer& out) const;
+    // extension: the variance-guided a-trous denoiser over the adaptive sample statistics
+    // (rtEnqueueDenoiseSamples); variance may be null
+    inline void DenoiseSamples(std::shared_ptr<CLKernel> kernel, const Buffer& stats, const Buffer& features,
+                               unsigned width, unsigned height, const rt_denoise_samples_params& params, const Buffer& out,
+                               const Buffer* variance = nullptr) const;
     // extension: temporal reprojection of the previous image into the current view (rtEnqueueTemporalAccumulate);
     // hist and histFeatures are both null when there is no history yet
     inline void TemporalAccumulate(std::shared_ptr<CLKernel> kernel, const Buffer& cur, const Buffer& curFeatures,
@@ -190,6 +195,13 @@ inline void CLContext::Denoise(std::shared_ptr<CLKernel> kernel, const Buffer& i
                                const Buffer& out) const {
     check(rtEnqueueDenoise(ctx_, kernel->GetKernel(), image.get(), features.get(), width, height, &params, out.get()),
           "Failed to enqueue denoise");
+}
+inline void CLContext::DenoiseSamples(std::shared_ptr<CLKernel> kernel, const Buffer& stats, const Buffer& features,
+                                      unsigned width, unsigned height, const rt_denoise_samples_params& params,
+                                      const Buffer& out, const Buffer* variance) const {
+    check(rtEnqueueDenoiseSamples(ctx_, kernel->GetKernel(), stats.get(), features.get(), width, height, &params, out.get(),
+                                  variance ? variance->get() : nullptr),
+          "Failed to enqueue sample denoise");
 }
 inline void CLContext::TemporalAccumulate(std::shared_ptr<CLKernel> kernel, const Buffer& cur, const Buffer& curFeatures,
                                           const Buffer* hist, const Buffer* histFeatures, unsigned width,

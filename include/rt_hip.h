@@ -577,6 +577,75 @@ typedef struct rt_denoise_params {
 int rtEnqueueDenoise(rt_context ctx, rt_kernel k, rt_mem image, rt_mem features, unsigned width, unsigned height,
                      const rt_denoise_params* params, rt_mem out);
 
+/* ---- variance-guided denoiser over the adaptive sample statistics (extension) ------------------
+ * rtEnqueueDenoiseSamples filters what adaptive sampling has gathered with the a-trous filter above, on
+ * linear radiance and with the edge-stopping function of SVGF (Schied et al. 2017): the luminance
+ * tolerance of every centre is proportional to the standard deviation of that pixel's mean, which the
+ * statistics hold, and the variance is filtered along with the colour.  A pixel of 4 samples is
+ * smoothed hard and a converged one barely.  `stats` holds width * height rt_pixel_stats, `features` as
+ * many rt_pixel_features, `out` as many slots of 16 B {r, g, b, sample count} (rtEnqueueResolveSamples'
+ * layout) and `variance`, which may be NULL, as many floats.  Pixel p = (x, y) is record y * width + x.
+ * The filter is one definition in every math mode of `k`; every operation below is one correctly
+ * rounded fp32 operation, nothing is contracted, denormals are kept, `/` and sqrtf are IEEE, and
+ * comparisons are IEEE comparisons (false for a NaN).
+ *   input       of iteration 0, per pixel q from stats[q]:
+ *                 c_q = sum / n, three divisions
+ *                 v_q = n >= 2.0f ? (m2_y / (n - 1.0f)) / n : mean_y * mean_y
+ *               (the variance of the mean luminance; a single sample is taken to be as uncertain as it
+ *               is bright).  A pixel with !(n >= 1.0f) has c_q = 0 and v_q = -1.0f.
+ *   counting    a pixel counts when coverage_q != 0 && v_q >= 0.0f: the one rule in every iteration,
+ *               decided from the iteration's input alone.  A negative or NaN variance never enters a sum.
+ *   luminance   l(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b
+ *   iterations  i = 0 .. params->iterations - 1 with step s = 2^i; the input of a later iteration is the
+ *               {r, g, b, v} image of the one before; the features are the same in all of them.
+ *   centre      a centre that does not count keeps its {r, g, b, v} unchanged.
+ *   tolerance   for a centre that counts, once per centre: over the taps q = p + s * (dx, dy), dy outer
+ *               and dx inner, each -1 .. 1, that lie inside the image and count, with weight
+ *               g = g1[dy + 1] * g1[dx + 1], g1 = {1/4, 1/2, 1/4}:  sg += g; sv += g * v_q; both from
+ *               +0.0f.  gv = sv / sg;  tol = sigma_luminance * sqrtf(gv) + epsilon.  (At step 1 SVGF's
+ *               3 x 3 Gaussian of the variance; at larger steps taken at the tap spacing.)
+ *   taps        the 25 taps and their weight k are rtEnqueueDenoise's.  A tap outside the image or one
+ *               that does not count adds nothing.  With dot3, e, x_n, x_z, rz_p, x_a, inv_n, inv_z and
+ *               inv_a as defined there and x_l = fabsf(l(c_p) - l(c_q)) / tol:
+ *                 w = (((k * e(x_l)) * e(x_n)) * e(x_z)) * e(x_a)
+ *               A sigma of 0 disables its term: it is left out of the product.
+ *   sums        sw += w; s_r += w * c_q.r, likewise g and b; s_v += (w * w) * v_q; all from +0.0f.
+ *   result      rgb = s_rgb / sw, three divisions; v' = s_v / (sw * sw).
+ *   output      after the last iteration, with n_p read from stats[p]: out[p] = {enc(r), enc(g),
+ *               enc(b), n_p}, enc(x) = x for RT_DENOISE_LINEAR and pm_pow(x, 0.45454545f) of
+ *               rt_pinned_math.h for RT_DENOISE_GAMMA (rtEnqueueResolveSamples' encoding); variance[p]
+ *               = v', or the carried v of a centre that does not count.  A pixel with !(n_p >= 1.0f)
+ *               gets sixteen zero bytes and variance +0.0f.
+ * Behaviour is specified for finite inputs.  Others may propagate in any way, but no value of `stats` or
+ * `features` ever becomes an address, and skipped taps and disabled terms are dropped by select, never
+ * by a multiplication.
+ * Two or more iterations alternate between `out` and the scratch image rtEnqueueDenoise uses, by its
+ * rule: the last iteration lands in `out`; the scratch is grown before anything is enqueued.  `stats`
+ * and `features` are never written, bytes of `out` past width * height * 16 and of `variance` past
+ * width * height * 4 are not touched, and no scene need be bound to `k`.
+ * Ordering is rtEnqueueDenoise's: asynchronous on the context's in-order queue, coalesced per-frame
+ * launches first, after the pending accumulations; `out` and `variance` count as written; with timing
+ * on the whole call adds to kernel_ms and counts as one launch.
+ * Errors (nothing is launched or allocated), checked in this order after the context and the kernel:
+ * RT_INVALID_VALUE for params NULL, iterations outside 1 .. 5, one of the four sigmas negative, not
+ * finite, in (0, 2^-20) or above 2^20, epsilon not finite or outside [2^-40, 2^20], an encoding other
+ * than the two, width or height zero, or width * height > 2^31; RT_INVALID_MEM_OBJECT for a required
+ * buffer that is NULL or another context's, a non-NULL `variance` of another context, or `out` or
+ * `variance` the same buffer as an input or as each other; RT_INVALID_BUFFER_SIZE for `stats` or
+ * `features` under 32 B per pixel, `out` under 16 B or `variance` under 4 B. */
+#define RT_DENOISE_LINEAR 0   /* rgb as filtered */
+#define RT_DENOISE_GAMMA  1   /* pm_pow(rgb, 0.45454545f) of rt_pinned_math.h, as rtEnqueueResolveSamples */
+typedef struct rt_denoise_samples_params {
+    unsigned iterations;        /* 1 .. 5 */
+    float sigma_luminance;      /* tolerance in standard deviations of the mean; 0 leaves the term out */
+    float sigma_normal, sigma_depth, sigma_albedo;   /* exactly rt_denoise_params' */
+    float epsilon;              /* added to the luminance tolerance, in [2^-40, 2^20] */
+    int encoding;               /* RT_DENOISE_LINEAR / RT_DENOISE_GAMMA */
+} rt_denoise_samples_params;
+int rtEnqueueDenoiseSamples(rt_context ctx, rt_kernel k, rt_mem stats, rt_mem features, unsigned width,
+                            unsigned height, const rt_denoise_samples_params* params, rt_mem out,
+                            rt_mem variance /* may be NULL: 4 B per pixel */);
+
 /* ---- temporal reprojection (extension) --------------------------------------------------------
  * rtEnqueueTemporalAccumulate carries an image across a camera move: for every pixel of the current
  * view it rebuilds the world point from the feature buffer's depth, projects it into the previous

@@ -154,6 +154,18 @@ class DENOISE_PARAMS(ctypes.Structure):
                 ("sigma_depth", ctypes.c_float), ("sigma_albedo", ctypes.c_float)]
 
 
+class DENOISE_SAMPLES_PARAMS(ctypes.Structure):
+    """rt_denoise_samples_params (rt_hip.h): rtEnqueueDenoiseSamples' iteration count, the luminance
+    tolerance in standard deviations of a pixel's mean, rt_denoise_params' three feature tolerances (a sigma
+    of 0 turns its term off), the epsilon added to the luminance tolerance and the output's encoding."""
+    _fields_ = [("iterations", ctypes.c_uint), ("sigma_luminance", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_depth", ctypes.c_float), ("sigma_albedo", ctypes.c_float), ("epsilon", ctypes.c_float),
+                ("encoding", ctypes.c_int)]
+
+
+DENOISE_LINEAR, DENOISE_GAMMA = 0, 1
+
+
 class VIEW(ctypes.Structure):
     """rt_view (rt_hip.h): a camera's position, front and up vectors."""
     _fields_ = [("pos", ctypes.c_float * 3), ("front", ctypes.c_float * 3), ("up", ctypes.c_float * 3)]
@@ -226,6 +238,8 @@ _HIP_PROTOS = {
     "rtEnqueueFrameFeatures": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint, _vp]),
     "rtEnqueueDenoise": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
                                         ctypes.POINTER(DENOISE_PARAMS), _vp]),
+    "rtEnqueueDenoiseSamples": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
+                                               ctypes.POINTER(DENOISE_SAMPLES_PARAMS), _vp, _vp]),
     "rtEnqueueTemporalAccumulate": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
                                                    ctypes.POINTER(TEMPORAL_PARAMS), _vp]),
     "rtEnqueueUpdateVertices": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),

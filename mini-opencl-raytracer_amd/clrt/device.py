@@ -173,6 +173,23 @@ class CLContext:
         check(self._lib.rtEnqueueDenoise(self.handle, kernel.handle, image.handle, features.handle, int(width),
                                          int(height), ctypes.byref(params), out.handle), "Failed to enqueue denoise")
 
+    def DenoiseSamples(self, kernel: "CLKernel", stats: "Buffer", features: "Buffer", width: int, height: int,
+                       out: "Buffer", variance: "Buffer | None" = None, iterations: int = 3,
+                       sigma_luminance: float = 8.0, sigma_normal: float = 0.5, sigma_depth: float = 0.1,
+                       sigma_albedo: float = 0.25, epsilon: float = 1e-4, encoding: int = N.DENOISE_GAMMA) -> None:
+        """rtEnqueueDenoiseSamples: `iterations` passes of the a-trous filter over the linear means of the
+        width x height statistics (N.PIXEL_STATS_DTYPE), the luminance tolerance of each pixel
+        `sigma_luminance` standard deviations of its mean, guided by the N.PIXEL_FEATURES_DTYPE records of
+        `features`, into `out` ({r, g, b, sample count}, gamma-encoded or linear) and, when given, the
+        filtered variance of the mean luminance into `variance` (4 B per pixel).  A sigma of 0 turns its
+        term off.  Asynchronous; neither input is written."""
+        params = N.DENOISE_SAMPLES_PARAMS(int(iterations), float(sigma_luminance), float(sigma_normal),
+                                          float(sigma_depth), float(sigma_albedo), float(epsilon), int(encoding))
+        check(self._lib.rtEnqueueDenoiseSamples(self.handle, kernel.handle, stats.handle, features.handle, int(width),
+                                                int(height), ctypes.byref(params), out.handle,
+                                                variance.handle if variance is not None else None),
+              "Failed to enqueue sample denoise")
+
     def TemporalAccumulate(self, kernel: "CLKernel", cur: "Buffer", cur_features: "Buffer", hist: "Buffer | None",
                            hist_features: "Buffer | None", width: int, height: int, out: "Buffer", cur_view,
                            prev_view, cur_frames: float = 1.0, history_frames: float = 0.0,

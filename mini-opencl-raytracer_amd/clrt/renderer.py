@@ -52,6 +52,7 @@ class Raytracer:
         self._sample_frame = 1                # render_adaptive(): FRAME_COUNT of the next sample
         self._feat_buf: Buffer | None = None  # features(): width * height records
         self._denoise_buf: Buffer | None = None  # denoise(): the filtered image, width * height slots
+        self._sample_denoise: dict | None = None  # denoise_adaptive(): the filtered image and its variance plane
         self._temporal_feat: list = [None, None]  # temporal(): this call's and the previous call's features
         self._temporal_img: list = [None, None]   # ... and outputs; index _temporal_at is the history
         self._temporal_at = 0
@@ -353,6 +354,48 @@ class Raytracer:
         self.ctx.ReadBuffer(self._denoise_buf, out, blocking=True)
         return out
 
+    def denoise_adaptive(self, n_frames: int | None = None, iterations: int = 3, sigma_luminance: float = 8.0,
+                         sigma_normal: float = 0.5, sigma_depth: float = 0.1, sigma_albedo: float = 0.25,
+                         epsilon: float = 1e-4, encoding: str = "gamma", variance: bool = False):
+        """render_adaptive()'s statistics filtered on the device (rtEnqueueDenoiseSamples: the a-trous
+        filter of denoise() on linear radiance, with a luminance tolerance of `sigma_luminance` standard
+        deviations of each pixel's own mean, so that a pixel of few samples is smoothed hard and a
+        converged one barely), as an (H, W, 4) float32 array {r, g, b, sample count}, gamma-encoded like
+        render_adaptive()'s image or, with encoding "linear", as filtered.  With `variance` the filtered
+        variance of the mean luminance comes along as an (H, W) array: (image, variance).  The guides are
+        features() over frames 1 .. n_frames at the current camera; with n_frames None, over the sample
+        frames taken so far (the first 4096 at the most), whose jittered camera rays are the ones the
+        samples were traced along.  The statistics are only read -- the results go into kept buffers of
+        their own -- and frame_count stays.  A sigma of 0 turns its edge-stopping term off."""
+        if encoding not in ("gamma", "linear"):
+            raise ValueError("encoding is 'gamma' or 'linear'")
+        if n_frames is None:
+            n_frames = min(max(self._sample_frame - 1, 1), 4096)
+        b = self._adaptive_buffers()
+        at = self.frame_count
+        self.frame_count = 1
+        try:
+            fb = self._enqueue_features(n_frames)
+        finally:
+            self.frame_count = at
+            self.kernel.set_uint(N.FRAME_COUNT, at)
+        work = self.width * self.height
+        if self._sample_denoise is None:
+            self._sample_denoise = {"image": self.ctx.create_buffer(N.MEM_READ_WRITE, work * 16),
+                                    "variance": self.ctx.create_buffer(N.MEM_READ_WRITE, work * 4)}
+        d = self._sample_denoise
+        self.ctx.DenoiseSamples(self.kernel, b["stats"], fb, self.width, self.height, d["image"],
+                                d["variance"] if variance else None, iterations, sigma_luminance, sigma_normal,
+                                sigma_depth, sigma_albedo, epsilon,
+                                N.DENOISE_GAMMA if encoding == "gamma" else N.DENOISE_LINEAR)
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self.ctx.ReadBuffer(d["image"], out, blocking=True)
+        if not variance:
+            return out
+        var = np.empty((self.height, self.width), np.float32)
+        self.ctx.ReadBuffer(d["variance"], var, blocking=True)
+        return out, var
+
     def temporal(self, n_frames: int | None = None, max_history: float = 32.0, depth_tolerance: float = 0.05,
                  normal_threshold: float = 0.9) -> np.ndarray:
         """The accumulated image joined with the result of the previous temporal() call, which is
@@ -500,6 +543,10 @@ class Raytracer:
         if self._denoise_buf:
             self._denoise_buf.release()
             self._denoise_buf = None
+        if self._sample_denoise:
+            for b in self._sample_denoise.values():
+                b.release()
+            self._sample_denoise = None
         for bufs in (self._temporal_feat, self._temporal_img):
             for i in range(2):
                 if bufs[i]:

@@ -37,6 +37,7 @@
 #include "rt_bvh.hpp"
 #include "rt_denoise.hpp"
 #include "rt_denoise_plan.hpp"
+#include "rt_denoise_samples.hpp"
 #include "rt_device_scene.hpp"
 #include "rt_internal.hpp"
 #include "rt_kernel_state.hpp"
@@ -97,7 +98,7 @@ struct rt_kernel_s {
     rti::WavefrontQueues wfq;  // wavefront schedule: ray queues
     rti::WorkCounters counters;  // chunk counters, sky keys, rt_stats words
     rti::FeatureScratch feat;  // rtEnqueueFrameFeatures: a frame's camera rays and hits
-    rti::DenoiseScratch denoise;  // rtEnqueueDenoise: the ping-pong image
+    rti::DenoiseScratch denoise;  // rtEnqueueDenoise, rtEnqueueDenoiseSamples: the ping-pong image
     rti::AdaptiveScratch adaptive;  // rtEnqueueSelectPixels: flag planes and block counts
     rtk::OccupancyCache occ;  // workgroups per CU of the kernels launched so far
 
@@ -1042,6 +1043,67 @@ int rtEnqueueDenoise(rt_context ctx, rt_kernel k, rt_mem image, rt_mem features,
             a.invC = t.inv_c;
             e = rtd::launch_denoise(a, t, st);
         }
+        return e;
+    });
+}
+
+// ---- variance-guided a-trous denoise over the sample statistics (rt_denoise_samples.hip; the plan:
+// rt_denoise_plan.cpp) -------------------------------------------------------------------------------
+
+int rtEnqueueDenoiseSamples(rt_context ctx, rt_kernel k, rt_mem stats, rt_mem features, unsigned width, unsigned height,
+                            const rt_denoise_samples_params* params, rt_mem out, rt_mem variance) {
+    // 1. the handles and the plan: nothing is allocated or launched on an error
+    int rc = queue_head(ctx, k, {});
+    if (rc) return rc;
+    rtp::DenoiseSamplesIn in{};
+    in.params_ok = params != nullptr;
+    if (params) {
+        in.iterations = params->iterations;
+        in.sigma_luminance = params->sigma_luminance, in.sigma_normal = params->sigma_normal;
+        in.sigma_depth = params->sigma_depth, in.sigma_albedo = params->sigma_albedo;
+        in.epsilon = params->epsilon, in.encoding = params->encoding;
+    }
+    in.width = width, in.height = height;
+    in.stats_ok = stats && stats->ctx == ctx;
+    in.features_ok = features && features->ctx == ctx;
+    in.out_ok = out && out->ctx == ctx;
+    in.variance_given = variance != nullptr, in.variance_ok = variance && variance->ctx == ctx;
+    in.aliased = (out && (out == stats || out == features)) ||
+                 (variance && (variance == stats || variance == features || variance == out));
+    in.stats_bytes = in.stats_ok ? stats->size : 0;
+    in.features_bytes = in.features_ok ? features->size : 0;
+    in.out_bytes = in.out_ok ? out->size : 0;
+    in.variance_bytes = in.variance_ok ? variance->size : 0;
+    rtp::DenoiseSamplesPlan p;
+    rc = rtp::denoise_samples_plan(in, &p);
+    if (rc) return pending_error(ctx, rc);
+    // 2. the scratch rtEnqueueDenoise uses, before anything is enqueued (growing it waits for nothing:
+    // rt_internal.hpp)
+    if (p.scratch_pixels) {
+        const hipError_t me = k->denoise.reserve((size_t)p.scratch_pixels);
+        if (me != hipSuccess) return map_hip(me);
+    }
+    // 3. one launch per iteration, in order on the context's stream after the pending accumulations
+    // and gathers (the first iteration stages from the statistics: its src slot is not read)
+    float4* const bufs[3] = {nullptr, static_cast<float4*>(out->dptr), k->denoise.image()};
+    rtd::DenoiseSamplesArgs a{};
+    a.stats = static_cast<const float4*>(stats->dptr);
+    a.features = static_cast<const float4*>(features->dptr);
+    a.variance = p.write_variance ? static_cast<float*>(variance->dptr) : nullptr;
+    a.width = p.width, a.height = p.height;
+    a.terms = p.terms, a.encoding = p.encoding;
+    a.sigmaL = p.sigma_luminance, a.epsilon = p.epsilon;
+    a.invN = p.inv_n, a.invZ = p.inv_z, a.invA = p.inv_a;
+    return launch_on_queue(ctx, k, out, [&](hipStream_t st) {
+        hipError_t e = hipSuccess;
+        for (unsigned i = 0; i < p.iterations && e == hipSuccess; ++i) {
+            const rtp::DenoiseStep& t = p.it[i];
+            a.src = bufs[t.src], a.dst = bufs[t.dst];
+            a.tilesX = t.tiles_x, a.tilesPerClass = t.tiles_per_class;
+            a.last = p.last[i] ? 1u : 0u;
+            e = rtd::launch_denoise_samples(a, t, p.first[i], st);
+        }
+        if (e == hipSuccess && p.write_variance) mark_device_write(variance, true);
         return e;
     });
 }

@@ -82,4 +82,48 @@ struct DenoisePlan {
 // RT_INVALID_BUFFER_SIZE (image or out below 16 B per pixel, features below 32 B).
 int denoise_plan(const DenoiseIn& in, DenoisePlan* out);
 
+// ---- rtEnqueueDenoiseSamples: the variance-guided filter over the adaptive sample statistics ------
+// The tiles, the rows per step and the alternation of the buffers are denoise_plan's: the staged cell is
+// the same 48 B (the colour plane's w slot carries the variance), so the LDS of a step is too.  The
+// first iteration stages from the statistics (kDenoiseImage stands for them), the last one encodes,
+// reads the sample counts and writes the variance plane.
+constexpr uint32_t kDenoiseStatsBytes = 32, kDenoiseVarianceBytes = 4;
+constexpr float kDenoiseEpsilonMin = 0x1p-40f, kDenoiseEpsilonMax = 0x1p20f;
+constexpr int kDenoiseLinear = 0, kDenoiseGamma = 1;  // RT_DENOISE_LINEAR, RT_DENOISE_GAMMA
+constexpr uint32_t kDenoiseLuminance = kDenoiseColor;  // the luminance term takes the colour term's bit
+
+struct DenoiseSamplesIn {
+    bool params_ok;                      // params != NULL
+    unsigned iterations;
+    float sigma_luminance, sigma_normal, sigma_depth, sigma_albedo, epsilon;
+    int encoding;
+    uint64_t width, height;
+    bool stats_ok, features_ok, out_ok;  // each a buffer of this context
+    bool variance_given, variance_ok;    // `variance` is not NULL; ... and a buffer of this context
+    bool aliased;                        // `out` or `variance` is an input, or they are each other
+    uint64_t stats_bytes, features_bytes, out_bytes, variance_bytes;
+};
+
+struct DenoiseSamplesPlan {
+    unsigned iterations;
+    uint32_t width, height;
+    uint64_t scratch_pixels;             // the ping-pong image (0: not needed)
+    uint32_t terms;                      // DenoiseTerm bits of the enabled terms (kDenoiseLuminance for the first)
+    float sigma_luminance, epsilon;
+    float inv_n, inv_z, inv_a;           // 1 / sigma^2 (0 when the term is off)
+    int encoding;
+    bool write_variance;
+    DenoiseStep it[kDenoiseMaxIterations];  // (inv_c is not used: 0)
+    bool first[kDenoiseMaxIterations];   // stages from the statistics: iteration 0 alone
+    bool last[kDenoiseMaxIterations];    // writes the encoded image, the counts and the variance: the last alone
+};
+
+// RT_SUCCESS, or, in this order: RT_INVALID_VALUE (no params; iterations outside 1..5; a sigma that is
+// negative, not finite, in (0, 2^-20) or above 2^20; epsilon not finite or outside [2^-40, 2^20]; an
+// encoding other than the two; width or height zero; width * height > 2^31), RT_INVALID_MEM_OBJECT (a
+// required buffer that is NULL or another context's; a `variance` of another context; `out` or
+// `variance` an input or each other), RT_INVALID_BUFFER_SIZE (stats or features below 32 B per pixel,
+// out below 16 B, variance below 4 B).
+int denoise_samples_plan(const DenoiseSamplesIn& in, DenoiseSamplesPlan* out);
+
 }  // namespace rtp

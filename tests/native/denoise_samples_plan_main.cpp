@@ -1,0 +1,471 @@
+// denoise_samples_plan_main.cpp -- stand-alone driver of the plan and the shared math of rtEnqueueDenoiseSamples
+// (csrc/rt_denoise_plan.cpp denoise_samples_plan, csrc/rt_denoise_samples_math.hpp), CPU only.
+//   ... sweep    plans a sweep of image sizes and iteration counts and checks on every plan: the tiles, rows and
+//                buffers are denoise_plan's for the same size; only iteration 0 is first (it reads the statistics)
+//                and only the last is last (it writes `out`); no iteration writes what it reads; the scratch is
+//                asked for exactly when used; walking every lane of every workgroup as rt_denoise_samples.hip maps
+//                them, every pixel is filtered by exactly one lane and each of its 25 taps -- the 9 of the
+//                tolerance among them -- lies in a staged cell that holds the tap's coordinates.
+//   ... errors   the error rows of rtEnqueueDenoiseSamples (rt_hip.h) return their codes, in order.
+//   ... math     the shared math over a grid of statistics, non-finite and negative ones included: the cell of
+//                iteration 0, the counting rule, and that a tap that does not count or a term that is off leaves
+//                no trace, whatever the dropped values are.
+//   ... filter W H ITERATIONS SL SN SZ SA EPS ENCODING IN OUT
+//                the whole definition through the shared math, pixel by pixel: IN holds W * H rt_pixel_stats then
+//                as many rt_pixel_features, OUT receives W * H {r, g, b, n} then as many variances.  The sigmas
+//                and epsilon are fp32 bit patterns in decimal.  The test compares the bytes with the numpy
+//                restatement's.
+// Exit status 1 if anything breaks.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <limits>
+#include <vector>
+
+#include "../../include/rt_pinned_math.h"
+#include "../../include/rt_status.h"
+#include "../../mini-opencl-raytracer_amd/csrc/rt_denoise_plan.hpp"
+#include "../../mini-opencl-raytracer_amd/csrc/rt_denoise_samples_math.hpp"
+
+static rtp::DenoiseSamplesIn base_in() {
+    rtp::DenoiseSamplesIn in{};
+    in.params_ok = true;
+    in.iterations = 3;
+    in.sigma_luminance = 4.0f, in.sigma_normal = 0.5f, in.sigma_depth = 0.1f, in.sigma_albedo = 0.25f;
+    in.epsilon = 1e-4f, in.encoding = rtp::kDenoiseGamma;
+    in.width = 131, in.height = 77;
+    in.stats_ok = in.features_ok = in.out_ok = true;
+    in.variance_given = in.variance_ok = true;
+    in.stats_bytes = in.features_bytes = 131 * 77 * 32, in.out_bytes = 131 * 77 * 16, in.variance_bytes = 131 * 77 * 4;
+    return in;
+}
+
+static rtp::DenoiseSamplesIn sized(uint64_t w, uint64_t h, unsigned n) {
+    rtp::DenoiseSamplesIn in = base_in();
+    in.width = w, in.height = h, in.iterations = n;
+    in.stats_bytes = in.features_bytes = w * h * 32, in.out_bytes = w * h * 16, in.variance_bytes = w * h * 4;
+    return in;
+}
+
+// one iteration's tiles walked lane by lane; false (with a message) on the first thing that breaks
+static bool walk(const rtp::DenoiseStep& t, uint64_t W, uint64_t H, std::vector<uint8_t>& seen) {
+    seen.assign(W * H, 0);
+    const int64_t s = t.step;
+    for (uint32_t b = 0; b < t.grid; ++b) {
+        const uint32_t tx = b % t.tiles_x, rest = b / t.tiles_x;
+        const uint32_t ty = rest % t.tiles_per_class, cls = rest / t.tiles_per_class;
+        if (cls >= t.classes) return std::printf("class %u of %u\n", cls, t.classes), false;
+        const int64_t x0 = (int64_t)tx * rtp::kDenoiseTileW, j0 = (int64_t)ty * t.rows;
+        for (uint32_t j = 0; j < t.rows; ++j)
+            for (uint32_t lx = 0; lx < rtp::kDenoiseTileW; ++lx) {
+                const int64_t x = x0 + lx, y = cls + (j0 + j) * s;
+                if (x >= (int64_t)W || y >= (int64_t)H) continue;
+                if (++seen[y * W + x] != 1) return std::printf("pixel (%lld, %lld) twice\n", (long long)x, (long long)y), false;
+                for (int dy = -2; dy <= 2; ++dy)      // (the tolerance's taps are those with |dx|, |dy| <= 1)
+                    for (int dx = -2; dx <= 2; ++dx) {
+                        const int64_t cx = lx + 2 * s + dx * s, cy = (int64_t)j + 2 + dy;
+                        if (cx < 0 || cx >= t.stage_w || cy < 0 || cy >= t.stage_h)
+                            return std::printf("tap (%d, %d) outside the staged block\n", dx, dy), false;
+                        const int64_t sx = x0 - 2 * s + cx, sy = cls + (j0 - 2 + cy) * s;
+                        if (sx != x + dx * s || sy != y + dy * s) return std::printf("cell holds another pixel\n"), false;
+                    }
+            }
+    }
+    for (uint64_t i = 0; i < W * H; ++i)
+        if (seen[i] != 1) return std::printf("pixel %llu filtered %d times\n", (unsigned long long)i, seen[i]), false;
+    return true;
+}
+
+static bool same_step(const rtp::DenoiseStep& a, const rtp::DenoiseStep& b) {
+    return a.step == b.step && a.src == b.src && a.dst == b.dst && a.rows == b.rows && a.stage_w == b.stage_w &&
+           a.stage_h == b.stage_h && a.lds_bytes == b.lds_bytes && a.tiles_x == b.tiles_x && a.classes == b.classes &&
+           a.tiles_per_class == b.tiles_per_class && a.grid == b.grid;
+}
+
+static bool check_plan(const rtp::DenoiseSamplesIn& in, const rtp::DenoiseSamplesPlan& p, bool walk_it,
+                       std::vector<uint8_t>& seen) {
+    const uint64_t W = in.width, H = in.height;
+    if (p.iterations != in.iterations || p.width != W || p.height != H) return std::printf("sizes\n"), false;
+    // the image filter's plan of the same size: the tiles and the buffers are shared
+    rtp::DenoiseIn din{};
+    din.params_ok = true, din.iterations = in.iterations;
+    din.sigma_color = 4.0f, din.sigma_normal = in.sigma_normal, din.sigma_depth = in.sigma_depth, din.sigma_albedo = in.sigma_albedo;
+    din.width = W, din.height = H, din.image_ok = din.features_ok = din.out_ok = true;
+    din.image_bytes = din.out_bytes = W * H * 16, din.features_bytes = W * H * 32;
+    rtp::DenoisePlan dp;
+    if (rtp::denoise_plan(din, &dp) != RT_SUCCESS) return std::printf("denoise_plan\n"), false;
+    if (p.scratch_pixels != dp.scratch_pixels || p.inv_n != dp.inv_n || p.inv_z != dp.inv_z || p.inv_a != dp.inv_a)
+        return std::printf("shared constants\n"), false;
+    bool scratch_used = false;
+    for (unsigned i = 0; i < p.iterations; ++i) {
+        const rtp::DenoiseStep& t = p.it[i];
+        if (!same_step(t, dp.it[i])) return std::printf("step %u is not denoise_plan's\n", i), false;
+        if (p.first[i] != (i == 0) || p.last[i] != (i + 1 == p.iterations)) return std::printf("first / last\n"), false;
+        if (p.first[i] != (t.src == rtp::kDenoiseImage) || (p.first[i] && t.step != 1)) return std::printf("first src\n"), false;
+        if (p.last[i] && t.dst != rtp::kDenoiseOut) return std::printf("last dst\n"), false;
+        if (t.dst == t.src || t.dst == rtp::kDenoiseImage) return std::printf("dst\n"), false;
+        if (i > 0 && t.src != p.it[i - 1].dst) return std::printf("src\n"), false;
+        scratch_used = scratch_used || t.dst == rtp::kDenoiseScratch;
+        if (t.lds_bytes > rtp::kDenoiseLdsBudget) return std::printf("lds %u\n", t.lds_bytes), false;
+        if (t.grid == 0 || t.grid >= (1u << 31)) return std::printf("grid\n"), false;
+        if (walk_it && !walk(t, W, H, seen)) return false;
+    }
+    for (unsigned i = p.iterations; i < rtp::kDenoiseMaxIterations; ++i)
+        if (p.first[i] || p.last[i]) return std::printf("flags past the end\n"), false;
+    if (p.scratch_pixels != (scratch_used ? W * H : 0)) return std::printf("scratch\n"), false;
+    return true;
+}
+
+static int sweep() {
+    static const uint64_t widths[] = {1, 2, 5, 40, 61, 63, 64, 65, 127, 128, 131, 200};
+    static const uint64_t heights[] = {1, 2, 3, 7, 8, 9, 15, 16, 17, 31, 33, 64, 77, 129, 200};
+    static const uint64_t big[][2] = {{3840, 2160}, {1ull << 31, 1}, {1, 1ull << 31}, {65536, 32768}, {46340, 46340},
+                                      {(1ull << 31) / 3, 3}, {3, (1ull << 31) / 3}, {1ull << 20, 1ull << 11}};
+    unsigned long long plans = 0, failures = 0;
+    std::vector<uint8_t> seen;
+    auto one = [&](uint64_t w, uint64_t h, unsigned n, bool walk_it) {
+        const rtp::DenoiseSamplesIn in = sized(w, h, n);
+        rtp::DenoiseSamplesPlan p;
+        const int rc = rtp::denoise_samples_plan(in, &p);
+        ++plans;
+        if ((rc != RT_SUCCESS || !check_plan(in, p, walk_it, seen)) && ++failures <= 20)
+            std::printf("broken: %llu x %llu, %u iterations: rc %d\n", (unsigned long long)w, (unsigned long long)h, n, rc);
+    };
+    for (uint64_t w : widths)
+        for (uint64_t h : heights)
+            for (unsigned n = 1; n <= rtp::kDenoiseMaxIterations; ++n) one(w, h, n, n == rtp::kDenoiseMaxIterations);
+    for (auto& wh : big)
+        for (unsigned n = 1; n <= rtp::kDenoiseMaxIterations; ++n) one(wh[0], wh[1], n, false);
+    std::printf("sweep: %llu plans, %llu failures\n", plans, failures);
+    return failures ? 1 : 0;
+}
+
+// the documented order, spelled independently of the plan
+static int expected(const rtp::DenoiseSamplesIn& in) {
+    if (!in.params_ok || in.iterations < 1 || in.iterations > 5) return RT_INVALID_VALUE;
+    for (float s : {in.sigma_luminance, in.sigma_normal, in.sigma_depth, in.sigma_albedo})
+        if (!(s == 0.0f || (s >= 0x1p-20f && s <= 0x1p20f))) return RT_INVALID_VALUE;  // (false for a NaN)
+    if (!(in.epsilon >= 0x1p-40f && in.epsilon <= 0x1p20f)) return RT_INVALID_VALUE;
+    if (in.encoding != 0 && in.encoding != 1) return RT_INVALID_VALUE;
+    const unsigned __int128 pixels = (unsigned __int128)in.width * in.height;
+    if (pixels == 0 || pixels > ((unsigned __int128)1 << 31)) return RT_INVALID_VALUE;
+    if (!in.stats_ok || !in.features_ok || !in.out_ok || (in.variance_given && !in.variance_ok) || in.aliased)
+        return RT_INVALID_MEM_OBJECT;
+    if (pixels * 32 > in.stats_bytes || pixels * 32 > in.features_bytes || pixels * 16 > in.out_bytes ||
+        (in.variance_given && pixels * 4 > in.variance_bytes))
+        return RT_INVALID_BUFFER_SIZE;
+    return RT_SUCCESS;
+}
+
+static int errors() {
+    int failures = 0;
+    auto expect = [&](const char* name, const rtp::DenoiseSamplesIn& in, int want) {
+        rtp::DenoiseSamplesPlan p;
+        const int rc = rtp::denoise_samples_plan(in, &p);
+        const bool ok = rc == want && expected(in) == want;
+        std::printf("%s %s: rc %d (want %d, restated %d)\n", ok ? "ok    " : "FAILED", name, rc, want, expected(in));
+        if (!ok) ++failures;
+    };
+    const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+    rtp::DenoiseSamplesIn in = base_in();
+    expect("valid", in, RT_SUCCESS);
+    in = base_in(), in.variance_given = in.variance_ok = false, in.variance_bytes = 0;
+    expect("valid_without_variance", in, RT_SUCCESS);
+    in = base_in(), in.params_ok = false;
+    expect("params_null", in, RT_INVALID_VALUE);
+    in = base_in(), in.iterations = 0;
+    expect("iterations_zero", in, RT_INVALID_VALUE);
+    in = base_in(), in.iterations = 6;
+    expect("iterations_six", in, RT_INVALID_VALUE);
+    in = base_in(), in.iterations = 5;
+    expect("iterations_five", in, RT_SUCCESS);
+    in = base_in(), in.sigma_luminance = -1.0f;
+    expect("sigma_negative", in, RT_INVALID_VALUE);
+    in = base_in(), in.sigma_normal = nan;
+    expect("sigma_nan", in, RT_INVALID_VALUE);
+    in = base_in(), in.sigma_depth = inf;
+    expect("sigma_infinite", in, RT_INVALID_VALUE);
+    in = base_in(), in.sigma_albedo = 0x1p-21f;
+    expect("sigma_tiny", in, RT_INVALID_VALUE);
+    in = base_in(), in.sigma_luminance = 0x1p-20f;
+    expect("sigma_smallest", in, RT_SUCCESS);
+    in = base_in(), in.sigma_luminance = 0x1.000002p20f;
+    expect("sigma_huge", in, RT_INVALID_VALUE);
+    in = base_in(), in.sigma_luminance = 0x1p20f;
+    expect("sigma_largest", in, RT_SUCCESS);
+    in = base_in(), in.sigma_luminance = in.sigma_normal = in.sigma_depth = in.sigma_albedo = 0.0f;
+    expect("sigmas_all_zero", in, RT_SUCCESS);
+    in = base_in(), in.epsilon = 0.0f;
+    expect("epsilon_zero", in, RT_INVALID_VALUE);
+    in = base_in(), in.epsilon = 0x1p-41f;
+    expect("epsilon_tiny", in, RT_INVALID_VALUE);
+    in = base_in(), in.epsilon = 0x1p-40f;
+    expect("epsilon_smallest", in, RT_SUCCESS);
+    in = base_in(), in.epsilon = 0x1.000002p20f;
+    expect("epsilon_huge", in, RT_INVALID_VALUE);
+    in = base_in(), in.epsilon = 0x1p20f;
+    expect("epsilon_largest", in, RT_SUCCESS);
+    in = base_in(), in.epsilon = nan;
+    expect("epsilon_nan", in, RT_INVALID_VALUE);
+    in = base_in(), in.epsilon = inf;
+    expect("epsilon_infinite", in, RT_INVALID_VALUE);
+    in = base_in(), in.epsilon = -1e-4f;
+    expect("epsilon_negative", in, RT_INVALID_VALUE);
+    in = base_in(), in.encoding = 2;
+    expect("encoding_two", in, RT_INVALID_VALUE);
+    in = base_in(), in.encoding = -1;
+    expect("encoding_negative", in, RT_INVALID_VALUE);
+    in = base_in(), in.encoding = rtp::kDenoiseLinear;
+    expect("encoding_linear", in, RT_SUCCESS);
+    in = base_in(), in.width = 0;
+    expect("width_zero", in, RT_INVALID_VALUE);
+    in = base_in(), in.height = 0;
+    expect("height_zero", in, RT_INVALID_VALUE);
+    in = sized(65536, 32768 + 1, 1);
+    expect("past_2_31", in, RT_INVALID_VALUE);
+    in = sized(0xffffffffull, 0xffffffffull, 1), in.stats_bytes = in.out_bytes = in.features_bytes = in.variance_bytes = ~0ull;
+    expect("product_near_2_64", in, RT_INVALID_VALUE);
+    in = sized(65536, 32768, 1);
+    expect("exactly_2_31", in, RT_SUCCESS);
+    in = base_in(), in.stats_ok = false, in.stats_bytes = 0;
+    expect("stats_null", in, RT_INVALID_MEM_OBJECT);
+    in = base_in(), in.features_ok = false, in.features_bytes = 0;
+    expect("features_null", in, RT_INVALID_MEM_OBJECT);
+    in = base_in(), in.out_ok = false, in.out_bytes = 0;
+    expect("out_null", in, RT_INVALID_MEM_OBJECT);
+    in = base_in(), in.variance_ok = false, in.variance_bytes = 0;
+    expect("variance_foreign", in, RT_INVALID_MEM_OBJECT);
+    in = base_in(), in.aliased = true;
+    expect("aliased", in, RT_INVALID_MEM_OBJECT);
+    in = base_in(), in.stats_bytes -= 1;
+    expect("stats_short", in, RT_INVALID_BUFFER_SIZE);
+    in = base_in(), in.features_bytes -= 1;
+    expect("features_short", in, RT_INVALID_BUFFER_SIZE);
+    in = base_in(), in.out_bytes -= 1;
+    expect("out_short", in, RT_INVALID_BUFFER_SIZE);
+    in = base_in(), in.variance_bytes -= 1;
+    expect("variance_short", in, RT_INVALID_BUFFER_SIZE);
+    in = base_in(), in.variance_given = in.variance_ok = false, in.variance_bytes = 0;
+    expect("variance_absent_is_not_short", in, RT_SUCCESS);
+    // the order: the earlier row wins
+    in = base_in(), in.iterations = 0, in.out_ok = false, in.stats_bytes = 1;
+    expect("value_before_mem_object", in, RT_INVALID_VALUE);
+    in = base_in(), in.epsilon = 0.0f, in.aliased = true;
+    expect("epsilon_before_mem_object", in, RT_INVALID_VALUE);
+    in = base_in(), in.encoding = 7, in.variance_ok = false;
+    expect("encoding_before_mem_object", in, RT_INVALID_VALUE);
+    in = base_in(), in.sigma_depth = -1.0f, in.epsilon = 0.0f, in.encoding = 7, in.width = 0;
+    expect("all_value_rows", in, RT_INVALID_VALUE);
+    in = base_in(), in.width = 0, in.stats_bytes = 0;
+    expect("size_zero_before_buffer_size", in, RT_INVALID_VALUE);
+    in = base_in(), in.aliased = true, in.out_bytes = 1;
+    expect("mem_object_before_size", in, RT_INVALID_MEM_OBJECT);
+    // the constants
+    in = base_in(), in.iterations = 5;
+    rtp::DenoiseSamplesPlan p;
+    bool ok = rtp::denoise_samples_plan(in, &p) == RT_SUCCESS && p.terms == 15 && p.inv_n == 1.0f / (0.5f * 0.5f) &&
+              p.inv_z == 1.0f / (0.1f * 0.1f) && p.inv_a == 1.0f / (0.25f * 0.25f) && p.sigma_luminance == 4.0f &&
+              p.epsilon == 1e-4f && p.encoding == rtp::kDenoiseGamma && p.write_variance;
+    in.sigma_luminance = 0.0f, in.sigma_depth = 0.0f, in.variance_given = in.variance_ok = false;
+    ok = ok && rtp::denoise_samples_plan(in, &p) == RT_SUCCESS && p.terms == (rtp::kDenoiseNormal | rtp::kDenoiseAlbedo) &&
+         !p.write_variance;
+    std::printf("%s constants\n", ok ? "ok    " : "FAILED");
+    if (!ok) ++failures;
+    return failures ? 1 : 0;
+}
+
+// ---- the shared math ------------------------------------------------------------------------------------
+static uint32_t bits(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return u;
+}
+static bool same(float a, float b) { return bits(a) == bits(b) || (std::isnan(a) && std::isnan(b)); }
+static bool same_sums(const rtds::Sums& a, const rtds::Sums& b) {
+    return bits(a.w) == bits(b.w) && bits(a.r) == bits(b.r) && bits(a.g) == bits(b.g) && bits(a.b) == bits(b.b) &&
+           bits(a.v) == bits(b.v);
+}
+
+static int math() {
+    const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+    const float ns[] = {nan, -inf, -1.0f, -0.0f, 0.0f, 0x1p-149f, 0.5f, 0.99999994f, 1.0f, 1.5f, 2.0f, 5.0f, 40.0f, 3000.0f, 0x1p24f, inf};
+    const float m2s[] = {nan, -inf, -1.0f, -0x1p-149f, -0.0f, 0.0f, 0x1p-149f, 0.3f, 70.0f, 3.0e38f, inf};
+    const float means[] = {nan, -inf, -0.2f, 0.0f, 0x1p-80f, 0.7f, 2.0e19f, inf};
+    const float sums[] = {nan, -3.0f, 0.0f, 0.25f, 9000.0f, inf};
+    const float covs[] = {nan, -1.0f, -0.0f, 0.0f, 0x1p-149f, 0.125f, 1.0f, inf};
+    unsigned long long checks = 0, failures = 0;
+    auto fail = [&](const char* what) {
+        if (++failures <= 20) std::printf("broken: %s\n", what);
+    };
+    // the cell of iteration 0 and the counting rule
+    for (float n : ns)
+        for (float m2 : m2s)
+            for (float mean : means)
+                for (float sum : sums) {
+                    const rtds::Cell c = rtds::stats_cell(sum, sum * 0.5f, 1.0f, n, mean, m2);
+                    ++checks;
+                    if (!(n >= 1.0f)) {
+                        if (bits(c.r) != 0 || bits(c.g) != 0 || bits(c.b) != 0 || bits(c.v) != bits(-1.0f)) fail("empty pixel's cell");
+                        for (float cov : covs)
+                            if (rtds::counts(cov, c.v)) fail("an empty pixel counts");
+                        continue;
+                    }
+                    const float v = n >= 2.0f ? (m2 / (n - 1.0f)) / n : mean * mean;
+                    if (!same(c.v, v) || !same(c.r, sum / n) || !same(c.g, (sum * 0.5f) / n) || !same(c.b, 1.0f / n)) fail("cell");
+                    for (float cov : covs) {
+                        const bool want = cov != 0.0f && v >= 0.0f;
+                        if (rtds::counts(cov, c.v) != want) fail("counting rule");
+                        if (rtds::counts(cov, c.v) && (std::isnan(c.v) || c.v < 0.0f)) fail("a bad variance counts");
+                    }
+                }
+    // a tap that does not count leaves no trace; a term that is off neither, whatever its constant is
+    const rtds::Guide gp{0.5f, 0.25f, 0.75f, 21.0f, 0.0f, 0.0f, 1.0f, 1.0f};
+    const rtds::Cell cp{0.5f, 0.75f, 0.25f, 0.01f};
+    const rtds::Sums s0{0.3f, 0.1f, 0.2f, 0.05f, 0.002f};
+    const rtds::TolSums t0{0.75f, 0.004f};
+    const rtds::Terms all{true, true, true, true, 4.0f, 100.0f, 16.0f};
+    const rtds::Terms none{false, false, false, false, nan, inf, -1.0f};
+    for (float a : m2s)
+        for (float b : means)
+            for (float tol : {1e-4f, 0.5f, nan, 0.0f, inf}) {
+                const rtds::Cell cq{a, b, a, b};
+                const rtds::Guide gq{b, a, b, a, a, b, a, b};
+                const rtds::Centre ce = rtds::centre_of(cp, gp, tol);
+                ++checks;
+                if (!same_sums(rtds::tap_update(s0, 0.0625f, ce, cq, gq, all, false), s0)) fail("a dropped tap changes the sums");
+                const rtds::TolSums t1 = rtds::tol_tap(t0, 0.25f, a, false);
+                if (bits(t1.sg) != bits(t0.sg) || bits(t1.sv) != bits(t0.sv)) fail("a dropped tap changes the tolerance");
+                // every term off: w = k exactly, whatever the guides and the constants hold
+                const rtds::Cell fq{0.125f, 2.0f, 1.0f, 0.5f};
+                const rtds::Sums got = rtds::tap_update(s0, 0.25f, ce, fq, gq, none, true);
+                const rtds::Sums want{s0.w + 0.25f, s0.r + 0.25f * fq.r, s0.g + 0.25f * fq.g, s0.b + 0.25f * fq.b,
+                                      s0.v + (0.25f * 0.25f) * fq.v};
+                if (!same_sums(got, want)) fail("a term that is off leaves a trace");
+            }
+    // the centre tap has x = 0 in every term: w = k, and one tap alone gives the centre back
+    for (float tol : {0x1p-40f, 1e-4f, 0.5f, 3.0e5f}) {
+        const rtds::Centre ce = rtds::centre_of(cp, gp, tol);
+        const rtds::Sums one = rtds::tap_update(rtds::Sums{0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 0.140625f, ce, cp, gp, all, true);
+        ++checks;
+        if (bits(one.w) != bits(0.140625f)) fail("centre tap weight");
+        const rtds::Cell r = rtds::iteration_result(one);
+        if (!same(r.r, (0.140625f * cp.r) / 0.140625f) || !same(r.v, ((0.140625f * 0.140625f) * cp.v) / (0.140625f * 0.140625f)))
+            fail("one tap's result");
+    }
+    // edge: 1 at 0, 0 from 1 on, within [0, 1] between; the weights of the two kernels
+    for (float x : {0.0f, 0.25f, 0.999f, 1.0f, 7.0f, inf}) {
+        const float e = rtds::edge(x);
+        ++checks;
+        if (!(e >= 0.0f && e <= 1.0f) || (x == 0.0f && e != 1.0f) || (x >= 1.0f && e != 0.0f)) fail("edge");
+    }
+    float sk = 0.0f, sg = 0.0f;
+    for (int d = -2; d <= 2; ++d) sk += rtds::spline_weight(d);
+    for (int d = -1; d <= 1; ++d) sg += rtds::tol_weight(d);
+    ++checks;
+    if (sk != 1.0f || sg != 1.0f || rtds::spline_weight(0) != 0.375f || rtds::tol_weight(0) != 0.5f) fail("kernel weights");
+    // the tolerance: sigma * sqrt(sv / sg) + epsilon
+    {
+        rtds::TolSums t{0.0f, 0.0f};
+        t = rtds::tol_tap(t, 0.25f, 0.04f, true);
+        t = rtds::tol_tap(t, 0.125f, nan, false);
+        t = rtds::tol_tap(t, 0.0625f, 0.01f, true);
+        const float sv = 0.25f * 0.04f + 0.0625f * 0.01f, sgg = 0.25f + 0.0625f;
+        ++checks;
+        if (!same(rtds::tolerance(t, 4.0f, 1e-4f), 4.0f * std::sqrt(sv / sgg) + 1e-4f)) fail("tolerance");
+    }
+    std::printf("math: %llu checks, %llu failures\n", checks, failures);
+    return failures ? 1 : 0;
+}
+
+// ---- the whole definition, pixel by pixel -----------------------------------------------------------------
+static float from_bits(const char* s) {
+    const uint32_t u = (uint32_t)std::strtoul(s, nullptr, 10);
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+
+static int filter(char** argv) {
+    const int64_t W = std::atoll(argv[0]), H = std::atoll(argv[1]);
+    const int iterations = std::atoi(argv[2]);
+    const float sl = from_bits(argv[3]), sn = from_bits(argv[4]), sz = from_bits(argv[5]), sa = from_bits(argv[6]);
+    const float eps = from_bits(argv[7]);
+    const int encoding = std::atoi(argv[8]);
+    if (W <= 0 || H <= 0 || W * H > (1 << 24) || iterations < 1 || iterations > 5) return 2;
+    const size_t px = (size_t)(W * H);
+    std::vector<float> stats(px * 8), feat(px * 8);
+    FILE* f = std::fopen(argv[9], "rb");
+    if (!f || std::fread(stats.data(), 32, px, f) != px || std::fread(feat.data(), 32, px, f) != px) return 2;
+    std::fclose(f);
+    auto inv_sq = [](float s) { return s == 0.0f ? 0.0f : 1.0f / (s * s); };
+    const rtds::Terms terms{sl != 0.0f, sn != 0.0f, sz != 0.0f, sa != 0.0f, inv_sq(sn), inv_sq(sz), inv_sq(sa)};
+    auto guide = [&](size_t p) {
+        const float* g = &feat[p * 8];
+        return rtds::Guide{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7]};
+    };
+    std::vector<rtds::Cell> cur(px), next(px);
+    for (size_t p = 0; p < px; ++p) {
+        const float* s = &stats[p * 8];
+        cur[p] = rtds::stats_cell(s[0], s[1], s[2], s[3], s[4], s[5]);
+    }
+    for (int i = 0; i < iterations; ++i) {
+        const int64_t step = 1 << i;
+        for (int64_t y = 0; y < H; ++y)
+            for (int64_t x = 0; x < W; ++x) {
+                const size_t p = (size_t)(y * W + x);
+                const rtds::Guide gp = guide(p);
+                next[p] = cur[p];
+                if (!rtds::counts(gp.coverage, cur[p].v)) continue;
+                auto inside = [&](int64_t qx, int64_t qy) { return qx >= 0 && qx < W && qy >= 0 && qy < H; };
+                rtds::TolSums ts{0.0f, 0.0f};
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int64_t qx = x + step * dx, qy = y + step * dy;
+                        if (!inside(qx, qy)) continue;
+                        const size_t q = (size_t)(qy * W + qx);
+                        ts = rtds::tol_tap(ts, rtds::tol_weight(dy) * rtds::tol_weight(dx), cur[q].v,
+                                           rtds::counts(guide(q).coverage, cur[q].v));
+                    }
+                const rtds::Centre ce = rtds::centre_of(cur[p], gp, rtds::tolerance(ts, sl, eps));
+                rtds::Sums s{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                for (int dy = -2; dy <= 2; ++dy)
+                    for (int dx = -2; dx <= 2; ++dx) {
+                        const int64_t qx = x + step * dx, qy = y + step * dy;
+                        if (!inside(qx, qy)) continue;
+                        const size_t q = (size_t)(qy * W + qx);
+                        const rtds::Guide gq = guide(q);
+                        s = rtds::tap_update(s, rtds::spline_weight(dy) * rtds::spline_weight(dx), ce, cur[q], gq, terms,
+                                             rtds::counts(gq.coverage, cur[q].v));
+                    }
+                next[p] = rtds::iteration_result(s);
+            }
+        cur.swap(next);
+    }
+    std::vector<float> out(px * 4, 0.0f), var(px, 0.0f);
+    for (size_t p = 0; p < px; ++p) {
+        const float n = stats[p * 8 + 3];
+        if (!(n >= 1.0f)) continue;
+        const float g = 0.45454545f;
+        const rtds::Cell& c = cur[p];
+        out[p * 4 + 0] = encoding == rtp::kDenoiseGamma ? pm_pow(c.r, g) : c.r;
+        out[p * 4 + 1] = encoding == rtp::kDenoiseGamma ? pm_pow(c.g, g) : c.g;
+        out[p * 4 + 2] = encoding == rtp::kDenoiseGamma ? pm_pow(c.b, g) : c.b;
+        out[p * 4 + 3] = n;
+        var[p] = c.v;
+    }
+    f = std::fopen(argv[10], "wb");
+    if (!f || std::fwrite(out.data(), 16, px, f) != px || std::fwrite(var.data(), 4, px, f) != px) return 2;
+    std::fclose(f);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 2 && std::strcmp(argv[1], "sweep") == 0) return sweep();
+    if (argc == 2 && std::strcmp(argv[1], "errors") == 0) return errors();
+    if (argc == 2 && std::strcmp(argv[1], "math") == 0) return math();
+    if (argc == 13 && std::strcmp(argv[1], "filter") == 0) return filter(argv + 2);
+    std::fprintf(stderr, "usage: denoise_samples_plan_main sweep|errors|math|filter W H N SL SN SZ SA EPS ENC IN OUT\n");
+    return 2;
+}
