@@ -115,6 +115,10 @@ public:
     inline void TemporalAccumulate(std::shared_ptr<CLKernel> kernel, const Buffer& cur, const Buffer& curFeatures,
                                    const Buffer* hist, const Buffer* histFeatures, unsigned width, unsigned height,
                                    const rt_temporal_params& params, const Buffer& out) const;
+    // extension: the adaptive sample statistics reprojected into the current view (rtEnqueueReprojectSamples)
+    inline void ReprojectSamples(std::shared_ptr<CLKernel> kernel, const Buffer& histStats, const Buffer& histFeatures,
+                                 const Buffer& curFeatures, unsigned width, unsigned height,
+                                 const rt_reproject_params& params, const Buffer& outStats) const;
     // extensions: adaptive sampling (rt_hip.h): per-pixel sample statistics from linear path results (ids null:
     // record i is pixel i), the ordered list of pixels that still need samples, camera paths for such a list,
     // and the statistics resolved into an {r, g, b, sample count} image
@@ -210,6 +214,13 @@ inline void CLContext::TemporalAccumulate(std::shared_ptr<CLKernel> kernel, cons
                                       hist ? hist->get() : nullptr, histFeatures ? histFeatures->get() : nullptr, width,
                                       height, &params, out.get()),
           "Failed to enqueue temporal accumulate");
+}
+inline void CLContext::ReprojectSamples(std::shared_ptr<CLKernel> kernel, const Buffer& histStats,
+                                        const Buffer& histFeatures, const Buffer& curFeatures, unsigned width,
+                                        unsigned height, const rt_reproject_params& params, const Buffer& outStats) const {
+    check(rtEnqueueReprojectSamples(ctx_, kernel->GetKernel(), histStats.get(), histFeatures.get(), curFeatures.get(), width,
+                                    height, &params, outStats.get()),
+          "Failed to enqueue sample reprojection");
 }
 inline void CLContext::AccumulateSamples(std::shared_ptr<CLKernel> kernel, const Buffer* ids, const Buffer& results,
                                          size_t first, size_t n, size_t nPixels, const Buffer& stats) const {

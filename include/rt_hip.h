@@ -722,6 +722,71 @@ int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem 
                                 rt_mem hist /* may be NULL */, rt_mem hist_features /* NULL iff hist is */,
                                 unsigned width, unsigned height, const rt_temporal_params* params, rt_mem out);
 
+/* ---- reprojection of the adaptive sample statistics (extension) ---------------------------------
+ * rtEnqueueReprojectSamples carries the per-pixel statistics of adaptive sampling across a camera move:
+ * for every pixel of the current view it finds, as rtEnqueueTemporalAccumulate does, the point of the
+ * previous view that shows the same surface, gathers the statistics of the taps around it that lie on
+ * that surface, and recombines them into one rt_pixel_stats -- a mean, a per-sample luminance variance
+ * and an integer sample count of at most max_history.  A pixel that finds nothing (a disocclusion, a
+ * point outside the previous image, an uncovered pixel) gets 32 zero bytes, rt_pixel_stats' "no
+ * samples", which rtEnqueueSelectPixels selects unconditionally; the pixels that keep statistics are
+ * selected only where those still say so.  `hist_stats` and `out_stats` hold width * height
+ * rt_pixel_stats, `hist_features` and `cur_features` as many rt_pixel_features, taken at params->prev and
+ * params->cur.  Pixel p = (x, y) is record y * width + x.
+ * The operation is one definition in every math mode of `k`; every operation below is one correctly
+ * rounded fp32 operation, nothing is contracted, denormals are kept, `/` and sqrtf are IEEE, and
+ * comparisons are IEEE comparisons (false for a NaN).  Helpers, constants, W and H are
+ * rtEnqueueTemporalAccumulate's.  Per pixel, with f = cur_features[p]; every "nothing carried" below
+ * writes 32 zero bytes:
+ *   1 centre    nothing carried unless f.coverage > 0.
+ *   2 point, 3 project, 4 range
+ *               steps 2 to 4 of rtEnqueueTemporalAccumulate as they stand there, with "nothing carried"
+ *               for "no history": they give x0, y0, tx, ty and de.
+ *   5 taps      q = (x0 + i, y0 + j), j outer and i inner, each 0 then 1, with weight
+ *               bw = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty).  With s = hist_stats[q] and
+ *               g = hist_features[q] a tap counts only when q lies inside the image, g.coverage > 0,
+ *               fabsf(g.depth - de) <= depth_tolerance * de, dot3(f.normal, g.normal) >= normal_threshold,
+ *               and s.n >= 1.0f.  For a tap that counts
+ *                 m  = s.sum / s.n                                  per channel, three divisions
+ *                 sv = s.n >= 2.0f ? s.m2_y / (s.n - 1.0f) : s.mean_y * s.mean_y
+ *               (sv is the per-sample variance of the luminance; a single sample is taken to be as
+ *               uncertain as it is bright, rtEnqueueDenoiseSamples' rule stated per sample).  Sums start
+ *               at +0.0f: sw += bw; sm += bw * m per channel; sy += bw * s.mean_y; ss += bw * sv;
+ *               sn += bw * s.n.  A tap that does not count adds nothing and is never multiplied in.
+ *   6 result    nothing carried unless sw >= 0x1p-6f.  Otherwise
+ *                 n'         = fminf(floorf(sn / sw), max_history)
+ *                 out.sum    = (sm / sw) * n'                       per channel
+ *                 out.n      = n'
+ *                 out.mean_y = sy / sw
+ *                 out.m2_y   = n' >= 2.0f ? (ss / sw) * (n' - 1.0f) : +0.0f
+ *               and reserved[2] = 0.  n' is an integer value held as a float, as rt_pixel_stats requires,
+ *               and at least 1: every counted s.n is, and rounding is monotone.
+ * Behaviour is specified for every bit pattern of the depths and the coverages, and of the statistics of
+ * taps that do not count; the statistics of taps that count are specified for finite, non-negative
+ * values only (others may propagate in any way).  No index is formed from a coordinate that was not
+ * range-tested first, and no value of `hist_stats` ever takes part in an address.
+ * The three inputs are never written and may alias one another; `out_stats` may be none of them; bytes
+ * of `out_stats` past width * height * 32 are not touched; no scene need be bound to `k`.
+ * Ordering is rtEnqueueDenoise's: asynchronous on the context's in-order queue, coalesced per-frame
+ * launches first, after the pending accumulations, "another call touching the context" for the
+ * deferral rules; `out_stats` counts as written for the buffers' generations; with timing on the call
+ * adds to kernel_ms and counts as one launch.
+ * Errors (nothing is launched), checked in this order after the context and the kernel:
+ * RT_INVALID_VALUE for params NULL; width or height zero or width * height > 2^31; a camera component
+ * that is not finite; max_history not finite, not an integer value, < 1 or > 2^20; depth_tolerance not
+ * finite or outside [0, 1]; normal_threshold not finite or outside [-1, 1].  RT_INVALID_MEM_OBJECT for
+ * a buffer that is NULL or another context's; `out_stats` the same buffer as any input.
+ * RT_INVALID_BUFFER_SIZE for any buffer under 32 B per pixel. */
+typedef struct rt_reproject_params {
+    rt_view cur, prev;       /* cameras of cur_features / out_stats and of hist_stats / hist_features */
+    float max_history;       /* cap of a carried sample count: an integer value in [1, 2^20] */
+    float depth_tolerance;   /* relative, 0 .. 1   (rt_temporal_params') */
+    float normal_threshold;  /* -1 .. 1            (rt_temporal_params') */
+} rt_reproject_params;
+int rtEnqueueReprojectSamples(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt_mem hist_features,
+                              rt_mem cur_features, unsigned width, unsigned height,
+                              const rt_reproject_params* params, rt_mem out_stats);
+
 /* ---- moving geometry: vertex update + device-side BVH refit (extension) ----
  * For a mesh whose triangles move while the tree's shape stays put.  Both enqueue calls are
  * asynchronous on the context's in-order queue and never wait on the host: they launch the

@@ -180,6 +180,13 @@ class TEMPORAL_PARAMS(ctypes.Structure):
                 ("normal_threshold", ctypes.c_float)]
 
 
+class REPROJECT_PARAMS(ctypes.Structure):
+    """rt_reproject_params (rt_hip.h): rtEnqueueReprojectSamples' two cameras, the cap of a carried sample
+    count (an integer value) and rt_temporal_params' two surface tests of a history tap."""
+    _fields_ = [("cur", VIEW), ("prev", VIEW), ("max_history", ctypes.c_float), ("depth_tolerance", ctypes.c_float),
+                ("normal_threshold", ctypes.c_float)]
+
+
 # tan of the fp32 0.5f * (45.0f * 3.1415f / 180.0f) rounded to fp32 (kernel_bvh.cl:392): the reprojection's A
 TEMPORAL_TAN_HALF_FOV = float.fromhex("0x1.a82408p-2")
 TEMPORAL_MAX_FRAMES = 2.0 ** 20
@@ -242,6 +249,8 @@ _HIP_PROTOS = {
                                                ctypes.POINTER(DENOISE_SAMPLES_PARAMS), _vp, _vp]),
     "rtEnqueueTemporalAccumulate": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
                                                    ctypes.POINTER(TEMPORAL_PARAMS), _vp]),
+    "rtEnqueueReprojectSamples": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
+                                                 ctypes.POINTER(REPROJECT_PARAMS), _vp]),
     "rtEnqueueUpdateVertices": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
     "rtRefitBVH": (ctypes.c_int, [_vp, _vp]),
     "rtDiagScenePrepares": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),

@@ -212,6 +212,26 @@ class CLContext:
                                                     int(width), int(height), ctypes.byref(params), out.handle),
               "Failed to enqueue temporal accumulate")
 
+    def ReprojectSamples(self, kernel: "CLKernel", hist_stats: "Buffer", hist_features: "Buffer",
+                         cur_features: "Buffer", width: int, height: int, out_stats: "Buffer", cur_view, prev_view,
+                         max_history: float = 16.0, depth_tolerance: float = 0.05,
+                         normal_threshold: float = 0.9) -> None:
+        """rtEnqueueReprojectSamples: the width x height sample statistics `hist_stats`
+        (N.PIXEL_STATS_DTYPE, with the features of their view) reprojected from `prev_view` into `cur_view`
+        and recombined into `out_stats`: per pixel a mean, a per-sample variance and an integer sample
+        count of at most `max_history` from the history taps on the same surface, or 32 zero bytes (no
+        samples) where there is none.  A view is (position, front, up), three xyz triples.  Asynchronous;
+        no input is written, and `out_stats` is none of them."""
+        def view(v):
+            pos, front, up = v
+            return N.VIEW((ctypes.c_float * 3)(*map(float, pos)), (ctypes.c_float * 3)(*map(float, front)),
+                          (ctypes.c_float * 3)(*map(float, up)))
+        params = N.REPROJECT_PARAMS(view(cur_view), view(prev_view), float(max_history), float(depth_tolerance),
+                                    float(normal_threshold))
+        check(self._lib.rtEnqueueReprojectSamples(self.handle, kernel.handle, hist_stats.handle, hist_features.handle,
+                                                  cur_features.handle, int(width), int(height), ctypes.byref(params),
+                                                  out_stats.handle), "Failed to enqueue sample reprojection")
+
     def UpdateVertices(self, tris: "Buffer", first: int, n: int, positions: "Buffer",
                        normals: "Buffer | None" = None) -> None:
         """rtEnqueueUpdateVertices: the position (and normal) xyz of triangles [first, first + n) of `tris`

@@ -53,6 +53,7 @@ class Raytracer:
         self._feat_buf: Buffer | None = None  # features(): width * height records
         self._denoise_buf: Buffer | None = None  # denoise(): the filtered image, width * height slots
         self._sample_denoise: dict | None = None  # denoise_adaptive(): the filtered image and its variance plane
+        self._reproject_feat: list = [None, None]  # reproject_samples(): the previous and the current view's features
         self._temporal_feat: list = [None, None]  # temporal(): this call's and the previous call's features
         self._temporal_img: list = [None, None]   # ... and outputs; index _temporal_at is the history
         self._temporal_at = 0
@@ -253,7 +254,8 @@ class Raytracer:
         rtEnqueueAccumulateSamples run over the list.  At the end the statistics are resolved
         (rtEnqueueResolveSamples) into a kept buffer.  Returns the (H, W, 4) image, whose w slot is the
         pixel's sample count, and a dict: rounds run, paths traced, and the last select's selected / hot.
-        The statistics persist across calls: reset_samples() after a camera move or move_vertices().
+        The statistics persist across calls: reproject_samples() or reset_samples() after a camera move,
+        reset_samples() after move_vertices().
         frame_count and BUFFER_OUT are left as they are.  `on_sample(round, sample_frame, n, buffers)` is
         called after each sample's calls are enqueued (buffers: ids, results, stats; for tools and tests)."""
         b = self._adaptive_buffers()
@@ -298,10 +300,54 @@ class Raytracer:
 
     def reset_samples(self) -> None:
         """Zero render_adaptive()'s statistics and restart its sample frames at 1: after a camera move or
-        move_vertices() the samples taken so far are of another image."""
+        move_vertices() the samples taken so far are of another image.  After a camera move alone
+        reproject_samples() carries them over instead; after move_vertices() this stays the tool, since a
+        moved surface invalidates a reprojection that knows the camera's motion only."""
         work = self.width * self.height
         self.ctx.WriteBuffer(self._adaptive_buffers()["stats"], np.zeros(work, N.PIXEL_STATS_DTYPE))
         self._sample_frame = 1
+
+    def reproject_samples(self, prev: Camera, n_frames: int = 4, max_history: float = 16.0,
+                          depth_tolerance: float = 0.05, normal_threshold: float = 0.9) -> None:
+        """Carry render_adaptive()'s statistics across a camera move (rtEnqueueReprojectSamples), instead
+        of reset_samples().  Call it after `camera` was changed, with `prev` the camera the statistics were
+        gathered at.  Every pixel of the new view takes the mean, the per-sample variance and the sample
+        count (an integer, at most max_history) of the history pixels that show the same surface --
+        relative depth within depth_tolerance, normals' dot product at least normal_threshold -- and a
+        pixel that finds none (a disocclusion, the image's new margin) is left without samples.  The next
+        render_adaptive() round then selects those pixels and the ones that are still noisy, not the
+        whole frame; a lower max_history trusts the old samples less.  The guides are the features of
+        frames 1 .. n_frames at `prev` and at the current camera.  The result goes into a second kept
+        buffer, which becomes render_adaptive()'s statistics buffer (the two swap at every call); the
+        sample frames go on counting, so the samples that follow draw fresh seeds.  Nothing is read back;
+        the camera, frame_count and BUFFER_OUT are left as they are.  After move_vertices() use
+        reset_samples(): a moved surface invalidates a reprojection that knows the camera's motion only."""
+        b = self._adaptive_buffers()
+        work = self.width * self.height
+        if "spare" not in b:
+            b["spare"] = self.ctx.create_buffer(N.MEM_READ_WRITE, work * N.PIXEL_STATS_DTYPE.itemsize)
+        for i in range(2):
+            if self._reproject_feat[i] is None:
+                self._reproject_feat[i] = self.ctx.create_buffer(N.MEM_READ_WRITE,
+                                                                 work * N.PIXEL_FEATURES_DTYPE.itemsize)
+        hist_feat, cur_feat = self._reproject_feat
+        at, cam = self.frame_count, self.camera
+        self.frame_count = 1
+        try:
+            self.camera = prev
+            try:
+                self._enqueue_features(n_frames, hist_feat)
+            finally:
+                self.camera = cam
+            self._enqueue_features(n_frames, cur_feat)
+        finally:
+            self.frame_count = at
+            self.set_uniforms()   # (the kernel's camera slots and FRAME_COUNT, whatever was enqueued)
+        view = (tuple(cam.position), tuple(cam.front), tuple(cam.up))
+        prev_view = (tuple(prev.position), tuple(prev.front), tuple(prev.up))
+        self.ctx.ReprojectSamples(self.kernel, b["stats"], hist_feat, cur_feat, self.width, self.height, b["spare"],
+                                  view, prev_view, max_history, depth_tolerance, normal_threshold)
+        b["stats"], b["spare"] = b["spare"], b["stats"]
 
     def features(self, n_frames: int = 1) -> np.ndarray:
         """First-hit feature buffers for a denoiser (rtEnqueueFrameFeatures): an (H, W) array of
@@ -547,7 +593,7 @@ class Raytracer:
             for b in self._sample_denoise.values():
                 b.release()
             self._sample_denoise = None
-        for bufs in (self._temporal_feat, self._temporal_img):
+        for bufs in (self._temporal_feat, self._temporal_img, self._reproject_feat):
             for i in range(2):
                 if bufs[i]:
                     bufs[i].release()

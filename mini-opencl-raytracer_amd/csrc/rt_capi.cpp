@@ -45,6 +45,8 @@
 #include "rt_launch_plan.hpp"
 #include "rt_query_plan.hpp"
 #include "rt_refit.hpp"
+#include "rt_reproject.hpp"
+#include "rt_reproject_plan.hpp"
 #include "rt_scene_pack.hpp"
 #include "rt_temporal.hpp"
 #include "rt_temporal_plan.hpp"
@@ -1156,6 +1158,49 @@ int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem 
     a.depth_tolerance = p.depth_tolerance, a.normal_threshold = p.normal_threshold;
     a.k = p.k;
     return launch_on_queue(ctx, k, out, [&](hipStream_t st) { return rtt::launch_temporal(a, p, st); });
+}
+
+// ---- reprojection of the sample statistics (rt_reproject.hip; the plan: rt_reproject_plan.cpp) ------
+
+int rtEnqueueReprojectSamples(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt_mem hist_features, rt_mem cur_features,
+                              unsigned width, unsigned height, const rt_reproject_params* params, rt_mem out_stats) {
+    // 1. the handles and the plan: nothing is launched on an error
+    int rc = queue_head(ctx, k, {});
+    if (rc) return rc;
+    rtp::ReprojectIn in{};
+    in.params_ok = params != nullptr;
+    if (params) {
+        for (int c = 0; c < 3; ++c) {
+            in.cur.pos[c] = params->cur.pos[c], in.cur.front[c] = params->cur.front[c], in.cur.up[c] = params->cur.up[c];
+            in.prev.pos[c] = params->prev.pos[c], in.prev.front[c] = params->prev.front[c];
+            in.prev.up[c] = params->prev.up[c];
+        }
+        in.max_history = params->max_history;
+        in.depth_tolerance = params->depth_tolerance, in.normal_threshold = params->normal_threshold;
+    }
+    in.width = width, in.height = height;
+    in.hist_stats_ok = hist_stats && hist_stats->ctx == ctx;
+    in.hist_features_ok = hist_features && hist_features->ctx == ctx;
+    in.cur_features_ok = cur_features && cur_features->ctx == ctx;
+    in.out_ok = out_stats && out_stats->ctx == ctx;
+    in.out_is_input = out_stats && (out_stats == hist_stats || out_stats == hist_features || out_stats == cur_features);
+    in.hist_stats_bytes = in.hist_stats_ok ? hist_stats->size : 0;
+    in.hist_features_bytes = in.hist_features_ok ? hist_features->size : 0;
+    in.cur_features_bytes = in.cur_features_ok ? cur_features->size : 0;
+    in.out_bytes = in.out_ok ? out_stats->size : 0;
+    rtp::ReprojectPlan p;
+    rc = rtp::reproject_plan(in, &p);
+    if (rc) return pending_error(ctx, rc);
+    // 2. one launch, in order on the context's stream after the pending accumulations and gathers
+    rtrs::ReprojectArgs a{};
+    a.hist_stats = static_cast<const float4*>(hist_stats->dptr);
+    a.hist_features = static_cast<const float4*>(hist_features->dptr);
+    a.cur_features = static_cast<const float4*>(cur_features->dptr);
+    a.out_stats = static_cast<float4*>(out_stats->dptr);
+    a.width = p.width, a.height = p.height, a.tilesX = p.tiles_x;
+    a.max_history = p.max_history, a.depth_tolerance = p.depth_tolerance, a.normal_threshold = p.normal_threshold;
+    a.k = p.k;
+    return launch_on_queue(ctx, k, out_stats, [&](hipStream_t st) { return rtrs::launch_reproject(a, p, st); });
 }
 
 // ---- adaptive sampling (rt_adaptive.hip, rt_trace.hpp; the plans: rt_adaptive_plan.cpp) -------------
