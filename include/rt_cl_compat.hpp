@@ -130,6 +130,9 @@ public:
                                const Buffer& rays, const Buffer& seeds) const;
     inline void ResolveSamples(std::shared_ptr<CLKernel> kernel, const Buffer& stats, unsigned width, unsigned height,
                                const Buffer& out) const;
+    // one sample for ids[first, first + min(n, count's first word)) in one launch; count may be null (then n)
+    inline void SamplePixels(std::shared_ptr<CLKernel> kernel, const Buffer& ids, const Buffer* count, size_t first,
+                             size_t n, size_t nPixels, const Buffer& stats) const;
     // extensions: moving geometry (rtEnqueueUpdateVertices, rtRefitBVH); normals may be null
     void UpdateVertices(const Buffer& tris, size_t firstTri, size_t nTris, const Buffer& positions,
                         const Buffer* normals = nullptr) const {
@@ -242,6 +245,12 @@ inline void CLContext::ResolveSamples(std::shared_ptr<CLKernel> kernel, const Bu
                                       unsigned height, const Buffer& out) const {
     check(rtEnqueueResolveSamples(ctx_, kernel->GetKernel(), stats.get(), width, height, out.get()),
           "Failed to enqueue sample resolve");
+}
+inline void CLContext::SamplePixels(std::shared_ptr<CLKernel> kernel, const Buffer& ids, const Buffer* count, size_t first,
+                                    size_t n, size_t nPixels, const Buffer& stats) const {
+    check(rtEnqueueSamplePixels(ctx_, kernel->GetKernel(), ids.get(), count ? count->get() : nullptr, first, n, nPixels,
+                                stats.get()),
+          "Failed to enqueue pixel samples");
 }
 inline void CLContext::RefitBVH(std::shared_ptr<CLKernel> kernel) const {
     check(rtRefitBVH(ctx_, kernel->GetKernel()), "Failed to refit BVH");

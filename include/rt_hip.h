@@ -470,6 +470,47 @@ int rtEnqueueSelectPixels(rt_context ctx, rt_kernel k, rt_mem stats, unsigned wi
 int rtEnqueueCameraPathsFor(rt_context ctx, rt_kernel k, rt_mem ids, size_t first, size_t n, rt_mem rays, rt_mem seeds);
 int rtEnqueueResolveSamples(rt_context ctx, rt_kernel k, rt_mem stats, unsigned width, unsigned height, rt_mem out);
 
+/* ---- adaptive sampling: one sample for the listed pixels in one launch (extension) ----------------
+ * rtEnqueueSamplePixels is the round's three calls -- rtEnqueueCameraPathsFor, rtEnqueueTracePaths
+ * (RT_TRACE_LINEAR, the seeds given) and rtEnqueueAccumulateSamples -- as one kernel that keeps the ray,
+ * the seed and the radiance in registers, and that can take its record count from device memory, so that a
+ * round needs no host read:
+ *   rtEnqueueSelectPixels -> rtEnqueueSamplePixels(ids, count = the select's `result`, n = width * height).
+ *
+ * Let m = n when `count` is NULL, else m = min(n, c) with c the first uint32 of `count`
+ * (rt_select_result.selected) as it stands when the launch runs.  The word is compared and clamped against
+ * n, which the host has range-checked; it never forms an address.  For records i in [first, first + m),
+ * gid = ids[i]:
+ *   - gid >= n_pixels: the record is skipped before anything is traced; stats is untouched and nothing of
+ *     it is counted in rt_stats.  (A gid becomes an address only after this test.)
+ *   - otherwise {ray, seed} are exactly what rtEnqueueCameraPathsFor writes for gid (k's WIDTH, HEIGHT,
+ *     FRAME_COUNT and camera slots, in k's math mode), s is the radiance rtEnqueueTracePaths returns for
+ *     that ray and seed (RT_TRACE_LINEAR; scene, materials, LIGHT_BOUNCES, LIGHT_TYPE, SKYBOX_INTENSITY and
+ *     rtKernelForceGlobalScene as bound to k), and stats[gid] receives rtEnqueueAccumulateSamples' update by
+ *     s: the non-finite skip applies, reserved[2] is kept as found, mean_y' = mean_y + d / n' is the IEEE
+ *     quotient in every math mode, and a LIGHT_BOUNCES of 0 adds a zero sample as the composed calls do.
+ * `stats` ends with the bytes the three calls leave over the same range with n replaced by m, in every math
+ * mode.  Repeated ids: some mixture of the duplicates' updates, nothing outside that record.  Records of
+ * `ids` and `stats` outside those named are not touched; `ids` and `count` are only read.  A device count
+ * of 0 still launches; the kernel finds nothing to do.
+ *
+ * Ordering is a query's (queued, coalesced frames first, after the pending accumulations, "another call
+ * touching the context"); `stats` counts as written.  With stats on it adds rays, node visits, triangle
+ * tests and hits as rtEnqueueTracePaths would for the in-range records; with timing on it is one launch.
+ * After rtEnqueueUpdateVertices + rtRefitBVH it sees the moved geometry without a full preparation, and it
+ * walks the node-collapse records whenever the trace would.
+ *
+ * Errors (nothing prepared or launched), in this order after the context and the kernel: first + n > 2^31,
+ * n_pixels 0 or above 2^31 RT_INVALID_VALUE; `ids` or `stats` NULL or of another context, a non-NULL
+ * `count` of another context, `stats` the same buffer as `ids` or `count`, or `count` the same buffer as
+ * `ids` RT_INVALID_MEM_OBJECT; the range beyond `ids` (4 B per record), `count` under 16 B or `stats` under
+ * 32 * n_pixels bytes RT_INVALID_BUFFER_SIZE; one of WIDTH, HEIGHT, FRAME_COUNT or the camera slots unset,
+ * WIDTH or HEIGHT zero, the scene, node or material slot unbound, or LIGHT_BOUNCES, LIGHT_TYPE or
+ * SKYBOX_INTENSITY unset RT_INVALID_KERNEL_ARGS; n == 0 RT_SUCCESS with nothing prepared or launched; then
+ * the scene preparation's own errors, and a leaf of more than 127 triangles RT_INVALID_OPERATION. */
+int rtEnqueueSamplePixels(rt_context ctx, rt_kernel k, rt_mem ids, rt_mem count /* may be NULL */, size_t first,
+                          size_t n, size_t n_pixels, rt_mem stats);
+
 /* ---- surface records of ray hits, and first-hit feature buffers ----------------------------
  * rtEnqueueHitSurfaces writes, for records [first, first + n) of `rays` (rt_ray) and `hits`
  * (rt_ray_hit), the same slots of `surfaces` (rt_surface); the other slots are not touched.  The

@@ -241,6 +241,7 @@ _HIP_PROTOS = {
                                              ctypes.POINTER(ADAPTIVE_PARAMS), _vp, _vp]),
     "rtEnqueueCameraPathsFor": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
     "rtEnqueueResolveSamples": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint, _vp]),
+    "rtEnqueueSamplePixels": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtEnqueueHitSurfaces": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtEnqueueFrameFeatures": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint, _vp]),
     "rtEnqueueDenoise": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,

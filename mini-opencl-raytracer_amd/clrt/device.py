@@ -148,6 +148,15 @@ class CLContext:
         check(self._lib.rtEnqueueResolveSamples(self.handle, kernel.handle, stats.handle, int(width), int(height),
                                                 out.handle), "Failed to enqueue sample resolve")
 
+    def SamplePixels(self, kernel: "CLKernel", ids: "Buffer", n: int, n_pixels: int, stats: "Buffer",
+                     count: "Buffer | None" = None, first: int = 0) -> None:
+        """rtEnqueueSamplePixels: one sample for the pixels ids[first, first + m) in one launch -- the camera
+        path, its trace and the statistics update -- with m = n, or min(n, the first uint32 of `count`) read on
+        the device when the launch runs (a SelectPixels result, no host read in between)."""
+        check(self._lib.rtEnqueueSamplePixels(self.handle, kernel.handle, ids.handle,
+                                              count.handle if count is not None else None, int(first), int(n),
+                                              int(n_pixels), stats.handle), "Failed to enqueue pixel samples")
+
     def HitSurfaces(self, kernel: "CLKernel", rays: "Buffer", hits: "Buffer", surfaces: "Buffer", n: int,
                     first: int = 0) -> None:
         """rtEnqueueHitSurfaces: the surface (N.SURFACE_DTYPE: position, shading and geometric normal,

@@ -244,7 +244,8 @@ class Raytracer:
         return self._adaptive
 
     def render_adaptive(self, rounds: int, samples_per_round: int = 1, threshold: float = 0.05, floor_y: float = 0.01,
-                        min_samples: int = 4, max_samples: int = 64, radius: int = 1, on_sample=None) -> tuple:
+                        min_samples: int = 4, max_samples: int = 64, radius: int = 1, on_sample=None,
+                        fused: bool = False, sync_every: int = 1) -> tuple:
         """Progressive rendering that puts its paths where the noise is.  Per round the device selects the
         pixels that still need samples (rtEnqueueSelectPixels: fewer than min_samples, or within `radius`
         of a pixel whose mean luminance has a relative standard error above `threshold`, and fewer than
@@ -257,9 +258,20 @@ class Raytracer:
         The statistics persist across calls: reproject_samples() or reset_samples() after a camera move,
         reset_samples() after move_vertices().
         frame_count and BUFFER_OUT are left as they are.  `on_sample(round, sample_frame, n, buffers)` is
-        called after each sample's calls are enqueued (buffers: ids, results, stats; for tools and tests)."""
+        called after each sample's calls are enqueued (buffers: ids, results, stats; for tools and tests).
+
+        fused=True runs each sample as one rtEnqueueSamplePixels launch that takes its record count from the
+        select's result on the device: a round is the select, a non-blocking read of the result into that
+        round's row of a host array, and the samples; the host waits only after every sync_every-th round and
+        at the end, and then stops at the first round it finds with nothing selected.  Rounds enqueued past
+        such a round change nothing (every later select finds nothing either), so the statistics, the image
+        and the dict are those of fused=False for any sync_every.  on_sample then gets results=None."""
         b = self._adaptive_buffers()
         work = self.width * self.height
+        if fused:
+            info = self._adaptive_rounds_fused(b, int(rounds), int(samples_per_round), max(1, int(sync_every)), on_sample,
+                                               (threshold, floor_y, min_samples, max_samples, radius))
+            return self._resolve_adaptive(b), info
         rb, sb, ob = self._trace_buffers(work)
         res = np.zeros(1, N.SELECT_RESULT_DTYPE)
         info = {"rounds": 0, "paths": 0, "selected": 0, "hot": 0}
@@ -287,10 +299,50 @@ class Raytracer:
         finally:
             self.frame_count = at
             self.kernel.set_uint(N.FRAME_COUNT, at)
+        return self._resolve_adaptive(b), info
+
+    def _resolve_adaptive(self, b: dict) -> np.ndarray:
         self.ctx.ResolveSamples(self.kernel, b["stats"], self.width, self.height, b["image"])
         out = np.empty((self.height, self.width, 4), np.float32)
         self.ctx.ReadBuffer(b["image"], out, blocking=True)
-        return out, info
+        return out
+
+    def _adaptive_rounds_fused(self, b: dict, rounds: int, per_round: int, sync_every: int, on_sample, params) -> dict:
+        """render_adaptive(fused=True)'s rounds: queued, with a wait after every sync_every-th one."""
+        work = self.width * self.height
+        rows = np.zeros(max(rounds, 1), N.SELECT_RESULT_DTYPE)   # row r: round r's select result, once waited for
+        info = {"rounds": 0, "paths": 0, "selected": 0, "hot": 0}
+        at, frame0 = self.frame_count, self._sample_frame
+        seen, done = 0, False
+        try:
+            for rnd in range(rounds):
+                self.ctx.SelectPixels(self.kernel, b["stats"], self.width, self.height, b["ids"], b["result"], *params)
+                self.ctx.ReadBuffer(b["result"], rows[rnd:rnd + 1], blocking=False)
+                for s in range(per_round):
+                    # (the frames of the rounds so far, all of which selected something if this one does)
+                    self.frame_count = frame0 + rnd * per_round + s
+                    self.set_uniforms()
+                    self.ctx.SamplePixels(self.kernel, b["ids"], work, work, b["stats"], count=b["result"])
+                    if on_sample is not None:
+                        on_sample(rnd, self.frame_count, None, {"ids": b["ids"], "results": None, "stats": b["stats"]})
+                if (rnd + 1) % sync_every == 0 or rnd + 1 == rounds:
+                    self.ctx.Finish()
+                    while seen <= rnd and not done:
+                        n = int(rows["selected"][seen])
+                        info["selected"], info["hot"] = n, int(rows["hot"][seen])
+                        done = n == 0
+                        if not done:
+                            info["rounds"] += 1
+                            info["paths"] += n * per_round
+                        seen += 1
+                    if done:
+                        break
+        finally:
+            self.ctx.Finish()   # (no read may land in `rows` after this returns)
+            self._sample_frame = frame0 + info["rounds"] * per_round
+            self.frame_count = at
+            self.kernel.set_uint(N.FRAME_COUNT, at)
+        return info
 
     def sample_stats(self) -> np.ndarray:
         """render_adaptive()'s per-pixel statistics as an (H, W) array of N.PIXEL_STATS_DTYPE."""

@@ -31,14 +31,20 @@ RTA_FN bool finite_sample(float r, float g, float b) { return finite_channel(r) 
 
 RTA_FN float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
-// Welford's update of the luminance moments by one sample
-RTA_FN Moments sample_update(Moments s, float y) {
+// Welford's update of the luminance moments by one sample.  `div(a, b)` is the IEEE quotient a / b: a
+// translation unit whose `/` is not that one (the shipped kernels') passes its own (rt_sample.hpp)
+template <class Div>
+RTA_FN Moments sample_update(Moments s, float y, Div div) {
     const float n1 = s.n + 1.0f;
     const float d = y - s.mean_y;
-    const float mean1 = s.mean_y + d / n1;
+    const float mean1 = s.mean_y + div(d, n1);
     const float m21 = s.m2_y + d * (y - mean1);
     return Moments{n1, mean1, m21};
 }
+struct Quotient {
+    RTA_FN float operator()(float a, float b) const { return a / b; }
+};
+RTA_FN Moments sample_update(Moments s, float y) { return sample_update(s, y, Quotient{}); }
 
 // the variance of the mean luminance above (threshold * (mean + floor))^2; never with fewer than two samples
 RTA_FN bool is_hot(Moments s, float threshold, float floor_y) {

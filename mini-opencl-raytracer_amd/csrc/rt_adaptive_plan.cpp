@@ -1,5 +1,5 @@
-// rt_adaptive_plan.cpp -- the plans of the four adaptive-sampling calls (rt_adaptive_plan.hpp): the
-// argument checks in their documented order, the grids and the select's scratch layout.  Pure arithmetic,
+// rt_adaptive_plan.cpp -- the plans of the adaptive-sampling calls (rt_adaptive_plan.hpp): the argument
+// checks in their documented order (the fused sample's too: sample_check), the grids and the select's scratch layout.  Pure arithmetic,
 // kept where a CPU test can sweep it (tests/native/adaptive_plan_main.cpp).
 #include "rt_adaptive_plan.hpp"
 
@@ -83,6 +83,21 @@ int paths_for_plan(const PathsForIn& in, PathsForPlan* out) {
     out->nothing = in.n == 0;
     out->first = (uint32_t)in.first, out->count = (uint32_t)in.n;
     out->grid = groups(in.n, kAdaptiveThreads);
+    return RT_SUCCESS;
+}
+
+int sample_check(const SampleIn& in, SamplePlan* out) {
+    *out = SamplePlan{};
+    if (!range_ok(in.first, in.n)) return RT_INVALID_VALUE;
+    if (in.n_pixels == 0 || in.n_pixels > kAdaptiveMaxRecords) return RT_INVALID_VALUE;
+    if (!in.ids_ok || !in.stats_ok || (in.count_given && !in.count_ok) || in.aliased) return RT_INVALID_MEM_OBJECT;
+    if (!range_inside(in.first, in.n, in.ids_bytes, kIdBytes)) return RT_INVALID_BUFFER_SIZE;
+    if (in.count_given && in.count_bytes < kSelectResultBytes) return RT_INVALID_BUFFER_SIZE;
+    if (in.n_pixels > in.stats_bytes / kStatsBytes) return RT_INVALID_BUFFER_SIZE;
+    if (!in.slots_set || in.width == 0 || in.height == 0) return RT_INVALID_KERNEL_ARGS;
+    if (!in.scene_bound || !in.lights_set) return RT_INVALID_KERNEL_ARGS;
+    out->nothing = in.n == 0;
+    out->first = (uint32_t)in.first, out->n = (uint32_t)in.n, out->n_pixels = (uint32_t)in.n_pixels;
     return RT_SUCCESS;
 }
 

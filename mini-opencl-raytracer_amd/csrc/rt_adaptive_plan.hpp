@@ -1,6 +1,6 @@
-// rt_adaptive_plan.hpp -- how the four adaptive-sampling calls (rtEnqueueAccumulateSamples,
-// rtEnqueueSelectPixels, rtEnqueueCameraPathsFor, rtEnqueueResolveSamples) are checked and launched, as
-// pure functions of plain values (rt_adaptive_plan.cpp): no HIP, no allocation, no globals.  The C ABI
+// rt_adaptive_plan.hpp -- how the adaptive-sampling calls (rtEnqueueAccumulateSamples, rtEnqueueSelectPixels,
+// rtEnqueueCameraPathsFor, rtEnqueueResolveSamples and the fused rtEnqueueSamplePixels) are checked and launched,
+// as pure functions of plain values (rt_adaptive_plan.cpp): no HIP, no allocation, no globals.  The C ABI
 // fills an *In, calls the plan and launches the kernels of rt_adaptive.hip (the indexed camera paths:
 // rt_trace.hpp) with the plan's grids.
 //
@@ -14,6 +14,8 @@
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "rt_trace_plan.hpp"
 
 namespace rtp {
 
@@ -107,5 +109,64 @@ struct ResolvePlan {
 // RT_INVALID_MEM_OBJECT (a buffer not the context's; out is stats), RT_INVALID_BUFFER_SIZE (stats below
 // 32 B per pixel, out below 16 B).
 int resolve_plan(const ResolveIn& in, ResolvePlan* out);
+
+// ---- rtEnqueueSamplePixels ------------------------------------------------------------------------
+// One launch of the trace's kernel shape (rt_sample.hpp) over the records ids[first, first + m), m = n or
+// min(n, the device count): the checks are this call's, the variant, the LDS size and the grid are the
+// trace's (trace_shape / trace_grid) with n as the capacity.
+struct SampleIn {
+    uint64_t first, n, n_pixels;
+    bool ids_ok, stats_ok;             // not NULL and a buffer of this context
+    bool count_given, count_ok;        // `count` is not NULL; ... and a buffer of this context
+    bool aliased;                      // stats is ids or count, or count is ids
+    uint64_t ids_bytes, count_bytes, stats_bytes;
+    bool slots_set;                    // WIDTH, HEIGHT, FRAME_COUNT and the three camera slots
+    uint32_t width, height;            // k's slots (looked at only when set)
+    bool scene_bound;                  // scene, node and material slots are bound
+    bool lights_set;                   // LIGHT_BOUNCES, LIGHT_TYPE and SKYBOX_INTENSITY are set
+    // the kernel's settings and its packed scene, as rtEnqueueTracePaths fills them (sample_shape; the
+    // call's own fields of it are not looked at)
+    TraceIn scene;
+};
+struct SamplePlan {
+    bool nothing;                      // n == 0: no preparation, no launch
+    uint32_t first, n, n_pixels;
+    uint32_t capUnits;                 // 64-record units of n: the most the device count can leave
+    TracePlan trace;                   // variant, LDS bytes, walk records, thresholds, grid
+};
+// The rows that need no packed scene, in this order: RT_INVALID_VALUE (first + n > 2^31; n_pixels 0 or >
+// 2^31), RT_INVALID_MEM_OBJECT (ids or stats not a buffer of the context; a given count that is not; two of
+// them the same), RT_INVALID_BUFFER_SIZE (the range beyond ids; count below 16 B; stats below 32 B per
+// pixel), RT_INVALID_KERNEL_ARGS (a camera slot unset; WIDTH or HEIGHT zero; scene, node or material slot
+// unbound; a light slot unset).  RT_SUCCESS otherwise, out->nothing when n == 0.
+int sample_check(const SampleIn& in, SamplePlan* out);
+
+// After the scene's preparation: sample_check, then trace_shape's RT_INVALID_OPERATION (a leaf of more than
+// 127 triangles) and everything up to the LDS size.  Inline, like sample_grid: they call into
+// rt_trace_plan.cpp, which the programs that link rt_adaptive_plan.cpp alone do not.
+inline TraceIn sample_trace_in(const SampleIn& in) {
+    TraceIn t = in.scene;
+    t.params_given = true, t.encoding = kTraceLinear;
+    t.first = in.first, t.n = in.n;
+    t.rays_ok = t.out_ok = true, t.seeds_given = t.seeds_ok = false, t.out_is_input = false;
+    t.rays_bytes = t.out_bytes = ~0ull, t.seeds_bytes = 0;  // (no such buffers: the range was checked against ids)
+    t.scene_bound = in.scene_bound, t.lights_set = in.lights_set;
+    return t;
+}
+inline int sample_shape(const SampleIn& in, SamplePlan* out) {
+    int rc = sample_check(in, out);
+    if (rc || out->nothing) return rc;
+    rc = trace_shape(sample_trace_in(in), &out->trace);
+    if (rc) return rc;
+    out->capUnits = out->trace.nUnits;
+    return 0;
+}
+// The grid, from the occupancy (workgroups per CU) of the kernel sample_shape chose at its LDS size.
+inline void sample_grid(const SampleIn& in, int occ, SamplePlan* out) { trace_grid(sample_trace_in(in), occ, &out->trace); }
+inline int sample_plan(const SampleIn& in, int occ, SamplePlan* out) {
+    const int rc = sample_shape(in, out);
+    if (rc == 0 && !out->nothing) sample_grid(in, occ, out);
+    return rc;
+}
 
 }  // namespace rtp

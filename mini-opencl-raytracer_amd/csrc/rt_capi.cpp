@@ -1294,6 +1294,62 @@ int rtEnqueueCameraPathsFor(rt_context ctx, rt_kernel k, rt_mem ids, size_t firs
     });
 }
 
+// One sample for the listed pixels in one launch (rt_sample.hpp): rtEnqueueTracePaths' six steps, with the
+// camera slots and the statistics where the trace has the caller's arrays.
+int rtEnqueueSamplePixels(rt_context ctx, rt_kernel k, rt_mem ids, rt_mem count, size_t first, size_t n, size_t n_pixels,
+                          rt_mem stats) {
+    // 1. the handles, then the coalesced frames: another call touches the context
+    int rc = queue_head(ctx, k, {});
+    if (rc) return rc;
+    // 2. the arguments, in the plan's order: no scene is packed and nothing launched on an error
+    rtp::SampleIn in{};
+    in.first = first, in.n = n, in.n_pixels = n_pixels;
+    in.ids_ok = ids && ids->ctx == ctx, in.stats_ok = stats && stats->ctx == ctx;
+    in.count_given = count != nullptr, in.count_ok = count && count->ctx == ctx;
+    in.aliased = (stats && (stats == ids || stats == count)) || (count && count == ids);
+    in.ids_bytes = in.ids_ok ? ids->size : 0, in.stats_bytes = in.stats_ok ? stats->size : 0;
+    in.count_bytes = in.count_ok ? count->size : 0;
+    in.slots_set = k->args.has({RT_ARG_WIDTH, RT_ARG_HEIGHT, RT_ARG_FRAME_COUNT, RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT,
+                                RT_ARG_CAMERA_UP});
+    if (in.slots_set) in.width = k->args.width(), in.height = k->args.height();
+    in.scene_bound = k->args.has({RT_ARG_BUFFER_SCENE, RT_ARG_BUFFER_NODE, RT_ARG_BUFFER_MATERIAL});
+    in.lights_set = k->args.has({RT_ARG_LIGHT_BOUNCES, RT_ARG_LIGHT_TYPE, RT_ARG_SKYBOX_INTENSITY});
+    rtp::SamplePlan p;
+    rc = rtp::sample_check(in, &p);
+    if (rc || p.nothing) return pending_error(ctx, rc);
+    // 3. the scene, packed and validated as a render launch does
+    rc = prepare_scene(k, k->args);
+    if (rc) return rc;
+    // 4. the plan, with the kernel's occupancy at the LDS size it chose
+    rtp::TraceIn& t = in.scene;
+    t.math = k->math, t.stats = k->stats;
+    const rti::DeviceScene& sc = k->scene;
+    t.n_nodes = sc.n_nodes(), t.n_tris = sc.n_tris(), t.n_mats = sc.n_mats();
+    t.oct_ok = sc.oct_ok();
+    t.goct_available = sc.goct() != nullptr, t.goct_b = sc.goct_b();
+    t.force_global = k->force_global;
+    t.tune = k->tune;
+    t.num_cus = ctx->num_cus;
+    rc = rtp::sample_shape(in, &p);
+    if (rc || p.nothing) return pending_error(ctx, rc);
+    rtp::sample_grid(in, k->occ.get(rtk::Family::Sample, p.trace.variant, p.trace.smem), &p);
+    // 5. the arguments: the trace's, the camera's, the ids, the count and the statistics
+    rtk::KernelArgs a;
+    fill_trace_args(k, p.trace, &a);
+    fill_camera(k->args, k->args.frame_count(), &a);
+    rtk::SampleArgs q{};
+    q.ids = static_cast<const uint32_t*>(ids->dptr);
+    q.count = count ? static_cast<const uint32_t*>(count->dptr) : nullptr;
+    q.stats = static_cast<float4*>(stats->dptr);
+    q.first = p.first, q.n = p.n, q.nPixels = p.n_pixels;
+    q.refillMin = p.trace.refillMin, q.shadeMin = p.trace.shadeMin;
+    // 6. the launch, on the context's stream after the pending accumulations and gathers
+    k->last_lds = p.trace.variant.lds();
+    return launch_on_queue(ctx, k, stats, [&](hipStream_t st) {
+        return rtk::launch_sample(a, q, p.trace.variant, p.trace.grid, p.trace.smem, st);
+    });
+}
+
 int rtEnqueueResolveSamples(rt_context ctx, rt_kernel k, rt_mem stats, unsigned width, unsigned height, rt_mem out) {
     // 1. the handles and the plan: nothing is launched on an error
     int rc = queue_head(ctx, k, {});

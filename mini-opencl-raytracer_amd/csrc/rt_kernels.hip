@@ -115,13 +115,13 @@ static const Policy& policy(int math) {
                                      pack_mats,
                                      hit_surfaces<MathDeviceLib, false>, hit_surfaces<MathDeviceLib, true>,
                                      trace_pick<MathDeviceLib>, camera_paths<MathDeviceLib>,
-                                     camera_paths_for<MathDeviceLib>};
+                                     camera_paths_for<MathDeviceLib>, sample_pick<MathDeviceLib>};
     static const Policy pinned = {pick_entry<MathPinned>,   wf_pick<MathPinned>,  query_pick<MathPinned>,
                                   accum_frames<MathPinned>, accum_key<MathPinned>, camera_rays<MathPinned>,
                                   pack_mats,
                                   hit_surfaces<MathPinned, false>, hit_surfaces<MathPinned, true>,
                                      trace_pick<MathPinned>, camera_paths<MathPinned>,
-                                     camera_paths_for<MathPinned>};
+                                     camera_paths_for<MathPinned>, sample_pick<MathPinned>};
     return math == MathShipped::kId ? shipped_policy() : math == MathDeviceLib::kId ? devicelib : pinned;
 }
 
@@ -174,6 +174,13 @@ hipError_t launch_trace(const KernelArgs& a, const TraceArgs& q, const Variant& 
     return hipGetLastError();
 }
 
+// ---- one adaptive sample per listed pixel (rt_sample.hpp) -----------------------------------------
+hipError_t launch_sample(const KernelArgs& a, const SampleArgs& q, const Variant& v, unsigned grid, size_t smem,
+                         hipStream_t st) {
+    hipLaunchKernelGGL(policy(v.math).sample(v), dim3(grid), dim3(kTraceThreads), smem, st, a, q);
+    return hipGetLastError();
+}
+
 hipError_t launch_camera_paths(const KernelArgs& a, float4* rays, uint32_t* seeds, uint32_t n, int math,
                                hipStream_t st) {
     const dim3 grid((unsigned)(((uint64_t)n + 255u) / 256u));
@@ -209,6 +216,7 @@ int OccupancyCache::get(Family f, const Variant& v, size_t smem) {
         case Family::WfShade: fn = reinterpret_cast<const void*>(p.wavefront(v).shade), threads = kWfShadeThreads; break;
         case Family::Query: fn = reinterpret_cast<const void*>(p.query(v)), threads = kQueryThreads; break;
         case Family::Trace: fn = reinterpret_cast<const void*>(p.trace(v)), threads = kTraceThreads; break;
+        case Family::Sample: fn = reinterpret_cast<const void*>(p.sample(v)), threads = kTraceThreads; break;
     }
     int blocks = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, threads, smem) != hipSuccess) blocks = 1;

@@ -147,6 +147,22 @@ hipError_t launch_camera_paths(const KernelArgs& a, float4* rays, uint32_t* seed
 hipError_t launch_camera_paths_for(const KernelArgs& a, const uint32_t* ids, uint32_t first, uint32_t n, float4* rays,
                                    uint32_t* seeds, unsigned grid, int math, hipStream_t st);
 
+// ---- one adaptive sample per listed pixel (rt_sample.hpp) -----------------------------------------
+// rtEnqueueSamplePixels: KernelArgs carries what rtEnqueueTracePaths' does plus width, height,
+// frameCount and the camera slots.
+struct SampleArgs {
+    const uint32_t* ids;      // work-item ids; records [first, first + m) are sampled
+    const uint32_t* count;    // null: m = n; else m = min(n, count[0]), read on the device
+    float4* stats;            // rt_pixel_stats records as 2 x float4, nPixels of them
+    uint32_t first, n;        // first + n <= 2^31, inside `ids`
+    uint32_t nPixels;         // ids from nPixels on are skipped
+    uint32_t refillMin;       // take new records once this many lanes are free
+    uint32_t shadeMin;        // shade once this many lanes' walks have ended
+};
+using SampleKernelFn = void (*)(KernelArgs, SampleArgs);
+hipError_t launch_sample(const KernelArgs& a, const SampleArgs& q, const Variant& v, unsigned grid, size_t smem,
+                         hipStream_t st);
+
 // ---- surface records of ray hits (rt_surface.hpp) ------------------------------------------------
 // rtEnqueueHitSurfaces / rtEnqueueFrameFeatures: KernelArgs carries trisFull (uvs), packedTris (e1, e2),
 // shadeTris (normals, mtlIndex), nTris and -- accumulating variant only -- materials; the rest is unused.
@@ -174,13 +190,13 @@ hipError_t launch_pack(const rt_cl_triangle* tris, uint32_t n_tris, float4* pt, 
 // Workgroups per CU of a kernel at a dynamic LDS size, remembered per (kernel family, variant): the
 // runtime is asked on the first use and again when the LDS size differs.  The kernel is picked as
 // the launch picks it, from the same Variant.
-enum class Family : int { Entry, WfExtend, WfShade, Query, Trace };
+enum class Family : int { Entry, WfExtend, WfShade, Query, Trace, Sample };
 struct OccupancyCache {
     struct Entry {
         int blocks;   // 0: not asked yet
         size_t smem;
     };
-    Entry e[(int)Family::Trace + 1][kVariantSlots] = {};
+    Entry e[(int)Family::Sample + 1][kVariantSlots] = {};
     int get(Family f, const Variant& v, size_t smem);
 };
 
@@ -199,6 +215,7 @@ struct Policy {
     TraceKernelFn (*trace)(const Variant&);
     void (*camera_paths)(KernelArgs, float4*, uint32_t*, uint32_t);
     void (*camera_paths_for)(KernelArgs, const uint32_t*, uint32_t, uint32_t, float4*, uint32_t*);
+    SampleKernelFn (*sample)(const Variant&);
 };
 const Policy& shipped_policy();
 // the step schedule's entry points are specialised per launch kind (step_body kMode: 1 fused, 2

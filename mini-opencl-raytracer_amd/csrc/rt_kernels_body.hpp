@@ -1956,4 +1956,5 @@ __device__ __forceinline__ void material_record(const rt_cl_material& m, float4*
 #include "rt_wavefront.hpp"
 #include "rt_query.hpp"
 #include "rt_trace.hpp"
+#include "rt_sample.hpp"
 #include "rt_surface.hpp"

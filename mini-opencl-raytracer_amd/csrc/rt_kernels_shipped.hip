@@ -64,7 +64,7 @@ const Policy& shipped_policy() {
                                    pack_mats_shipped,
                                    hit_surfaces<MathShipped, false>, hit_surfaces<MathShipped, true>,
                                    trace_pick<MathShipped>, camera_paths<MathShipped>,
-                                   camera_paths_for<MathShipped>};
+                                   camera_paths_for<MathShipped>, sample_pick<MathShipped>};
     return shipped;
 }
 

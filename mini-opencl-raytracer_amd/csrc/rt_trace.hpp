@@ -25,8 +25,54 @@ namespace rtk {
 
 constexpr uint32_t kTraceRingF4 = kTraceRingBytes / 16u;  // float4 per wave: 128 of rays, 16 of seeds
 
-template <class M, bool kStats, bool kBofs, bool kGlobalOct>
-__device__ __forceinline__ void trace_body(const KernelArgs& a, const TraceArgs& q) {
+// The loop's two ends -- where a wave's records come from and where a finished path goes -- are a small
+// type the loop is instantiated over; everything between them (the ring's take, the walk, the shading
+// round) is one text.  An Ends type provides, per lane unless marked wave-uniform:
+//   uint32_t n_units()                          wave-uniform: 64-record units of the launch
+//   uint32_t fill(u0, lane, ring, ring_seed)    wave-uniform result: loads the unit whose first record is
+//                                               u0 into ring entries [0, result)
+//   void take(slot, e0)                         the lane takes entry `slot`, whose first vector is e0
+//   void unwalked()                             LIGHT_BOUNCES 0: the taken record ends without a walk
+//   float tmin(e0)                              else: the lane starts its walk; where the first segment's
+//                                               interval starts
+//   void first_hit(prim)                        the first segment's primitive (-1: a miss)
+//   void finish(r)                              the path's radiance, clamped at zero
+// TraceEnds is rtEnqueueTracePaths: records from the caller's arrays, a 16-B result per record.
+struct TraceEnds {
+    const TraceArgs& q;
+    uint32_t rc_base = 0;  // wave-uniform: first record of the ring's unit
+    uint32_t pos = 0;
+    int32_t prim0 = -1;
+
+    __device__ __forceinline__ uint32_t n_units() const { return q.nUnits; }
+    // the unit's rays as 128 float4s, two coalesced loads per lane, and its seeds, one 4-B load per
+    // lane or seed_base + the record's index (the last unit of the range may be partial)
+    __device__ __forceinline__ uint32_t fill(uint32_t u0, uint32_t lane, float4* ring, uint32_t* ring_seed) {
+        rc_base = q.first + u0;
+        const uint32_t rc_n = min(64u, q.count - u0);
+        const float4* src = q.rays + 2 * (size_t)rc_base;
+        if (lane < 2u * rc_n) ring[lane] = src[lane];
+        if (lane + 64u < 2u * rc_n) ring[lane + 64u] = src[lane + 64u];
+        if (lane < rc_n) ring_seed[lane] = q.seeds ? q.seeds[(size_t)rc_base + lane] : q.seedBase + (rc_base + lane);
+        return rc_n;
+    }
+    __device__ __forceinline__ void take(uint32_t slot, const float4&) { pos = rc_base + slot; }
+    // Render's loop does not run: radiance 0 (either encoding), no first hit
+    __device__ __forceinline__ void unwalked() { q.out[pos] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1)); }
+    __device__ __forceinline__ float tmin(const float4& e0) {
+        prim0 = -1;  // (the walk starts: no first hit yet)
+        return e0.w;
+    }
+    __device__ __forceinline__ void first_hit(int32_t prim) { prim0 = prim; }
+    template <class M>
+    __device__ __forceinline__ void finish(F3 r) {
+        if (q.encoding != 0) r = gamma_out<M>(0u, f3s(0.0f), r);
+        q.out[pos] = make_float4(r.x, r.y, r.z, __int_as_float(prim0));
+    }
+};
+
+template <class M, bool kStats, bool kBofs, bool kGlobalOct, class Ends>
+__device__ __forceinline__ void trace_loop(const KernelArgs& a, Ends& e, uint32_t refillMin, uint32_t shadeMin) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     const uint32_t tid = threadIdx.x, nthr = blockDim.x;
     SceneView sc;
@@ -56,18 +102,16 @@ __device__ __forceinline__ void trace_body(const KernelArgs& a, const TraceArgs&
     uint32_t* ring_seed = reinterpret_cast<uint32_t*>(ring + 128);
     const uint32_t bounces = (uint32_t)a.lightBounces;
 
-    uint32_t unit = wave;                         // wave-uniform: next unit of this wave
-    uint32_t rc_base = 0, rc_head = 0, rc_n = 0;  // wave-uniform: ring entries [rc_head, rc_head + rc_n) of
-                                                  // the unit whose first record is rc_base
-    bool exhausted = false;                       // wave-uniform
+    uint32_t unit = wave;            // wave-uniform: next unit of this wave
+    uint32_t rc_head = 0, rc_n = 0;  // wave-uniform: ring entries [rc_head, rc_head + rc_n) of the loaded unit
+    bool exhausted = false;          // wave-uniform
 
     LaneStats st;
     Ray ray{};
     Traversal h{0.0f, -1, 0.0f, 0.0f};
     F3 radiance = f3s(0.0f), beta = f3s(1.0f);
     float tmin = 0.0f;
-    uint32_t pos = 0, seed = 0, bounce = 0;
-    int32_t prim0 = -1;
+    uint32_t seed = 0, bounce = 0;
     // the walk word as in query_body: node < 2^24, leaf code, END (a.nNodes: the walk is over, the lane
     // waits for its shading round), kNotWalking (the lane is free)
     uint32_t cur = kNotWalking, skip = 0u;
@@ -76,48 +120,38 @@ __device__ __forceinline__ void trace_body(const KernelArgs& a, const TraceArgs&
         uint32_t n_trav = popc_ballot(cur < kLeafMin && cur != a.nNodes);
         uint32_t n_leaf = popc_ballot((int32_t)cur >= (int32_t)kLeafMin);
         uint32_t n_ready = popc_ballot(cur == a.nNodes);
-        if (!exhausted && 64u - (n_trav + n_leaf + n_ready) >= q.refillMin) {
+        if (!exhausted && 64u - (n_trav + n_leaf + n_ready) >= refillMin) {
             // ---- free lanes take records from the ring; an empty ring loads the next unit -------
             for (;;) {
                 const bool idle = cur == kNotWalking;
                 const unsigned long long im = __ballot(idle);
                 if (im == 0ull) break;
                 if (rc_n == 0u) {
-                    if (unit >= q.nUnits) {
+                    if (unit >= e.n_units()) {
                         exhausted = true;
                         break;
                     }
-                    // the unit's rays as 128 float4s, two coalesced loads per lane, and its seeds, one
-                    // 4-B load per lane or seed_base + the record's index (the last unit of the range
-                    // may be partial)
                     const uint32_t u0 = unit * 64u;
                     unit += nwaves;
-                    rc_base = q.first + u0;
-                    rc_n = min(64u, q.count - u0);
+                    rc_n = e.fill(u0, lane, ring, ring_seed);
                     rc_head = 0;
-                    const float4* src = q.rays + 2 * (size_t)rc_base;
-                    if (lane < 2u * rc_n) ring[lane] = src[lane];
-                    if (lane + 64u < 2u * rc_n) ring[lane + 64u] = src[lane + 64u];
-                    if (lane < rc_n) ring_seed[lane] = q.seeds ? q.seeds[(size_t)rc_base + lane] : q.seedBase + (rc_base + lane);
                 }
                 const uint32_t rank = lane_rank(im);
                 const uint32_t take = min((uint32_t)__popcll(im), rc_n);
                 if (idle && rank < take) {
                     const float4 e0 = ring[2u * (rc_head + rank)], e1 = ring[2u * (rc_head + rank) + 1u];
                     seed = ring_seed[rc_head + rank];
-                    pos = rc_base + rc_head + rank;
+                    e.take(rc_head + rank, e0);
                     if (bounces == 0u) {
-                        // Render's loop does not run: radiance 0 (either encoding), no first hit
-                        q.out[pos] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+                        e.unwalked();
                     } else {
-                        // InitRay (kernel_bvh.cl:42-55) on the caller's direction; isect.t starts at tmax
+                        // InitRay (kernel_bvh.cl:42-55) on the record's direction; isect.t starts at tmax
                         ray = init_ray<M>(F3{e0.x, e0.y, e0.z}, F3{e1.x, e1.y, e1.z});
-                        tmin = e0.w;
+                        tmin = e.tmin(e0);
                         h = Traversal{e1.w, -1, 0.0f, 0.0f};
                         radiance = f3s(0.0f);
                         beta = f3s(1.0f);
                         bounce = 0u;
-                        prim0 = -1;
                         cur = 0u;
                         if (kStats) ++st.rays;
                     }
@@ -129,18 +163,18 @@ __device__ __forceinline__ void trace_body(const KernelArgs& a, const TraceArgs&
             n_leaf = popc_ballot((int32_t)cur >= (int32_t)kLeafMin);
             n_ready = popc_ballot(cur == a.nNodes);
         }
-        if (n_ready >= q.shadeMin || (n_ready != 0u && n_trav + n_leaf == 0u)) {
+        if (n_ready >= shadeMin || (n_ready != 0u && n_trav + n_leaf == 0u)) {
             // ---- shading round (kernel_bvh.cl:358-380 per lane) ---------------------------------
             if (cur == a.nNodes) {
                 // the hit's barycentrics re-evaluated from the accepted triangle (the values the
                 // acceptance computed, as with_uv)
                 Traversal hu = h;
                 if (h.prim >= 0) {
-                    const TriEval e = tri_eval<M>(sc.tris + 3 * (size_t)h.prim, ray);
-                    hu.u = e.u;
-                    hu.v = e.v;
+                    const TriEval ev = tri_eval<M>(sc.tris + 3 * (size_t)h.prim, ray);
+                    hu.u = ev.u;
+                    hu.v = ev.v;
                 }
-                if (bounce == 0u) prim0 = h.prim;
+                if (bounce == 0u) e.first_hit(h.prim);
                 const bool go = shade_bounce<M, kStats>(hu, ray, radiance, beta, seed, sc, a, st);
                 ++bounce;
                 if (go && bounce < bounces) {
@@ -150,9 +184,7 @@ __device__ __forceinline__ void trace_body(const KernelArgs& a, const TraceArgs&
                     cur = 0u;
                     if (kStats) ++st.rays;
                 } else {
-                    F3 r{M::max(radiance.x, 0.0f), M::max(radiance.y, 0.0f), M::max(radiance.z, 0.0f)};
-                    if (q.encoding != 0) r = gamma_out<M>(0u, f3s(0.0f), r);
-                    q.out[pos] = make_float4(r.x, r.y, r.z, __int_as_float(prim0));
+                    e.template finish<M>(F3{M::max(radiance.x, 0.0f), M::max(radiance.y, 0.0f), M::max(radiance.z, 0.0f)});
                     cur = kNotWalking;
                 }
             }
@@ -188,6 +220,12 @@ __device__ __forceinline__ void trace_body(const KernelArgs& a, const TraceArgs&
         }
     }
     if (kStats) flush_stats(a, st, (int)lane);
+}
+
+template <class M, bool kStats, bool kBofs, bool kGlobalOct>
+__device__ __forceinline__ void trace_body(const KernelArgs& a, const TraceArgs& q) {
+    TraceEnds e{q};
+    trace_loop<M, kStats, kBofs, kGlobalOct>(a, e, q.refillMin, q.shadeMin);
 }
 
 // camera_rays_body's record for work-item gid, and the RNG state CreateRay leaves behind: gid +
