@@ -205,6 +205,35 @@ int launch_on_queue(rt_context ctx, rt_kernel k, rt_mem written, Launch&& launch
     return pending_error(ctx, RT_SUCCESS);
 }
 
+// the cameras of the two reprojection calls
+rtp::TemporalView view_of(const rt_view& v) {
+    rtp::TemporalView o;
+    for (int c = 0; c < 3; ++c) o.pos[c] = v.pos[c], o.front[c] = v.front[c], o.up[c] = v.up[c];
+    return o;
+}
+
+// The frame of the two a-trous denoise calls once their plan `p` stands: the scratch, before anything is
+// enqueued (growing it waits for nothing: rt_internal.hpp), then one launch per iteration, in order on the
+// context's stream after the pending accumulations and gathers, until one fails.  `step(i, t, src, dst, st)`
+// launches iteration i from and into the buffers its DenoiseStep `t` names (`image` is the first one's
+// source slot).
+template <class Plan, class Step>
+int enqueue_atrous(rt_context ctx, rt_kernel k, const Plan& p, float4* image, rt_mem out, Step&& step) {
+    if (p.scratch_pixels) {
+        const hipError_t me = k->denoise.reserve((size_t)p.scratch_pixels);
+        if (me != hipSuccess) return map_hip(me);
+    }
+    float4* const bufs[3] = {image, static_cast<float4*>(out->dptr), k->denoise.image()};
+    return launch_on_queue(ctx, k, out, [&](hipStream_t st) {
+        hipError_t e = hipSuccess;
+        for (unsigned i = 0; i < p.iterations && e == hipSuccess; ++i) {
+            const rtp::DenoiseStep& t = p.it[i];
+            e = step(i, t, bufs[t.src], bufs[t.dst], st);
+        }
+        return e;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1023,30 +1052,19 @@ int rtEnqueueDenoise(rt_context ctx, rt_kernel k, rt_mem image, rt_mem features,
     rtp::DenoisePlan p;
     rc = rtp::denoise_plan(in, &p);
     if (rc) return pending_error(ctx, rc);
-    // 2. the scratch, before anything is enqueued (growing it waits for nothing: rt_internal.hpp)
-    if (p.scratch_pixels) {
-        const hipError_t me = k->denoise.reserve((size_t)p.scratch_pixels);
-        if (me != hipSuccess) return map_hip(me);
-    }
-    // 3. one launch per iteration, in order on the context's stream after the pending accumulations
-    // and gathers
-    float4* const bufs[3] = {static_cast<float4*>(image->dptr), static_cast<float4*>(out->dptr), k->denoise.image()};
+    // 2. the scratch and one launch per iteration
     rtd::DenoiseArgs a{};
     a.features = static_cast<const float4*>(features->dptr);
     a.width = p.width, a.height = p.height;
     a.terms = p.terms;
     a.invN = p.inv_n, a.invZ = p.inv_z, a.invA = p.inv_a;
-    return launch_on_queue(ctx, k, out, [&](hipStream_t st) {
-        hipError_t e = hipSuccess;
-        for (unsigned i = 0; i < p.iterations && e == hipSuccess; ++i) {
-            const rtp::DenoiseStep& t = p.it[i];
-            a.src = bufs[t.src], a.dst = bufs[t.dst];
-            a.tilesX = t.tiles_x, a.tilesPerClass = t.tiles_per_class;
-            a.invC = t.inv_c;
-            e = rtd::launch_denoise(a, t, st);
-        }
-        return e;
-    });
+    return enqueue_atrous(ctx, k, p, static_cast<float4*>(image->dptr), out,
+                          [&](unsigned, const rtp::DenoiseStep& t, const float4* src, float4* dst, hipStream_t st) {
+                              a.src = src, a.dst = dst;
+                              a.tilesX = t.tiles_x, a.tilesPerClass = t.tiles_per_class;
+                              a.invC = t.inv_c;
+                              return rtd::launch_denoise(a, t, st);
+                          });
 }
 
 // ---- variance-guided a-trous denoise over the sample statistics (rt_denoise_samples.hip; the plan:
@@ -1079,15 +1097,8 @@ int rtEnqueueDenoiseSamples(rt_context ctx, rt_kernel k, rt_mem stats, rt_mem fe
     rtp::DenoiseSamplesPlan p;
     rc = rtp::denoise_samples_plan(in, &p);
     if (rc) return pending_error(ctx, rc);
-    // 2. the scratch rtEnqueueDenoise uses, before anything is enqueued (growing it waits for nothing:
-    // rt_internal.hpp)
-    if (p.scratch_pixels) {
-        const hipError_t me = k->denoise.reserve((size_t)p.scratch_pixels);
-        if (me != hipSuccess) return map_hip(me);
-    }
-    // 3. one launch per iteration, in order on the context's stream after the pending accumulations
-    // and gathers (the first iteration stages from the statistics: its src slot is not read)
-    float4* const bufs[3] = {nullptr, static_cast<float4*>(out->dptr), k->denoise.image()};
+    // 2. the scratch rtEnqueueDenoise uses and one launch per iteration (the first stages from the
+    // statistics: its src slot is not read)
     rtd::DenoiseSamplesArgs a{};
     a.stats = static_cast<const float4*>(stats->dptr);
     a.features = static_cast<const float4*>(features->dptr);
@@ -1096,18 +1107,16 @@ int rtEnqueueDenoiseSamples(rt_context ctx, rt_kernel k, rt_mem stats, rt_mem fe
     a.terms = p.terms, a.encoding = p.encoding;
     a.sigmaL = p.sigma_luminance, a.epsilon = p.epsilon;
     a.invN = p.inv_n, a.invZ = p.inv_z, a.invA = p.inv_a;
-    return launch_on_queue(ctx, k, out, [&](hipStream_t st) {
-        hipError_t e = hipSuccess;
-        for (unsigned i = 0; i < p.iterations && e == hipSuccess; ++i) {
-            const rtp::DenoiseStep& t = p.it[i];
-            a.src = bufs[t.src], a.dst = bufs[t.dst];
-            a.tilesX = t.tiles_x, a.tilesPerClass = t.tiles_per_class;
-            a.last = p.last[i] ? 1u : 0u;
-            e = rtd::launch_denoise_samples(a, t, p.first[i], st);
-        }
-        if (e == hipSuccess && p.write_variance) mark_device_write(variance, true);
-        return e;
-    });
+    return enqueue_atrous(ctx, k, p, nullptr, out,
+                          [&](unsigned i, const rtp::DenoiseStep& t, const float4* src, float4* dst, hipStream_t st) {
+                              a.src = src, a.dst = dst;
+                              a.tilesX = t.tiles_x, a.tilesPerClass = t.tiles_per_class;
+                              a.last = p.last[i] ? 1u : 0u;
+                              const hipError_t e = rtd::launch_denoise_samples(a, t, p.first[i], st);
+                              // (the last iteration is launched only after every other one was)
+                              if (e == hipSuccess && p.last[i] && p.write_variance) mark_device_write(variance, true);
+                              return e;
+                          });
 }
 
 // ---- temporal reprojection (rt_temporal.hip; the plan: rt_temporal_plan.cpp) -----------------------
@@ -1121,11 +1130,7 @@ int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem 
     rtp::TemporalIn in{};
     in.params_ok = params != nullptr;
     if (params) {
-        for (int c = 0; c < 3; ++c) {
-            in.cur.pos[c] = params->cur.pos[c], in.cur.front[c] = params->cur.front[c], in.cur.up[c] = params->cur.up[c];
-            in.prev.pos[c] = params->prev.pos[c], in.prev.front[c] = params->prev.front[c];
-            in.prev.up[c] = params->prev.up[c];
-        }
+        in.cur = view_of(params->cur), in.prev = view_of(params->prev);
         in.cur_frames = params->cur_frames, in.history_frames = params->history_frames;
         in.max_history = params->max_history;
         in.depth_tolerance = params->depth_tolerance, in.normal_threshold = params->normal_threshold;
@@ -1170,11 +1175,7 @@ int rtEnqueueReprojectSamples(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt
     rtp::ReprojectIn in{};
     in.params_ok = params != nullptr;
     if (params) {
-        for (int c = 0; c < 3; ++c) {
-            in.cur.pos[c] = params->cur.pos[c], in.cur.front[c] = params->cur.front[c], in.cur.up[c] = params->cur.up[c];
-            in.prev.pos[c] = params->prev.pos[c], in.prev.front[c] = params->prev.front[c];
-            in.prev.up[c] = params->prev.up[c];
-        }
+        in.cur = view_of(params->cur), in.prev = view_of(params->prev);
         in.max_history = params->max_history;
         in.depth_tolerance = params->depth_tolerance, in.normal_threshold = params->normal_threshold;
     }

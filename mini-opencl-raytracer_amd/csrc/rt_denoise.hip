@@ -5,21 +5,16 @@
 // IEEE division -- which is why this is a translation unit of its own, built with the standard flags
 // and not with the shipped kernels' relaxed division).
 //
-// A workgroup filters one tile of rtp::denoise_plan: 64 contiguous columns of kRows rows of one
-// residue class y mod kStep.  It stages the tile plus a halo of 2 taps -- (64 + 4 kStep) columns of
-// kRows + 4 class rows -- in LDS as three float4 planes (colour; albedo, depth; normal, coverage)
-// with 16-B loads whose lanes run along x, then every lane runs the 25 taps of its pixels out of
-// LDS: a tap is kStep cells along a staged row, or one staged row up or down.  Cells outside the
-// image are staged as zeros with coverage 0, so the rule that skips an uncovered tap skips them, and
-// global indices are only ever formed from coordinates tested to lie inside the image.  Pixel values
-// never reach an address.
+// A workgroup filters one tile of rtp::denoise_plan, every lane the 25 taps of its pixels, out of a block
+// staged in LDS: the tile, its staging and its safety rules are rt_atrous_tile.hpp, which
+// rt_denoise_samples.hip shares.
 #include "rt_denoise.hpp"
+
+#include "rt_atrous_tile.hpp"
 
 namespace rtd {
 
 namespace {
-
-constexpr int kTileW = (int)rtp::kDenoiseTileW, kThreads = (int)rtp::kDenoiseThreads;
 
 __device__ __forceinline__ float dot3(float x, float y, float z) { return (x * x + y * y) + z * z; }
 __device__ __forceinline__ float edge(float x) {
@@ -30,53 +25,30 @@ __device__ __forceinline__ float edge(float x) {
 // kAll: all four edge-stopping terms are on (a.terms is not looked at)
 template <int kStep, bool kAll>
 __global__ __launch_bounds__(kThreads) void denoise_atrous(DenoiseArgs a) {
-    constexpr int kRows = (int)rtp::denoise_rows(kStep);
-    constexpr int SW = kTileW + 4 * kStep, SH = kRows + 4, kCells = SW * SH;
-    // the {normal, coverage} plane starts 4 cells on, so that a staging store's lane pairs (the two
-    // halves of one feature record) fall into different banks
-    constexpr int kPlaneB = kCells + (int)rtp::kDenoisePadBytes / 16;
-    static_assert((size_t)kCells * rtp::kDenoiseCellBytes + rtp::kDenoisePadBytes <= rtp::kDenoiseLdsBudget,
-                  "staged block over the LDS budget");
-    __shared__ float4 sCol[kCells];
-    __shared__ float4 sFeat[kPlaneB + kCells];
-
-    const uint32_t tid = threadIdx.x;
-    const uint32_t tx = blockIdx.x % a.tilesX, rest = blockIdx.x / a.tilesX;
-    const uint32_t ty = rest % a.tilesPerClass, cls = rest / a.tilesPerClass;
-    const int64_t W = a.width, H = a.height;
-    const int64_t x0 = (int64_t)tx * kTileW;
-    const int64_t j0 = (int64_t)ty * kRows;             // the tile's first row, counted within its class
-    if ((int64_t)cls + j0 * kStep >= H) return;         // a shorter class's last tile (the whole workgroup)
-
-    // ---- stage: lanes run along x, one 16-B load each ----
-    for (int c = (int)tid; c < kCells; c += kThreads) {
-        const int cy = c / SW, cx = c - cy * SW;
-        const int64_t x = x0 - 2 * kStep + cx, y = (int64_t)cls + (j0 - 2 + cy) * kStep;
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (x >= 0 && x < W && y >= 0 && y < H) v = a.src[(size_t)(y * W + x)];
-        sCol[c] = v;
-    }
-    for (int f = (int)tid; f < 2 * kCells; f += kThreads) {
-        const int c = f >> 1, half = f & 1;
-        const int cy = c / SW, cx = c - cy * SW;
-        const int64_t x = x0 - 2 * kStep + cx, y = (int64_t)cls + (j0 - 2 + cy) * kStep;
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // outside the image: coverage 0
-        if (x >= 0 && x < W && y >= 0 && y < H) v = a.features[(size_t)(y * W + x) * 2 + half];
-        sFeat[half * kPlaneB + c] = v;
-    }
+    using Tile = AtrousTile<kStep>;
+    constexpr int kPlaneB = Tile::kPlaneB;
+    __shared__ float4 sCol[Tile::kCells];
+    __shared__ float4 sFeat[kPlaneB + Tile::kCells];
+    const Tile tile{a.tilesX, a.tilesPerClass, a.width, a.height};
+    const typename Tile::Origin org = tile.origin();
+    if (tile.empty()) return;
+    tile.stage_colours(sCol, [&](size_t p) { return a.src[p]; });
+    tile.stage_features(sFeat, a.features);
     __syncthreads();
 
     // ---- filter: lane = column, one wave per tile row and pass ----
-    constexpr float kH[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    const uint32_t tid = threadIdx.x;
     const int lx = (int)(tid & 63u);
-    const int64_t x = x0 + lx;
-    if (x >= W) return;
+    const int64_t x = org.x0 + lx;
+    if (x >= org.W) return;
+    constexpr float kH[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     const bool onC = kAll || (a.terms & rtp::kDenoiseColor), onN = kAll || (a.terms & rtp::kDenoiseNormal);
     const bool onZ = kAll || (a.terms & rtp::kDenoiseDepth), onA = kAll || (a.terms & rtp::kDenoiseAlbedo);
-    for (int j = (int)(tid >> 6); j < kRows; j += kThreads / kTileW) {
-        const int64_t y = (int64_t)cls + (j0 + j) * kStep;
-        if (y >= H) break;
-        const int cc = (j + 2) * SW + 2 * kStep + lx;
+    for (int j = (int)(tid >> 6); j < Tile::kRows; j += kThreads / kTileW) {
+        const int64_t y = (int64_t)org.cls + (org.j0 + j) * kStep;
+        if (y >= org.H) break;
+        const int cc = Tile::centre(j, lx);
+        const size_t p = (size_t)(y * org.W + x);
         const float4 cp = sCol[cc];
         const float4 ap = sFeat[cc], np = sFeat[kPlaneB + cc];  // {albedo, depth}, {normal, coverage}
         float4 o = cp;  // an uncovered centre is copied
@@ -87,7 +59,7 @@ __global__ __launch_bounds__(kThreads) void denoise_atrous(DenoiseArgs a) {
             for (int dy = -2; dy <= 2; ++dy) {
 #pragma unroll
                 for (int dx = -2; dx <= 2; ++dx) {
-                    const int q = cc + dy * SW + dx * kStep;
+                    const int q = Tile::tap(cc, dx, dy);
                     const float4 cq = sCol[q];
                     const float4 aq = sFeat[q];
                     const float4 nq = sFeat[kPlaneB + q];
@@ -112,34 +84,23 @@ __global__ __launch_bounds__(kThreads) void denoise_atrous(DenoiseArgs a) {
             }
             o = make_float4(sr / sw, sg / sw, sb / sw, cp.w);
         }
-        a.dst[(size_t)(y * W + x)] = o;
+        a.dst[p] = o;
     }
-}
-
-template <int kStep>
-hipError_t launch_step(const DenoiseArgs& a, const rtp::DenoiseStep& t, hipStream_t st) {
-    if (t.rows != rtp::denoise_rows(kStep) || t.stage_w != rtp::kDenoiseTileW + 4u * kStep || t.stage_h != t.rows + 4u)
-        return hipErrorInvalidValue;
-    const uint32_t all = rtp::kDenoiseColor | rtp::kDenoiseNormal | rtp::kDenoiseDepth | rtp::kDenoiseAlbedo;
-    if (a.terms == all)
-        hipLaunchKernelGGL((denoise_atrous<kStep, true>), dim3(t.grid), dim3(kThreads), 0, st, a);
-    else
-        hipLaunchKernelGGL((denoise_atrous<kStep, false>), dim3(t.grid), dim3(kThreads), 0, st, a);
-    return hipGetLastError();
 }
 
 }  // namespace
 
 hipError_t launch_denoise(const DenoiseArgs& a, const rtp::DenoiseStep& t, hipStream_t st) {
     if (t.grid == 0 || a.tilesX != t.tiles_x || a.tilesPerClass != t.tiles_per_class) return hipErrorInvalidValue;
-    switch (t.step) {
-        case 1: return launch_step<1>(a, t, st);
-        case 2: return launch_step<2>(a, t, st);
-        case 4: return launch_step<4>(a, t, st);
-        case 8: return launch_step<8>(a, t, st);
-        case 16: return launch_step<16>(a, t, st);
-        default: return hipErrorInvalidValue;
-    }
+    return for_step(t, [&](auto step) {
+        constexpr int kStep = decltype(step)::value;
+        const uint32_t all = rtp::kDenoiseColor | rtp::kDenoiseNormal | rtp::kDenoiseDepth | rtp::kDenoiseAlbedo;
+        if (a.terms == all)
+            hipLaunchKernelGGL((denoise_atrous<kStep, true>), dim3(t.grid), dim3(kThreads), 0, st, a);
+        else
+            hipLaunchKernelGGL((denoise_atrous<kStep, false>), dim3(t.grid), dim3(kThreads), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace rtd

@@ -6,18 +6,17 @@
 // order written there (no contraction, denormals kept, IEEE division and square root -- the standard
 // flags, never the shipped kernels' relaxed ones).
 //
-// The shape is rt_denoise.hip's: a workgroup filters one tile of rtp::denoise_samples_plan, 64 contiguous
-// columns of kRows rows of one residue class y mod kStep, out of a block staged in LDS with a halo of 2
-// taps as three float4 planes.  The colour plane's w slot carries the variance of the pixel's mean
-// luminance, so a cell stays 48 B.  The first iteration stages straight from the 32-B statistics records
-// (two 16-B loads per cell, lanes along x) and computes {colour, variance} on the way into LDS: there is
-// no resolve pass.  A centre's luminance tolerance comes from the inner 3 x 3 of its own taps, which lie
-// in the staged block at every step.  Cells outside the image are staged as zeros with coverage 0, so the
-// rule that drops a tap that does not count drops them, and global indices are only ever formed from
-// coordinates tested to lie inside the image.  No value of `stats` or `features` reaches an address.
+// The shape is rt_denoise.hip's: a workgroup filters one tile of rtp::denoise_samples_plan out of a block
+// staged in LDS; the tile, its staging and its safety rules are rt_atrous_tile.hpp.  The colour plane's w
+// slot carries the variance of the pixel's mean luminance, so a cell stays 48 B.  The first iteration
+// stages straight from the 32-B statistics records (two 16-B loads per cell, lanes along x) and computes
+// {colour, variance} on the way into LDS: there is no resolve pass.  A centre's luminance tolerance comes
+// from the inner 3 x 3 of its own taps, which lie in the staged block at every step.  No value of `stats`
+// or `features` reaches an address.
 #include "rt_denoise_samples.hpp"
 
 #include "../../include/rt_pinned_math.h"
+#include "rt_atrous_tile.hpp"
 #include "rt_denoise_samples_math.hpp"
 
 #pragma clang fp contract(off)
@@ -25,8 +24,6 @@
 namespace rtd {
 
 namespace {
-
-constexpr int kTileW = (int)rtp::kDenoiseTileW, kThreads = (int)rtp::kDenoiseThreads;
 
 __device__ __forceinline__ rtds::Cell cell_of(float4 c) { return rtds::Cell{c.x, c.y, c.z, c.w}; }
 __device__ __forceinline__ rtds::Guide guide_of(float4 a, float4 n) {
@@ -37,64 +34,37 @@ __device__ __forceinline__ rtds::Guide guide_of(float4 a, float4 n) {
 // are on (a.terms is not looked at)
 template <int kStep, bool kFirst, bool kAll>
 __global__ __launch_bounds__(kThreads) void denoise_samples_atrous(DenoiseSamplesArgs a) {
-    constexpr int kRows = (int)rtp::denoise_rows(kStep);
-    constexpr int SW = kTileW + 4 * kStep, SH = kRows + 4, kCells = SW * SH;
-    // the {normal, coverage} plane starts 4 cells on, so that a staging store's lane pairs (the two
-    // halves of one feature record) fall into different banks
-    constexpr int kPlaneB = kCells + (int)rtp::kDenoisePadBytes / 16;
-    static_assert((size_t)kCells * rtp::kDenoiseCellBytes + rtp::kDenoisePadBytes <= rtp::kDenoiseLdsBudget,
-                  "staged block over the LDS budget");
     static_assert(!kFirst || kStep == 1, "the first iteration has step 1");
-    __shared__ float4 sCol[kCells];
-    __shared__ float4 sFeat[kPlaneB + kCells];
-
-    const uint32_t tid = threadIdx.x;
-    const uint32_t tx = blockIdx.x % a.tilesX, rest = blockIdx.x / a.tilesX;
-    const uint32_t ty = rest % a.tilesPerClass, cls = rest / a.tilesPerClass;
-    const int64_t W = a.width, H = a.height;
-    const int64_t x0 = (int64_t)tx * kTileW;
-    const int64_t j0 = (int64_t)ty * kRows;             // the tile's first row, counted within its class
-    if ((int64_t)cls + j0 * kStep >= H) return;         // a shorter class's last tile (the whole workgroup)
-
-    // ---- stage: lanes run along x, 16-B loads ----
-    for (int c = (int)tid; c < kCells; c += kThreads) {
-        const int cy = c / SW, cx = c - cy * SW;
-        const int64_t x = x0 - 2 * kStep + cx, y = (int64_t)cls + (j0 - 2 + cy) * kStep;
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // outside the image: coverage 0 drops it
-        if (x >= 0 && x < W && y >= 0 && y < H) {
-            const size_t p = (size_t)(y * W + x);
-            if (kFirst) {
-                const float4 lo = a.stats[2 * p], hi = a.stats[2 * p + 1];
-                const rtds::Cell s = rtds::stats_cell(lo.x, lo.y, lo.z, lo.w, hi.x, hi.y);
-                v = make_float4(s.r, s.g, s.b, s.v);
-            } else {
-                v = a.src[p];
-            }
-        }
-        sCol[c] = v;
-    }
-    for (int f = (int)tid; f < 2 * kCells; f += kThreads) {
-        const int c = f >> 1, half = f & 1;
-        const int cy = c / SW, cx = c - cy * SW;
-        const int64_t x = x0 - 2 * kStep + cx, y = (int64_t)cls + (j0 - 2 + cy) * kStep;
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // outside the image: coverage 0
-        if (x >= 0 && x < W && y >= 0 && y < H) v = a.features[(size_t)(y * W + x) * 2 + half];
-        sFeat[half * kPlaneB + c] = v;
-    }
+    using Tile = AtrousTile<kStep>;
+    constexpr int kPlaneB = Tile::kPlaneB;
+    __shared__ float4 sCol[Tile::kCells];
+    __shared__ float4 sFeat[kPlaneB + Tile::kCells];
+    const Tile tile{a.tilesX, a.tilesPerClass, a.width, a.height};
+    const typename Tile::Origin org = tile.origin();
+    if (tile.empty()) return;
+    tile.stage_colours(sCol, [&](size_t p) {
+        if (!kFirst) return a.src[p];
+        const float4 lo = a.stats[2 * p], hi = a.stats[2 * p + 1];
+        const rtds::Cell s = rtds::stats_cell(lo.x, lo.y, lo.z, lo.w, hi.x, hi.y);
+        return make_float4(s.r, s.g, s.b, s.v);
+    });
+    tile.stage_features(sFeat, a.features);
     __syncthreads();
 
     // ---- filter: lane = column, one wave per tile row and pass ----
+    const uint32_t tid = threadIdx.x;
     const int lx = (int)(tid & 63u);
-    const int64_t x = x0 + lx;
-    if (x >= W) return;
+    const int64_t x = org.x0 + lx;
+    if (x >= org.W) return;
     rtds::Terms terms;
     terms.luminance = kAll || (a.terms & rtp::kDenoiseLuminance), terms.normal = kAll || (a.terms & rtp::kDenoiseNormal);
     terms.depth = kAll || (a.terms & rtp::kDenoiseDepth), terms.albedo = kAll || (a.terms & rtp::kDenoiseAlbedo);
     terms.inv_n = a.invN, terms.inv_z = a.invZ, terms.inv_a = a.invA;
-    for (int j = (int)(tid >> 6); j < kRows; j += kThreads / kTileW) {
-        const int64_t y = (int64_t)cls + (j0 + j) * kStep;
-        if (y >= H) break;
-        const int cc = (j + 2) * SW + 2 * kStep + lx;
+    for (int j = (int)(tid >> 6); j < Tile::kRows; j += kThreads / kTileW) {
+        const int64_t y = (int64_t)org.cls + (org.j0 + j) * kStep;
+        if (y >= org.H) break;
+        const int cc = Tile::centre(j, lx);
+        const size_t p = (size_t)(y * org.W + x);
         const float4 cp = sCol[cc];
         const float4 ap = sFeat[cc], np = sFeat[kPlaneB + cc];  // {albedo, depth}, {normal, coverage}
         rtds::Cell o = cell_of(cp);  // a centre that does not count is carried
@@ -105,7 +75,7 @@ __global__ __launch_bounds__(kThreads) void denoise_samples_atrous(DenoiseSample
             for (int dy = -1; dy <= 1; ++dy) {
 #pragma unroll
                 for (int dx = -1; dx <= 1; ++dx) {
-                    const int q = cc + dy * SW + dx * kStep;
+                    const int q = Tile::tap(cc, dx, dy);
                     const float vq = sCol[q].w;
                     ts = rtds::tol_tap(ts, rtds::tol_weight(dy) * rtds::tol_weight(dx), vq,
                                        rtds::counts(sFeat[kPlaneB + q].w, vq));
@@ -117,7 +87,7 @@ __global__ __launch_bounds__(kThreads) void denoise_samples_atrous(DenoiseSample
             for (int dy = -2; dy <= 2; ++dy) {
 #pragma unroll
                 for (int dx = -2; dx <= 2; ++dx) {
-                    const int q = cc + dy * SW + dx * kStep;
+                    const int q = Tile::tap(cc, dx, dy);
                     const float4 cq = sCol[q];
                     const float4 aq = sFeat[q];
                     const float4 nq = sFeat[kPlaneB + q];
@@ -127,7 +97,6 @@ __global__ __launch_bounds__(kThreads) void denoise_samples_atrous(DenoiseSample
             }
             o = rtds::iteration_result(s);
         }
-        const size_t p = (size_t)(y * W + x);
         if (!a.last) {
             a.dst[p] = make_float4(o.r, o.g, o.b, o.v);
         } else {
@@ -146,32 +115,23 @@ __global__ __launch_bounds__(kThreads) void denoise_samples_atrous(DenoiseSample
     }
 }
 
-template <int kStep, bool kFirst>
-hipError_t launch_step(const DenoiseSamplesArgs& a, const rtp::DenoiseStep& t, hipStream_t st) {
-    if (t.rows != rtp::denoise_rows(kStep) || t.stage_w != rtp::kDenoiseTileW + 4u * kStep || t.stage_h != t.rows + 4u)
-        return hipErrorInvalidValue;
-    const uint32_t all = rtp::kDenoiseLuminance | rtp::kDenoiseNormal | rtp::kDenoiseDepth | rtp::kDenoiseAlbedo;
-    if (a.terms == all)
-        hipLaunchKernelGGL((denoise_samples_atrous<kStep, kFirst, true>), dim3(t.grid), dim3(kThreads), 0, st, a);
-    else
-        hipLaunchKernelGGL((denoise_samples_atrous<kStep, kFirst, false>), dim3(t.grid), dim3(kThreads), 0, st, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_denoise_samples(const DenoiseSamplesArgs& a, const rtp::DenoiseStep& t, bool first, hipStream_t st) {
+    // (the kernel of step 1 is the first iteration's, and only that one's)
     if (t.grid == 0 || a.tilesX != t.tiles_x || a.tilesPerClass != t.tiles_per_class || !a.stats || !a.features || !a.dst ||
-        (!first && !a.src) || (first && t.step != 1))
+        (!first && !a.src) || first != (t.step == 1))
         return hipErrorInvalidValue;
-    switch (t.step) {
-        case 1: return first ? launch_step<1, true>(a, t, st) : hipErrorInvalidValue;
-        case 2: return launch_step<2, false>(a, t, st);
-        case 4: return launch_step<4, false>(a, t, st);
-        case 8: return launch_step<8, false>(a, t, st);
-        case 16: return launch_step<16, false>(a, t, st);
-        default: return hipErrorInvalidValue;
-    }
+    return for_step(t, [&](auto step) {
+        constexpr int kStep = decltype(step)::value;
+        constexpr bool kFirst = kStep == 1;
+        const uint32_t all = rtp::kDenoiseLuminance | rtp::kDenoiseNormal | rtp::kDenoiseDepth | rtp::kDenoiseAlbedo;
+        if (a.terms == all)
+            hipLaunchKernelGGL((denoise_samples_atrous<kStep, kFirst, true>), dim3(t.grid), dim3(kThreads), 0, st, a);
+        else
+            hipLaunchKernelGGL((denoise_samples_atrous<kStep, kFirst, false>), dim3(t.grid), dim3(kThreads), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace rtd

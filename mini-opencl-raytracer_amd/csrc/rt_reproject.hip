@@ -20,24 +20,20 @@
 // part in an address; taps that do not count are dropped by select.
 #include "rt_reproject.hpp"
 
+#include "rt_temporal.hpp"
+
 namespace rtrs {
 
 namespace {
 
-constexpr int kTileW = (int)rtp::kTemporalTileW, kTileH = (int)rtp::kTemporalTileH;
-constexpr int kThreads = (int)rtp::kTemporalThreads;
-
-__global__ __launch_bounds__(kThreads) void reproject_samples(ReprojectArgs a) {
-    const uint32_t tx = blockIdx.x % a.tilesX, ty = blockIdx.x / a.tilesX;
-    const uint64_t x = (uint64_t)tx * kTileW + (threadIdx.x & (kTileW - 1));
-    const uint64_t y = (uint64_t)ty * kTileH + (threadIdx.x / kTileW);
+__global__ __launch_bounds__(rtt::kThreads) void reproject_samples(ReprojectArgs a) {
+    const rtt::Pixel px = rtt::tile_pixel(a.tilesX);
+    const uint64_t x = px.x, y = px.y;
     if (x >= a.width || y >= a.height) return;
     const uint64_t p = y * a.width + x;
     const float4 fa = a.cur_features[2 * p], fn = a.cur_features[2 * p + 1];  // {albedo, depth}, {normal, coverage}
-    rtt::Reprojection r = rtt::reproject(a.k, (uint32_t)x, (uint32_t)y, fa.w);
-    r.ok = r.ok && fn.w > 0.0f;
-    const float nrm[3] = {fn.x, fn.y, fn.z};
-    const float tol = a.depth_tolerance * r.de;
+    const rtt::Centre ce = rtt::centre_of(rtt::reproject(a.k, (uint32_t)x, (uint32_t)y, fa.w), fn, a.depth_tolerance);
+    const rtt::Reprojection& r = ce.r;
     // the features of the taps inside the image, then the statistics of those on the centre's surface
     uint64_t q[4];
     bool on[4];
@@ -48,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void reproject_samples(ReprojectArgs a) {
         float4 hz = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hn = hz;  // coverage 0: does not count
         if (inside) hz = a.hist_features[2 * q[t]], hn = a.hist_features[2 * q[t] + 1];
         const float hnrm[3] = {hn.x, hn.y, hn.z};
-        on[t] = tap_on_surface(inside, hn.w, hz.w, hnrm, nrm, r.de, tol, a.normal_threshold);
+        on[t] = tap_on_surface(inside, hn.w, hz.w, hnrm, ce.nrm, r.de, ce.tol, a.normal_threshold);
     }
     float4 s0[4], s1[4];
 #pragma unroll
@@ -78,7 +74,7 @@ hipError_t launch_reproject(const ReprojectArgs& a, const rtp::ReprojectPlan& p,
     if (p.grid == 0 || a.width != p.width || a.height != p.height || a.tilesX != p.tiles_x ||
         (uint64_t)p.tiles_x * p.tiles_y != p.grid || !a.hist_stats || !a.hist_features || !a.cur_features || !a.out_stats)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(reproject_samples, dim3(p.grid), dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL(reproject_samples, dim3(p.grid), dim3(rtt::kThreads), 0, st, a);
     return hipGetLastError();
 }
 

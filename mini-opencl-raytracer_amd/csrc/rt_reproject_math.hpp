@@ -1,6 +1,6 @@
 // rt_reproject_math.hpp -- steps 5 and 6 of rtEnqueueReprojectSamples' definition (include/rt_hip.h):
 // the test of a history tap, its per-sample quantities, the bilinear sums and the recombined record.
-// Steps 2-4 of the projection are rt_temporal_math.hpp's, compiled as they are.  The kernel
+// Steps 2-4 of the projection and the surface test are rt_temporal_math.hpp's, compiled as they are.  The kernel
 // (rt_reproject.hip) and a CPU program (tests/native/reproject_samples_plan_main.cpp, built with
 // sanitizers) compile this same text on records that were already loaded: nothing here forms an address.
 //
@@ -34,13 +34,7 @@ struct TapSums {
 
 RT_RM_FN TapSums no_taps() { return TapSums{0.0f, {0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, 0.0f}; }
 
-// The part of a tap's test that needs its features only: q inside the image, covered, on the centre's
-// surface.  `tol` is depth_tolerance * de.  False for a NaN anywhere.  The statistics of a tap that
-// fails here need not be fetched.
-RT_RM_FN bool tap_on_surface(bool inside, float coverage, float depth, const float* normal, const float* centre_normal,
-                             float de, float tol, float normal_threshold) {
-    return inside && coverage > 0.0f && fabsf(depth - de) <= tol && rtt::dot3(centre_normal, normal) >= normal_threshold;
-}
+using rtt::tap_on_surface;  // the features' part of a tap's test is the temporal pass's
 
 // One tap with weight bw: counted when it is on the surface and holds at least one sample.
 RT_RM_FN void add_tap(TapSums& t, bool on_surface, float bw, const Stats& s) {

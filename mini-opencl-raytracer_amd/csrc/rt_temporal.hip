@@ -20,24 +20,18 @@ namespace rtt {
 
 namespace {
 
-constexpr int kTileW = (int)rtp::kTemporalTileW, kTileH = (int)rtp::kTemporalTileH;
-constexpr int kThreads = (int)rtp::kTemporalThreads;
-
 template <bool kHistory>
 __global__ __launch_bounds__(kThreads) void temporal_accumulate(TemporalArgs a) {
-    const uint32_t tx = blockIdx.x % a.tilesX, ty = blockIdx.x / a.tilesX;
-    const uint64_t x = (uint64_t)tx * kTileW + (threadIdx.x & (kTileW - 1));
-    const uint64_t y = (uint64_t)ty * kTileH + (threadIdx.x / kTileW);
+    const Pixel px = tile_pixel(a.tilesX);
+    const uint64_t x = px.x, y = px.y;
     if (x >= a.width || y >= a.height) return;
     const uint64_t p = y * a.width + x;
     const float4 c = a.cur[p];
     float4 o = make_float4(c.x, c.y, c.z, a.cur_frames);  // every "no history" row
     if (kHistory) {
         const float4 fa = a.cur_features[2 * p], fn = a.cur_features[2 * p + 1];  // {albedo, depth}, {normal, coverage}
-        Reprojection r = reproject(a.k, (uint32_t)x, (uint32_t)y, fa.w);
-        r.ok = r.ok && fn.w > 0.0f;
-        const float nrm[3] = {fn.x, fn.y, fn.z};
-        const float tol = a.depth_tolerance * r.de;
+        const Centre ce = centre_of(reproject(a.k, (uint32_t)x, (uint32_t)y, fa.w), fn, a.depth_tolerance);
+        const Reprojection& r = ce.r;
         float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sn = 0.0f;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -52,8 +46,7 @@ __global__ __launch_bounds__(kThreads) void temporal_accumulate(TemporalArgs a) 
                 }
                 const float nq = a.history_frames != 0.0f ? a.history_frames : hc.w;
                 const float hnrm[3] = {hn.x, hn.y, hn.z};
-                const bool counts = inside && hn.w > 0.0f && fabsf(hz.w - r.de) <= tol &&
-                                    dot3(nrm, hnrm) >= a.normal_threshold && nq >= 1.0f;
+                const bool counts = tap_on_surface(inside, hn.w, hz.w, hnrm, ce.nrm, r.de, ce.tol, a.normal_threshold) && nq >= 1.0f;
                 const float bw = tap_weight(r, i, j);
                 sw = counts ? sw + bw : sw;
                 sr = counts ? sr + bw * hc.x : sr;

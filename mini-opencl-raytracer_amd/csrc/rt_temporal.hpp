@@ -20,6 +20,31 @@ struct TemporalArgs {
     TemporalConsts k;
 };
 
+// ---- how the two reprojection kernels (rt_temporal.hip, rt_reproject.hip) open ----
+constexpr int kTileW = (int)rtp::kTemporalTileW, kTileH = (int)rtp::kTemporalTileH;
+constexpr int kThreads = (int)rtp::kTemporalThreads;
+
+// The thread's pixel in tile blockIdx.x of the plan: a wave per row, a lane per column.  It may lie
+// outside the image.
+struct Pixel {
+    uint64_t x, y;
+};
+__device__ __forceinline__ Pixel tile_pixel(uint32_t tilesX) {
+    const uint32_t tx = blockIdx.x % tilesX, ty = blockIdx.x / tilesX;
+    return Pixel{(uint64_t)tx * kTileW + (threadIdx.x & (kTileW - 1)), (uint64_t)ty * kTileH + (threadIdx.x / kTileW)};
+}
+
+// What a history tap is tested against: the pixel's reprojection `r`, which passes only for a covered
+// centre (fn is its {normal, coverage}), the centre's normal and the depth tolerance at its distance.
+struct Centre {
+    Reprojection r;
+    float nrm[3], tol;
+};
+__device__ __forceinline__ Centre centre_of(Reprojection r, float4 fn, float depth_tolerance) {
+    r.ok = r.ok && fn.w > 0.0f;
+    return Centre{r, {fn.x, fn.y, fn.z}, depth_tolerance * r.de};
+}
+
 // One launch over p.grid workgroups on `st`.  hipErrorInvalidValue for a plan that does not match
 // the arguments: nothing is launched.
 hipError_t launch_temporal(const TemporalArgs& a, const rtp::TemporalPlan& p, hipStream_t st);

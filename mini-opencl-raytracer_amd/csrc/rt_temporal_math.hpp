@@ -1,6 +1,6 @@
 // rt_temporal_math.hpp -- steps 2-4 of rtEnqueueTemporalAccumulate's definition (include/rt_hip.h):
 // the world point of a pixel, its projection into the previous view, the range test and the tap
-// indices.  This is where a value read from a buffer (a depth) ends up deciding an address, so the
+// indices; and step 5's surface test of a tap, which rtEnqueueReprojectSamples shares.  This is where a value read from a buffer (a depth) ends up deciding an address, so the
 // kernel (rt_temporal.hip) and a CPU program (tests/native/temporal_plan_main.cpp, built with
 // sanitizers) compile this same text: the address logic is swept on the CPU over every class of
 // bit pattern before a GPU runs it.
@@ -99,6 +99,14 @@ RT_TM_FN bool tap_index(const Reprojection& r, int i, int j, uint32_t W, uint32_
 
 RT_TM_FN float tap_weight(const Reprojection& r, int i, int j) {
     return (i ? r.tx : 1.0f - r.tx) * (j ? r.ty : 1.0f - r.ty);
+}
+
+// The part of a history tap's test that needs its features only: q inside the image, covered, on the
+// centre's surface.  `tol` is depth_tolerance * de.  False for a NaN anywhere.  (The sample reprojection
+// need not fetch the statistics of a tap that fails here.)
+RT_TM_FN bool tap_on_surface(bool inside, float coverage, float depth, const float* normal, const float* centre_normal,
+                             float de, float tol, float normal_threshold) {
+    return inside && coverage > 0.0f && fabsf(depth - de) <= tol && dot3(centre_normal, normal) >= normal_threshold;
 }
 
 }  // namespace rtt

@@ -46,6 +46,15 @@ struct TemporalPlan {
     uint32_t grid;                  // workgroups of kTemporalThreads
 };
 
+// The parts temporal_plan shares with the plan of the sample reprojection (rt_reproject_plan.hpp), which
+// runs on the same views and the same tiles: each a row of the checks below or a piece of the plan.
+bool finite_in(float v, float lo, float hi);             // finite and in [lo, hi]
+bool view_finite(const TemporalView& v);
+bool image_size_ok(uint64_t width, uint64_t height);     // neither zero, width * height <= 2^31
+// the fp32 host constants of the definition (include/rt_hip.h) for an image that passed image_size_ok
+rtt::TemporalConsts view_consts(uint64_t width, uint64_t height, const TemporalView& cur, const TemporalView& prev);
+void temporal_tiles(uint64_t width, uint64_t height, uint32_t* tiles_x, uint32_t* tiles_y, uint32_t* grid);
+
 // RT_SUCCESS, or, in this order: RT_INVALID_VALUE (no params; width or height zero; width * height >
 // 2^31; a camera component not finite; cur_frames not finite, < 1 or > 2^20; history_frames negative,
 // not finite, in (0, 1) or > 2^20; max_history not finite, < cur_frames or > 2^20; depth_tolerance not

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Compare the gfx950 ISA of every kernel (the render objects' and rt_comm.o's) between a saved snapshot
+# Compare the gfx950 ISA of every kernel (the render objects', rt_comm.o's and the four image passes':
+# rt_denoise.o, rt_denoise_samples.o, rt_temporal.o, rt_reproject.o) between a saved snapshot
 # and the current build (the instruction text per function: addresses, encodings and branch-target
 # labels stripped).  A code change meant to leave the kernels' instruction streams alone must print
 # "identical" for them.
@@ -12,9 +13,10 @@
 set -eu
 B=${ISA_BUILD:-mini-opencl-raytracer_amd/build}  # (ISA_BUILD: a variant's object directory)
 LLVM=/opt/rocm/lib/llvm/bin
+OBJS="rt_kernels_shipped rt_kernels rt_comm rt_denoise rt_denoise_samples rt_temporal rt_reproject"
 dump() {  # dump OUTDIR
   mkdir -p $1
-  for o in rt_kernels_shipped rt_kernels rt_comm; do
+  for o in $OBJS; do
     cp $B/$o.o $1/
     (cd $1 && $LLVM/llvm-objdump --offloading $o.o > /dev/null && mv $o.o.0.hipv4-amdgcn-amd-amdhsa--gfx950 $o.co && rm -f $o.o.0.host* $o.o)
     $LLVM/llvm-objdump -d --no-show-raw-insn $1/$o.co \
@@ -31,7 +33,7 @@ case $1 in
   compare)
     rm -rf /tmp/isa_now
     dump /tmp/isa_now
-    for o in rt_kernels_shipped rt_kernels rt_comm; do
+    for o in $OBJS; do
       for f in $(cut -f1 $2/$o.isa | sort -u); do
         a=$(body "$f" $2/$o.isa | md5sum | cut -c1-12)
         b=$(body "$f" /tmp/isa_now/$o.isa | md5sum | cut -c1-12)

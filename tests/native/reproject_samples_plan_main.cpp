@@ -21,8 +21,7 @@
 
 #include "../../include/rt_status.h"
 #include "../../mini-opencl-raytracer_amd/csrc/rt_reproject_plan.hpp"
-
-static const rtp::TemporalView kDefaultView = {{0.0f, -25.0f, 8.5f}, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}};
+#include "image_pass_common.hpp"
 
 static rtp::ReprojectIn sized(uint64_t w, uint64_t h) {
     rtp::ReprojectIn in{};
@@ -38,12 +37,6 @@ static rtp::ReprojectIn sized(uint64_t w, uint64_t h) {
 static rtp::ReprojectIn base_in() { return sized(131, 77); }
 
 // ---- errors -------------------------------------------------------------------------------------
-
-static bool finite_view(const rtp::TemporalView& v) {
-    for (int c = 0; c < 3; ++c)
-        if (!std::isfinite(v.pos[c]) || !std::isfinite(v.front[c]) || !std::isfinite(v.up[c])) return false;
-    return true;
-}
 
 // the documented order, spelled independently of the plan
 static int expected(const rtp::ReprojectIn& in) {
