@@ -141,6 +141,30 @@ public:
               "Failed to update vertices");
     }
     inline void RefitBVH(std::shared_ptr<CLKernel> kernel) const;
+    // extensions: motion records (rt_hip.h).  ExtractVertices is UpdateVertices' inverse, the "before" snapshot
+    // of a move; HitMotion and FrameMotion give per hit / per pixel the surface point at the previous time
+    // (prevPositions null: nothing moved; prevNormals null: the current normals); the two Motion calls are
+    // TemporalAccumulate and ReprojectSamples whose previous points come from such records (motion null: the
+    // plain calls)
+    void ExtractVertices(const Buffer& tris, size_t firstTri, size_t nTris, const Buffer& positions,
+                         const Buffer* normals = nullptr) const {
+        check(rtEnqueueExtractVertices(ctx_, tris.get(), firstTri, nTris, positions.get(),
+                                       normals ? normals->get() : nullptr),
+              "Failed to extract vertices");
+    }
+    inline void HitMotion(std::shared_ptr<CLKernel> kernel, const Buffer& hits, size_t first, size_t n,
+                          const Buffer* prevPositions, const Buffer* prevNormals, size_t firstTri, size_t nTris,
+                          const Buffer& motion) const;
+    inline void FrameMotion(std::shared_ptr<CLKernel> kernel, size_t globalWorkSize, const Buffer* prevPositions,
+                            const Buffer* prevNormals, size_t firstTri, size_t nTris, const Buffer& motion) const;
+    inline void TemporalAccumulateMotion(std::shared_ptr<CLKernel> kernel, const Buffer& cur, const Buffer& curFeatures,
+                                         const Buffer* hist, const Buffer* histFeatures, const Buffer* motion,
+                                         unsigned width, unsigned height, const rt_temporal_params& params,
+                                         const Buffer& out) const;
+    inline void ReprojectSamplesMotion(std::shared_ptr<CLKernel> kernel, const Buffer& histStats,
+                                       const Buffer& histFeatures, const Buffer& curFeatures, const Buffer* motion,
+                                       unsigned width, unsigned height, const rt_reproject_params& params,
+                                       const Buffer& outStats) const;
     void Finish() const { check(rtFinish(ctx_), "Failed to finish queue"); }
     rt_context GetContext() const { return ctx_; }
 
@@ -254,6 +278,38 @@ inline void CLContext::SamplePixels(std::shared_ptr<CLKernel> kernel, const Buff
 }
 inline void CLContext::RefitBVH(std::shared_ptr<CLKernel> kernel) const {
     check(rtRefitBVH(ctx_, kernel->GetKernel()), "Failed to refit BVH");
+}
+inline void CLContext::HitMotion(std::shared_ptr<CLKernel> kernel, const Buffer& hits, size_t first, size_t n,
+                                 const Buffer* prevPositions, const Buffer* prevNormals, size_t firstTri, size_t nTris,
+                                 const Buffer& motion) const {
+    check(rtEnqueueHitMotion(ctx_, kernel->GetKernel(), hits.get(), first, n,
+                             prevPositions ? prevPositions->get() : nullptr, prevNormals ? prevNormals->get() : nullptr,
+                             firstTri, nTris, motion.get()),
+          "Failed to enqueue hit motion");
+}
+inline void CLContext::FrameMotion(std::shared_ptr<CLKernel> kernel, size_t globalWorkSize, const Buffer* prevPositions,
+                                   const Buffer* prevNormals, size_t firstTri, size_t nTris, const Buffer& motion) const {
+    check(rtEnqueueFrameMotion(ctx_, kernel->GetKernel(), globalWorkSize, prevPositions ? prevPositions->get() : nullptr,
+                               prevNormals ? prevNormals->get() : nullptr, firstTri, nTris, motion.get()),
+          "Failed to enqueue frame motion");
+}
+inline void CLContext::TemporalAccumulateMotion(std::shared_ptr<CLKernel> kernel, const Buffer& cur,
+                                                const Buffer& curFeatures, const Buffer* hist, const Buffer* histFeatures,
+                                                const Buffer* motion, unsigned width, unsigned height,
+                                                const rt_temporal_params& params, const Buffer& out) const {
+    check(rtEnqueueTemporalAccumulateMotion(ctx_, kernel->GetKernel(), cur.get(), curFeatures.get(),
+                                            hist ? hist->get() : nullptr, histFeatures ? histFeatures->get() : nullptr,
+                                            motion ? motion->get() : nullptr, width, height, &params, out.get()),
+          "Failed to enqueue temporal accumulate with motion");
+}
+inline void CLContext::ReprojectSamplesMotion(std::shared_ptr<CLKernel> kernel, const Buffer& histStats,
+                                              const Buffer& histFeatures, const Buffer& curFeatures, const Buffer* motion,
+                                              unsigned width, unsigned height, const rt_reproject_params& params,
+                                              const Buffer& outStats) const {
+    check(rtEnqueueReprojectSamplesMotion(ctx_, kernel->GetKernel(), histStats.get(), histFeatures.get(),
+                                          curFeatures.get(), motion ? motion->get() : nullptr, width, height, &params,
+                                          outStats.get()),
+          "Failed to enqueue sample reprojection with motion");
 }
 
 }  // namespace rtcl

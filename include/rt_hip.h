@@ -864,13 +864,115 @@ int rtEnqueueReprojectSamples(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt
  * another context or NULL (`normals` excepted) RT_INVALID_MEM_OBJECT; `positions` or `normals` the
  * same buffer as `tris` RT_INVALID_MEM_OBJECT; first_tri + n_tris beyond `tris`, or `positions` /
  * `normals` smaller than 48 * n_tris, RT_INVALID_BUFFER_SIZE.  n_tris == 0: RT_SUCCESS, no launch.
- * The caller restarts a progressive accumulation, as after a camera move. */
+ * What was accumulated from the old geometry is the caller's choice: restart it, as after a camera move,
+ * or take the "before" vertices with rtEnqueueExtractVertices just ahead of the update and carry the
+ * history across with the motion records below (rtEnqueueFrameMotion and the two ...Motion calls). */
 typedef struct rt_tri_points { rt_float3 p1, p2, p3; } rt_tri_points; /* 48 B, w ignored */
 int rtEnqueueUpdateVertices(rt_context ctx, rt_mem tris, size_t first_tri, size_t n_tris, rt_mem positions,
                             rt_mem normals /* may be NULL */);
 int rtRefitBVH(rt_context ctx, rt_kernel k);
 /* counts since kernel creation: full host-side scene preparations, device refits */
 int rtDiagScenePrepares(rt_kernel k, uint64_t* full, uint64_t* refits);
+
+/* ---- motion records: where a surface point was at the previous time (extension) ----------------
+ * The two reprojections above know the camera's motion only.  A motion record says, per hit or per
+ * pixel, where the surface point that is seen now was before the geometry moved, so that they can
+ * follow it (rtEnqueueTemporalAccumulateMotion, rtEnqueueReprojectSamplesMotion).
+ *
+ * rtEnqueueExtractVertices is the inverse of rtEnqueueUpdateVertices: records [0, n_tris) of `positions`
+ * (and, when non-NULL, `normals`) receive v1/v2/v3.position.xyz (.normal.xyz) of triangles
+ * [first_tri, first_tri + n_tris) of `tris` as rt_tri_points, the w slots written as 0.  `tris` is only
+ * read.  Ordering is rtEnqueueUpdateVertices': asynchronous on the context's in-order queue, coalesced
+ * per-frame launches first, never waiting on the host -- a caller takes the "before" snapshot on the
+ * device, just ahead of the update.  Errors (nothing is launched), rtEnqueueUpdateVertices' in its order:
+ * a buffer of another context or NULL (`normals` excepted), or an output that is `tris`, or `positions`
+ * and `normals` one buffer, RT_INVALID_MEM_OBJECT; first_tri + n_tris beyond `tris`, or an output
+ * smaller than 48 * n_tris, RT_INVALID_BUFFER_SIZE.  n_tris == 0: RT_SUCCESS, no launch.
+ *
+ * rtEnqueueHitMotion: hits in, previous surface points out, in the mould of rtEnqueueHitSurfaces.  For
+ * records [first, first + n) of `hits` (rt_ray_hit, as a query wrote them; the rays are not needed) it
+ * writes the same slots of `motion` (rt_pixel_motion).  `prev_positions` (and `prev_normals`) hold the
+ * vertices of triangles [first_tri, first_tri + n_tris) at the previous time, as rtEnqueueExtractVertices
+ * wrote them; every other triangle, and every normal when `prev_normals` is NULL, is where the scene
+ * bound to k has it now.  The definition is the same in every math mode of k; every operation is one
+ * correctly rounded fp32 operation, nothing is contracted, denormals are kept, `/` and sqrtf are IEEE.
+ * Per record h = hits[i], with nTris the scene's triangle count:
+ *   miss        (uint32)h.prim >= nTris (one unsigned compare: negative indices too) writes prim = -1 and
+ *               every other word 0.
+ *   moved       moved = (uint64)h.prim - first_tri < n_tris, unsigned: n_tris == 0 moves nothing.
+ *   vertices    P1..P3 = prev_positions[h.prim - first_tri] when moved, else the current
+ *               v1/v2/v3.position.xyz of the 256-B record; N1..N3 = prev_normals[h.prim - first_tri] when
+ *               moved and prev_normals is non-NULL, else the current v*.normal.xyz.
+ *   point       w = (1.0f - h.u) - h.v;  prev_point.c = P1.c * w + (P2.c * h.u + P3.c * h.v)
+ *   normal      nn.c = N1.c * w + (N2.c * h.u + N3.c * h.v);  l2 = dot3(nn, nn);
+ *               prev_normal = l2 > 0 ? nn * (1.0f / sqrtf(l2)) : 0   (per component; false for a NaN)
+ *   record      prim = h.prim, flags = moved ? RT_MOTION_MOVED : 0.
+ * u and v may have any bit pattern (IEEE leaves the sign and payload of a NaN result open); nothing read from
+ * `hits` but the range-tested prim forms an address.
+ * `hits`, the prev_* buffers and the scene are never written; slots of `motion` outside the range are
+ * not touched.  Ordering, timing and launch counting are rtEnqueueHitSurfaces' (one launch).
+ * Errors (nothing is launched), in this order after the context, the kernel and `hits`:
+ * RT_INVALID_VALUE for first + n > 2^31; RT_INVALID_MEM_OBJECT for `motion` NULL, another context's or
+ * `hits` itself, prev_positions NULL with n_tris != 0, a given prev_* buffer of another context or the
+ * same as `motion`; RT_INVALID_BUFFER_SIZE for a range beyond `hits` or `motion`, or a given prev_*
+ * buffer under 48 * n_tris bytes; RT_INVALID_KERNEL_ARGS for an unbound scene or node slot;
+ * RT_INVALID_BUFFER_SIZE for first_tri + n_tris beyond the scene's triangle count.  n == 0: RT_SUCCESS.
+ *
+ * rtEnqueueFrameMotion: for every pixel gid in [0, global_work_size), x = gid % WIDTH, y = gid / WIDTH,
+ * the closest hit of the pixel's centre ray followed by rtEnqueueHitMotion's record of it, as one fused
+ * launch: no ray and no hit goes through memory.
+ *   the ray     one definition in every math mode: origin = k's camera position;
+ *               dir = (right * sx + up * sy) + front per component, with sx, sy and
+ *               right = cross(front, up) exactly as step 2 of rtEnqueueTemporalAccumulate states them
+ *               and its host constants taken from k's WIDTH, HEIGHT and camera slots; not normalised;
+ *               tmin = -INFINITY, tmax = 100000.0f.  No operation of it is contracted.
+ *   the hit     RT_QUERY_CLOSEST's answer for that rt_ray in k's math mode (InitRay normalises dir
+ *               there), its u and v as the query re-evaluates them.  rtKernelForceGlobalScene, the
+ *               node-collapse records and the rt_stats counters behave as for a query.
+ *   the record  rtEnqueueHitMotion's, for {prim, u, v}.
+ * After rtEnqueueUpdateVertices and rtRefitBVH the call sees the moved geometry without a full
+ * preparation.  Ordering is rtEnqueueFrameFeatures'; with timing on the call counts as one launch.
+ * Errors (nothing is launched), in this order after the context, the kernel and `motion`:
+ * RT_INVALID_KERNEL_ARGS for an unbound scene, node, WIDTH, HEIGHT or camera slot, or WIDTH or HEIGHT
+ * zero or WIDTH * HEIGHT > 2^31; RT_INVALID_GLOBAL_WORK_SIZE for zero or more than 2^31;
+ * RT_INVALID_BUFFER_SIZE for `motion` under 32 B per work item; then rtEnqueueHitMotion's rows for the
+ * prev_* arguments; then a query's (RT_INVALID_OPERATION: a leaf of more than 127 triangles). */
+#define RT_MOTION_MOVED 1u
+typedef struct rt_pixel_motion {
+    float prev_point[3];   /* the surface point at the previous time */
+    int32_t prim;          /* the triangle that is seen now; -1: none, every other word 0 */
+    float prev_normal[3];  /* the unit shading normal there at the previous time, or 0 */
+    uint32_t flags;        /* RT_MOTION_MOVED: the triangle is one of [first_tri, first_tri + n_tris) */
+} rt_pixel_motion; /* 32 B */
+int rtEnqueueExtractVertices(rt_context ctx, rt_mem tris, size_t first_tri, size_t n_tris, rt_mem positions,
+                             rt_mem normals /* may be NULL */);
+int rtEnqueueHitMotion(rt_context ctx, rt_kernel k, rt_mem hits, size_t first, size_t n,
+                       rt_mem prev_positions /* NULL only when n_tris == 0 */, rt_mem prev_normals /* may be NULL */,
+                       size_t first_tri, size_t n_tris, rt_mem motion);
+int rtEnqueueFrameMotion(rt_context ctx, rt_kernel k, size_t global_work_size,
+                         rt_mem prev_positions /* NULL only when n_tris == 0 */, rt_mem prev_normals /* may be NULL */,
+                         size_t first_tri, size_t n_tris, rt_mem motion);
+
+/* rtEnqueueTemporalAccumulateMotion and rtEnqueueReprojectSamplesMotion.  With `motion` NULL each is
+ * its counterpart above exactly: the same bytes, the same errors.  With `motion`, width * height
+ * rt_pixel_motion records of the current view (rtEnqueueFrameMotion's), the definitions change in three
+ * places only:
+ *   1 centre    additionally "no history" / "nothing carried" when motion[p].prim < 0.
+ *   2 point     X = motion[p].prev_point.
+ *   5 taps      the centre normal is motion[p].prev_normal, not f.normal.
+ * Steps 3, 4 and 6 stand as they are.  f.depth and params->cur no longer enter the arithmetic; both
+ * are still validated.  X may have any bit pattern: the range test of step 4 comes before any integer
+ * conversion, and a tap's index is formed only after its coordinates were tested against the image.
+ * `motion` is never written.  Additional errors, with their rows: RT_INVALID_MEM_OBJECT for a `motion`
+ * of another context or the same buffer as the output; RT_INVALID_BUFFER_SIZE for one under 32 B per
+ * pixel. */
+int rtEnqueueTemporalAccumulateMotion(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem cur_features,
+                                      rt_mem hist /* may be NULL */, rt_mem hist_features /* NULL iff hist is */,
+                                      rt_mem motion /* may be NULL */, unsigned width, unsigned height,
+                                      const rt_temporal_params* params, rt_mem out);
+int rtEnqueueReprojectSamplesMotion(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt_mem hist_features,
+                                    rt_mem cur_features, rt_mem motion /* may be NULL */, unsigned width,
+                                    unsigned height, const rt_reproject_params* params, rt_mem out_stats);
 
 /* Where the scene lives: 1 = staged in LDS (when it fits), 0 = read from HBM/L2. */
 int rtKernelGetSceneInLDS(rt_kernel k, int* in_lds);

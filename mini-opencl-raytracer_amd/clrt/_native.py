@@ -87,6 +87,11 @@ assert SURFACE_DTYPE.itemsize == 64 and PIXEL_FEATURES_DTYPE.itemsize == 32
 # rt_tri_points (rt_hip.h): the records of rtEnqueueUpdateVertices, three float3 slots (w ignored)
 TRI_POINTS_DTYPE = np.dtype([("p1", FLOAT3), ("p2", FLOAT3), ("p3", FLOAT3)])
 assert TRI_POINTS_DTYPE.itemsize == 48
+# rt_pixel_motion (rt_hip.h): the records of rtEnqueueHitMotion and rtEnqueueFrameMotion
+PIXEL_MOTION_DTYPE = np.dtype([("prev_point", np.float32, (3,)), ("prim", np.int32),
+                               ("prev_normal", np.float32, (3,)), ("flags", np.uint32)])
+assert PIXEL_MOTION_DTYPE.itemsize == 32
+MOTION_MOVED = 1
 
 # RenderKernelArgument_t (CLutils.h:11-27)
 BUFFER_OUT, BUFFER_SCENE, BUFFER_NODE, BUFFER_MATERIAL = 0, 1, 2, 3
@@ -252,7 +257,15 @@ _HIP_PROTOS = {
                                                    ctypes.POINTER(TEMPORAL_PARAMS), _vp]),
     "rtEnqueueReprojectSamples": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
                                                  ctypes.POINTER(REPROJECT_PARAMS), _vp]),
+    "rtEnqueueTemporalAccumulateMotion": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
+                                                         ctypes.POINTER(TEMPORAL_PARAMS), _vp]),
+    "rtEnqueueReprojectSamplesMotion": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint, ctypes.c_uint,
+                                                       ctypes.POINTER(REPROJECT_PARAMS), _vp]),
     "rtEnqueueUpdateVertices": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
+    "rtEnqueueExtractVertices": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
+    "rtEnqueueHitMotion": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t,
+                                          ctypes.c_size_t, _vp]),
+    "rtEnqueueFrameMotion": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtRefitBVH": (ctypes.c_int, [_vp, _vp]),
     "rtDiagScenePrepares": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "rtEnqueueReadBuffer": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, _vp]),

@@ -203,29 +203,39 @@ class CLContext:
                            hist_features: "Buffer | None", width: int, height: int, out: "Buffer", cur_view,
                            prev_view, cur_frames: float = 1.0, history_frames: float = 0.0,
                            max_history: float = 32.0, depth_tolerance: float = 0.05,
-                           normal_threshold: float = 0.9) -> None:
+                           normal_threshold: float = 0.9, motion: "Buffer | None" = None) -> None:
         """rtEnqueueTemporalAccumulate: the previous image `hist` (with its features, both None when
         there is no history yet) reprojected from `prev_view` into `cur_view` and blended with `cur` by
         per-pixel sample count into `out`; images are width x height 16-B {r, g, b, w} slots, `out`'s w
         the new sample count.  A view is (position, front, up), three xyz triples.  Asynchronous; no
-        input is written."""
+        input is written.  With `motion` (width x height N.PIXEL_MOTION_DTYPE records of the current
+        view, FrameMotion's) it is rtEnqueueTemporalAccumulateMotion: each pixel's previous point and
+        normal come from its record, so the history follows geometry that moved."""
         def view(v):
             pos, front, up = v
             return N.VIEW((ctypes.c_float * 3)(*map(float, pos)), (ctypes.c_float * 3)(*map(float, front)),
                           (ctypes.c_float * 3)(*map(float, up)))
         params = N.TEMPORAL_PARAMS(view(cur_view), view(prev_view), float(cur_frames), float(history_frames),
                                    float(max_history), float(depth_tolerance), float(normal_threshold))
+        hist_h = hist.handle if hist is not None else None
+        hist_features_h = hist_features.handle if hist_features is not None else None
+        if motion is not None:
+            check(self._lib.rtEnqueueTemporalAccumulateMotion(self.handle, kernel.handle, cur.handle, cur_features.handle,
+                                                              hist_h, hist_features_h, motion.handle, int(width),
+                                                              int(height), ctypes.byref(params), out.handle),
+                  "Failed to enqueue temporal accumulate with motion")
+            return
         check(self._lib.rtEnqueueTemporalAccumulate(self.handle, kernel.handle, cur.handle, cur_features.handle,
-                                                    hist.handle if hist is not None else None,
-                                                    hist_features.handle if hist_features is not None else None,
+                                                    hist_h, hist_features_h,
                                                     int(width), int(height), ctypes.byref(params), out.handle),
               "Failed to enqueue temporal accumulate")
 
     def ReprojectSamples(self, kernel: "CLKernel", hist_stats: "Buffer", hist_features: "Buffer",
                          cur_features: "Buffer", width: int, height: int, out_stats: "Buffer", cur_view, prev_view,
                          max_history: float = 16.0, depth_tolerance: float = 0.05,
-                         normal_threshold: float = 0.9) -> None:
-        """rtEnqueueReprojectSamples: the width x height sample statistics `hist_stats`
+                         normal_threshold: float = 0.9, motion: "Buffer | None" = None) -> None:
+        """rtEnqueueReprojectSamples (with `motion`, the current view's N.PIXEL_MOTION_DTYPE records:
+        rtEnqueueReprojectSamplesMotion, whose previous points and normals come from the records): the width x height sample statistics `hist_stats`
         (N.PIXEL_STATS_DTYPE, with the features of their view) reprojected from `prev_view` into `cur_view`
         and recombined into `out_stats`: per pixel a mean, a per-sample variance and an integer sample
         count of at most `max_history` from the history taps on the same surface, or 32 zero bytes (no
@@ -237,6 +247,13 @@ class CLContext:
                           (ctypes.c_float * 3)(*map(float, up)))
         params = N.REPROJECT_PARAMS(view(cur_view), view(prev_view), float(max_history), float(depth_tolerance),
                                     float(normal_threshold))
+        if motion is not None:
+            check(self._lib.rtEnqueueReprojectSamplesMotion(self.handle, kernel.handle, hist_stats.handle,
+                                                            hist_features.handle, cur_features.handle, motion.handle,
+                                                            int(width), int(height), ctypes.byref(params),
+                                                            out_stats.handle),
+                  "Failed to enqueue sample reprojection with motion")
+            return
         check(self._lib.rtEnqueueReprojectSamples(self.handle, kernel.handle, hist_stats.handle, hist_features.handle,
                                                   cur_features.handle, int(width), int(height), ctypes.byref(params),
                                                   out_stats.handle), "Failed to enqueue sample reprojection")
@@ -248,6 +265,37 @@ class CLContext:
         check(self._lib.rtEnqueueUpdateVertices(self.handle, tris.handle, int(first), int(n), positions.handle,
                                                 normals.handle if normals is not None else None),
               "Failed to update vertices")
+
+    def ExtractVertices(self, tris: "Buffer", first: int, n: int, positions: "Buffer",
+                        normals: "Buffer | None" = None) -> None:
+        """rtEnqueueExtractVertices, UpdateVertices' inverse: records [0, n) of `positions` / `normals`
+        (N.TRI_POINTS_DTYPE, w slots 0) from the position (and normal) xyz of triangles [first, first + n)
+        of `tris`; asynchronous.  The "before" snapshot of a move, taken on the device."""
+        check(self._lib.rtEnqueueExtractVertices(self.handle, tris.handle, int(first), int(n), positions.handle,
+                                                 normals.handle if normals is not None else None),
+              "Failed to extract vertices")
+
+    def HitMotion(self, kernel: "CLKernel", hits: "Buffer", first: int, n: int, motion: "Buffer",
+                  prev_positions: "Buffer | None" = None, prev_normals: "Buffer | None" = None, first_tri: int = 0,
+                  n_tris: int = 0) -> None:
+        """rtEnqueueHitMotion: for hits [first, first + n) of `hits` (N.RAY_HIT_DTYPE) the surface point and
+        normal at the previous time into the same slots of `motion` (N.PIXEL_MOTION_DTYPE): triangles
+        [first_tri, first_tri + n_tris) take their vertices from `prev_positions` / `prev_normals`
+        (N.TRI_POINTS_DTYPE, ExtractVertices' records), the others from the scene bound to `kernel`."""
+        check(self._lib.rtEnqueueHitMotion(self.handle, kernel.handle, hits.handle, int(first), int(n),
+                                           prev_positions.handle if prev_positions is not None else None,
+                                           prev_normals.handle if prev_normals is not None else None, int(first_tri),
+                                           int(n_tris), motion.handle), "Failed to enqueue hit motion")
+
+    def FrameMotion(self, kernel: "CLKernel", work_size: int, motion: "Buffer",
+                    prev_positions: "Buffer | None" = None, prev_normals: "Buffer | None" = None, first_tri: int = 0,
+                    n_tris: int = 0) -> None:
+        """rtEnqueueFrameMotion: per work-item the closest hit of the pixel's centre ray and HitMotion's
+        record of it (N.PIXEL_MOTION_DTYPE), one fused launch."""
+        check(self._lib.rtEnqueueFrameMotion(self.handle, kernel.handle, int(work_size),
+                                             prev_positions.handle if prev_positions is not None else None,
+                                             prev_normals.handle if prev_normals is not None else None, int(first_tri),
+                                             int(n_tris), motion.handle), "Failed to enqueue frame motion")
 
     def RefitBVH(self, kernel: "CLKernel") -> None:
         """rtRefitBVH: the bounds of the tree bound to `kernel` from its triangles, on the device, into the

@@ -60,6 +60,10 @@ class Raytracer:
         self._temporal_view: tuple | None = None  # the camera of the last temporal() (None: no history)
         self._move_bufs: tuple | None = None  # (capacity in triangles, positions, normals) of move_vertices()
         self._move_keep: list = []            # host arrays of uploads still in the queue
+        # move_vertices(keep_previous=True): the vertices before the move ("pos", "nrm"; "live" while they are
+        # the scene's previous state), who has used them ("used"), whether the sample statistics' features
+        # were taken with them ("feat": their n_frames, or None), and FrameMotion's records ("records")
+        self._motion: dict | None = None
 
     # CLRaytracer::Init (CLRaytracer.cpp:104-120)
     def Init(self) -> None:
@@ -86,6 +90,7 @@ class Raytracer:
         for old in self._scene_bufs:
             old.release()
         self._scene_bufs = [tb, nb, mb]
+        self._drop_motion()   # (a snapshot of another scene's vertices)
         self.kernel.set_buffer(N.BUFFER_SCENE, tb)
         self.kernel.set_buffer(N.BUFFER_NODE, nb)
         self.kernel.set_buffer(N.BUFFER_MATERIAL, mb)
@@ -255,8 +260,8 @@ class Raytracer:
         rtEnqueueAccumulateSamples run over the list.  At the end the statistics are resolved
         (rtEnqueueResolveSamples) into a kept buffer.  Returns the (H, W, 4) image, whose w slot is the
         pixel's sample count, and a dict: rounds run, paths traced, and the last select's selected / hot.
-        The statistics persist across calls: reproject_samples() or reset_samples() after a camera move,
-        reset_samples() after move_vertices().
+        The statistics persist across calls: reproject_samples() or reset_samples() after a camera move;
+        after move_vertices(keep_previous=True) reproject_samples_motion(), else reset_samples().
         frame_count and BUFFER_OUT are left as they are.  `on_sample(round, sample_frame, n, buffers)` is
         called after each sample's calls are enqueued (buffers: ids, results, stats; for tools and tests).
 
@@ -352,9 +357,10 @@ class Raytracer:
 
     def reset_samples(self) -> None:
         """Zero render_adaptive()'s statistics and restart its sample frames at 1: after a camera move or
-        move_vertices() the samples taken so far are of another image.  After a camera move alone
-        reproject_samples() carries them over instead; after move_vertices() this stays the tool, since a
-        moved surface invalidates a reprojection that knows the camera's motion only."""
+        move_vertices() the samples taken so far are of another image.  reproject_samples() carries them
+        over instead after a camera move, reproject_samples_motion() after move_vertices(keep_previous=True).
+        After a plain move_vertices() this stays the tool, since a reprojection without motion records knows
+        the camera's motion only."""
         work = self.width * self.height
         self.ctx.WriteBuffer(self._adaptive_buffers()["stats"], np.zeros(work, N.PIXEL_STATS_DTYPE))
         self._sample_frame = 1
@@ -372,8 +378,24 @@ class Raytracer:
         frames 1 .. n_frames at `prev` and at the current camera.  The result goes into a second kept
         buffer, which becomes render_adaptive()'s statistics buffer (the two swap at every call); the
         sample frames go on counting, so the samples that follow draw fresh seeds.  Nothing is read back;
-        the camera, frame_count and BUFFER_OUT are left as they are.  After move_vertices() use
-        reset_samples(): a moved surface invalidates a reprojection that knows the camera's motion only."""
+        the camera, frame_count and BUFFER_OUT are left as they are.
+        Moving geometry: this call knows the camera's motion only, so after move_vertices() the choice is
+        reset_samples() or, when the move was made with keep_previous=True, reproject_samples_motion()."""
+        self._reproject_samples(prev, n_frames, max_history, depth_tolerance, normal_threshold, False)
+
+    def reproject_samples_motion(self, prev: Camera, n_frames: int = 4, max_history: float = 16.0,
+                                 depth_tolerance: float = 0.05, normal_threshold: float = 0.9) -> None:
+        """reproject_samples() across moved geometry (rtEnqueueReprojectSamplesMotion): the call after
+        move_vertices(keep_previous=True), with or without a camera move (`prev` may be the current camera).
+        Every pixel's previous point and normal come from rtEnqueueFrameMotion's records over the kept
+        vertices, so the statistics follow the surfaces that moved, and the history features are the ones
+        move_vertices() took before the move, not recomputed from the moved scene.  The kept vertices then
+        count as used by this call; without any (no such move since the last call) the records say where
+        the surfaces are now, and the history features are taken at `prev` as reproject_samples() does.
+        The arguments and everything else are reproject_samples()'."""
+        self._reproject_samples(prev, n_frames, max_history, depth_tolerance, normal_threshold, True)
+
+    def _reproject_samples(self, prev, n_frames, max_history, depth_tolerance, normal_threshold, motion) -> None:
         b = self._adaptive_buffers()
         work = self.width * self.height
         if "spare" not in b:
@@ -384,21 +406,25 @@ class Raytracer:
                                                                  work * N.PIXEL_FEATURES_DTYPE.itemsize)
         hist_feat, cur_feat = self._reproject_feat
         at, cam = self.frame_count, self.camera
+        kept = motion and self._motion is not None and self._motion["live"] and self._motion["feat"] is not None \
+            and "samples" not in self._motion["used"]
         self.frame_count = 1
         try:
-            self.camera = prev
-            try:
-                self._enqueue_features(n_frames, hist_feat)
-            finally:
-                self.camera = cam
+            if not kept:
+                self.camera = prev
+                try:
+                    self._enqueue_features(n_frames, hist_feat)
+                finally:
+                    self.camera = cam
             self._enqueue_features(n_frames, cur_feat)
         finally:
             self.frame_count = at
             self.set_uniforms()   # (the kernel's camera slots and FRAME_COUNT, whatever was enqueued)
         view = (tuple(cam.position), tuple(cam.front), tuple(cam.up))
         prev_view = (tuple(prev.position), tuple(prev.front), tuple(prev.up))
+        mb = self._enqueue_motion("samples") if motion else None
         self.ctx.ReprojectSamples(self.kernel, b["stats"], hist_feat, cur_feat, self.width, self.height, b["spare"],
-                                  view, prev_view, max_history, depth_tolerance, normal_threshold)
+                                  view, prev_view, max_history, depth_tolerance, normal_threshold, motion=mb)
         b["stats"], b["spare"] = b["spare"], b["stats"]
 
     def features(self, n_frames: int = 1) -> np.ndarray:
@@ -495,7 +521,7 @@ class Raytracer:
         return out, var
 
     def temporal(self, n_frames: int | None = None, max_history: float = 32.0, depth_tolerance: float = 0.05,
-                 normal_threshold: float = 0.9) -> np.ndarray:
+                 normal_threshold: float = 0.9, motion: bool = False) -> np.ndarray:
         """The accumulated image joined with the result of the previous temporal() call, which is
         reprojected into the current camera on the device (rtEnqueueTemporalAccumulate), as an (H, W, 4)
         float32 array whose w slot is the pixel's sample count (at most max_history, which is raised to
@@ -505,9 +531,14 @@ class Raytracer:
         the current camera, as in denoise(); with n_frames None, of the frames rendered so far.  So after
         a camera move (frame_count = 1 and a few new frames) the converged image is carried over instead
         of thrown away.  The first call, and the first after reset_history(), has no history and returns
-        the image with w = n_frames.  Call reset_history() after move_vertices(): a moved surface
-        invalidates the reprojection, which knows the camera's motion only.  The accumulation buffer
-        is only read and frame_count stays, so the progressive render goes on."""
+        the image with w = n_frames.  The accumulation buffer is only read and frame_count stays, so the
+        progressive render goes on.
+        Moving geometry: without `motion` the reprojection knows the camera's motion only, so after
+        move_vertices() the choice is reset_history() or, when the move was made with keep_previous=True,
+        motion=True.  With `motion` every pixel's previous point and normal come from
+        rtEnqueueFrameMotion's records over the kept vertices (rtEnqueueTemporalAccumulateMotion), so the
+        history follows the moved surfaces; the kept vertices then count as used by this call, and without
+        any (no such move since the last call) the records say where the surfaces are now."""
         if n_frames is None:
             n_frames = min(max(self.frame_count - 1, 1), 4096)
         work = self.width * self.height
@@ -525,11 +556,12 @@ class Raytracer:
             self.kernel.set_uint(N.FRAME_COUNT, at)
         view = (tuple(self.camera.position), tuple(self.camera.front), tuple(self.camera.up))
         has = self._temporal_view is not None
+        mb = self._enqueue_motion("temporal") if motion else None
         self.ctx.TemporalAccumulate(self.kernel, self.output, fb, self._temporal_img[prev] if has else None,
                                     self._temporal_feat[prev] if has else None, self.width, self.height,
                                     self._temporal_img[now], view, self._temporal_view if has else view,
                                     float(n_frames), 0.0, max(float(max_history), float(n_frames)), depth_tolerance,
-                                    normal_threshold)
+                                    normal_threshold, motion=mb)
         out = np.empty((self.height, self.width, 4), np.float32)
         self.ctx.ReadBuffer(self._temporal_img[now], out, blocking=True)
         self._temporal_at, self._temporal_view = now, view
@@ -539,14 +571,91 @@ class Raytracer:
         """Drop temporal()'s history: the next call starts from the current image alone."""
         self._temporal_view = None
 
-    def move_vertices(self, positions, normals=None, first: int = 0) -> None:
+    def motion(self) -> np.ndarray:
+        """The motion records of the current camera's centre rays (rtEnqueueFrameMotion) as an (H, W) array
+        of N.PIXEL_MOTION_DTYPE: per pixel the first hit's triangle (-1: none), and where that surface
+        point and its normal were before the last move_vertices(keep_previous=True) -- for triangles that
+        did not move, and when no vertices are kept, where they are now.  The kept vertices stay unused."""
+        mb = self._enqueue_motion(None)
+        out = np.empty((self.height, self.width), N.PIXEL_MOTION_DTYPE)
+        self.ctx.ReadBuffer(mb, out, blocking=True)
+        return out
+
+    def _enqueue_motion(self, user: str | None) -> Buffer:
+        """FrameMotion at the current camera into the kept record buffer: over the kept vertices while they
+        are live and `user` has not used them yet (they then count as used by it), else with nothing moved."""
+        m = self._motion_state()
+        if m["records"] is None:
+            m["records"] = self.ctx.create_buffer(N.MEM_READ_WRITE,
+                                                  self.width * self.height * N.PIXEL_MOTION_DTYPE.itemsize)
+        use = m["live"] and user not in m["used"]
+        self.set_uniforms()
+        self.ctx.FrameMotion(self.kernel, self.width * self.height, m["records"], m["pos"] if use else None,
+                             m["nrm"] if use else None, 0, m["n"] if use else 0)
+        if use and user is not None:
+            m["used"].add(user)
+        return m["records"]
+
+    def _motion_state(self) -> dict:
+        if self._motion is None:
+            self._motion = {"n": 0, "pos": None, "nrm": None, "records": None, "live": False, "used": set(),
+                            "feat": None}
+        return self._motion
+
+    def _drop_motion(self) -> None:
+        if self._motion:
+            for key in ("pos", "nrm", "records"):
+                if self._motion[key]:
+                    self._motion[key].release()
+        self._motion = None
+
+    def _keep_previous(self, n_frames: int) -> None:
+        """Before a move: the whole triangle array's vertices into the kept buffers (ExtractVertices), unless
+        kept vertices that nobody has used yet are still live -- they are then the older "before".  With
+        sample statistics, the features at the current camera go into reproject_samples()' history-feature
+        buffer, since they must predate the move."""
+        m = self._motion_state()
+        if m["live"] and not m["used"]:
+            return
+        n = self._scene_bufs[0].size // N.TRIANGLE_DTYPE.itemsize
+        if m["pos"] is None or m["n"] != n:
+            for key in ("pos", "nrm"):
+                if m[key]:
+                    m[key].release()
+                m[key] = self.ctx.create_buffer(N.MEM_READ_WRITE, n * N.TRI_POINTS_DTYPE.itemsize)
+            m["n"] = n
+        self.ctx.ExtractVertices(self._scene_bufs[0], 0, n, m["pos"], m["nrm"])
+        m["live"], m["used"], m["feat"] = True, set(), None
+        if self._adaptive is not None:
+            if self._reproject_feat[0] is None:
+                self._reproject_feat[0] = self.ctx.create_buffer(
+                    N.MEM_READ_WRITE, self.width * self.height * N.PIXEL_FEATURES_DTYPE.itemsize)
+            at = self.frame_count
+            self.frame_count = 1
+            try:
+                self._enqueue_features(n_frames, self._reproject_feat[0])
+            finally:
+                self.frame_count = at
+                self.kernel.set_uint(N.FRAME_COUNT, at)
+            m["feat"] = n_frames
+
+    def move_vertices(self, positions, normals=None, first: int = 0, keep_previous: bool = False,
+                      feature_frames: int = 4) -> None:
         """Move triangles [first, first + n) of the uploaded scene and refit its BVH on the device
         (rtEnqueueUpdateVertices + rtRefitBVH; nothing waits on the host).  `positions` -- and `normals`
         when given -- are (n, 3, 3) arrays (triangle, vertex, xyz) or n N.TRI_POINTS_DTYPE records, in
         the uploaded triangle order (BVH leaf order).  The tree's topology stays: a caller whose tree has
         degraded after large deformations builds a new one.  The output buffer still holds the frames
         accumulated from the old geometry: the caller restarts the progressive accumulation (frame_count
-        = 1), as the reference does on a camera move.  The device buffers are kept and reused."""
+        = 1), as the reference does on a camera move.  The device buffers are kept and reused.
+        What was converged before the move -- temporal()'s history, render_adaptive()'s statistics -- is
+        the caller's choice: drop it (reset_history(), reset_samples()), or move with keep_previous=True
+        and carry it across with temporal(motion=True) / reproject_samples_motion().  keep_previous
+        copies the whole triangle array's vertices aside on the device just ahead of the update
+        (rtEnqueueExtractVertices), at the first such move since one of those calls used the copy, so
+        several moves between two of them add up to one motion; when sample statistics exist it also takes
+        the features of frames 1 .. feature_frames at the current camera, the history features
+        reproject_samples_motion() needs from before the move."""
         recs = [self._tri_points(positions)]
         if normals is not None:
             recs.append(self._tri_points(normals))
@@ -555,6 +664,8 @@ class Raytracer:
         n = len(recs[0])
         if n == 0:
             return
+        if keep_previous:
+            self._keep_previous(feature_frames)
         if self._move_bufs is None or self._move_bufs[0] < n:
             if self._move_bufs:
                 self._move_bufs[1].release()
@@ -656,6 +767,7 @@ class Raytracer:
             self._move_bufs[2].release()
             self._move_bufs = None
         self._move_keep = []
+        self._drop_motion()
         if self.output:
             self.output.release()
         if self.kernel:

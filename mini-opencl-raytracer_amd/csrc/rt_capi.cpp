@@ -43,6 +43,8 @@
 #include "rt_kernel_state.hpp"
 #include "rt_kernels.hpp"
 #include "rt_launch_plan.hpp"
+#include "rt_motion_launch.hpp"
+#include "rt_motion_plan.hpp"
 #include "rt_query_plan.hpp"
 #include "rt_refit.hpp"
 #include "rt_reproject.hpp"
@@ -1121,9 +1123,10 @@ int rtEnqueueDenoiseSamples(rt_context ctx, rt_kernel k, rt_mem stats, rt_mem fe
 
 // ---- temporal reprojection (rt_temporal.hip; the plan: rt_temporal_plan.cpp) -----------------------
 
-int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem cur_features, rt_mem hist,
-                                rt_mem hist_features, unsigned width, unsigned height,
-                                const rt_temporal_params* params, rt_mem out) {
+// (motion null: rtEnqueueTemporalAccumulate itself)
+static int enqueue_temporal(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem cur_features, rt_mem hist,
+                            rt_mem hist_features, rt_mem motion, unsigned width, unsigned height,
+                            const rt_temporal_params* params, rt_mem out) {
     // 1. the handles and the plan: nothing is launched on an error
     int rc = queue_head(ctx, k, {});
     if (rc) return rc;
@@ -1142,7 +1145,9 @@ int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem 
     in.out_ok = out && out->ctx == ctx;
     in.hist_ok = hist && hist->ctx == ctx;
     in.hist_features_ok = hist_features && hist_features->ctx == ctx;
-    in.out_is_input = out && (out == cur || out == cur_features || out == hist || out == hist_features);
+    in.out_is_input = out && (out == cur || out == cur_features || out == hist || out == hist_features || out == motion);
+    in.motion_given = motion != nullptr, in.motion_ok = motion && motion->ctx == ctx;
+    in.motion_bytes = in.motion_ok ? motion->size : 0;
     in.cur_bytes = in.cur_ok ? cur->size : 0;
     in.cur_features_bytes = in.cur_features_ok ? cur_features->size : 0;
     in.hist_bytes = in.hist_ok ? hist->size : 0;
@@ -1158,17 +1163,32 @@ int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem 
     a.hist = p.has_history ? static_cast<const float4*>(hist->dptr) : nullptr;
     a.hist_features = p.has_history ? static_cast<const float4*>(hist_features->dptr) : nullptr;
     a.out = static_cast<float4*>(out->dptr);
+    const float4* records = p.has_motion ? static_cast<const float4*>(motion->dptr) : nullptr;
     a.width = p.width, a.height = p.height, a.tilesX = p.tiles_x;
     a.cur_frames = p.cur_frames, a.history_frames = p.history_frames, a.max_history = p.max_history;
     a.depth_tolerance = p.depth_tolerance, a.normal_threshold = p.normal_threshold;
     a.k = p.k;
-    return launch_on_queue(ctx, k, out, [&](hipStream_t st) { return rtt::launch_temporal(a, p, st); });
+    return launch_on_queue(ctx, k, out, [&](hipStream_t st) { return rtt::launch_temporal(a, records, p, st); });
+}
+
+int rtEnqueueTemporalAccumulate(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem cur_features, rt_mem hist,
+                                rt_mem hist_features, unsigned width, unsigned height,
+                                const rt_temporal_params* params, rt_mem out) {
+    return enqueue_temporal(ctx, k, cur, cur_features, hist, hist_features, nullptr, width, height, params, out);
+}
+
+int rtEnqueueTemporalAccumulateMotion(rt_context ctx, rt_kernel k, rt_mem cur, rt_mem cur_features, rt_mem hist,
+                                      rt_mem hist_features, rt_mem motion, unsigned width, unsigned height,
+                                      const rt_temporal_params* params, rt_mem out) {
+    return enqueue_temporal(ctx, k, cur, cur_features, hist, hist_features, motion, width, height, params, out);
 }
 
 // ---- reprojection of the sample statistics (rt_reproject.hip; the plan: rt_reproject_plan.cpp) ------
 
-int rtEnqueueReprojectSamples(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt_mem hist_features, rt_mem cur_features,
-                              unsigned width, unsigned height, const rt_reproject_params* params, rt_mem out_stats) {
+// (motion null: rtEnqueueReprojectSamples itself)
+static int enqueue_reproject(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt_mem hist_features, rt_mem cur_features,
+                             rt_mem motion, unsigned width, unsigned height, const rt_reproject_params* params,
+                             rt_mem out_stats) {
     // 1. the handles and the plan: nothing is launched on an error
     int rc = queue_head(ctx, k, {});
     if (rc) return rc;
@@ -1184,7 +1204,10 @@ int rtEnqueueReprojectSamples(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt
     in.hist_features_ok = hist_features && hist_features->ctx == ctx;
     in.cur_features_ok = cur_features && cur_features->ctx == ctx;
     in.out_ok = out_stats && out_stats->ctx == ctx;
-    in.out_is_input = out_stats && (out_stats == hist_stats || out_stats == hist_features || out_stats == cur_features);
+    in.out_is_input = out_stats && (out_stats == hist_stats || out_stats == hist_features || out_stats == cur_features ||
+                                    out_stats == motion);
+    in.motion_given = motion != nullptr, in.motion_ok = motion && motion->ctx == ctx;
+    in.motion_bytes = in.motion_ok ? motion->size : 0;
     in.hist_stats_bytes = in.hist_stats_ok ? hist_stats->size : 0;
     in.hist_features_bytes = in.hist_features_ok ? hist_features->size : 0;
     in.cur_features_bytes = in.cur_features_ok ? cur_features->size : 0;
@@ -1198,10 +1221,22 @@ int rtEnqueueReprojectSamples(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt
     a.hist_features = static_cast<const float4*>(hist_features->dptr);
     a.cur_features = static_cast<const float4*>(cur_features->dptr);
     a.out_stats = static_cast<float4*>(out_stats->dptr);
+    const float4* records = p.has_motion ? static_cast<const float4*>(motion->dptr) : nullptr;
     a.width = p.width, a.height = p.height, a.tilesX = p.tiles_x;
     a.max_history = p.max_history, a.depth_tolerance = p.depth_tolerance, a.normal_threshold = p.normal_threshold;
     a.k = p.k;
-    return launch_on_queue(ctx, k, out_stats, [&](hipStream_t st) { return rtrs::launch_reproject(a, p, st); });
+    return launch_on_queue(ctx, k, out_stats, [&](hipStream_t st) { return rtrs::launch_reproject(a, records, p, st); });
+}
+
+int rtEnqueueReprojectSamples(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt_mem hist_features, rt_mem cur_features,
+                              unsigned width, unsigned height, const rt_reproject_params* params, rt_mem out_stats) {
+    return enqueue_reproject(ctx, k, hist_stats, hist_features, cur_features, nullptr, width, height, params, out_stats);
+}
+
+int rtEnqueueReprojectSamplesMotion(rt_context ctx, rt_kernel k, rt_mem hist_stats, rt_mem hist_features,
+                                    rt_mem cur_features, rt_mem motion, unsigned width, unsigned height,
+                                    const rt_reproject_params* params, rt_mem out_stats) {
+    return enqueue_reproject(ctx, k, hist_stats, hist_features, cur_features, motion, width, height, params, out_stats);
 }
 
 // ---- adaptive sampling (rt_adaptive.hip, rt_trace.hpp; the plans: rt_adaptive_plan.cpp) -------------
@@ -1445,6 +1480,133 @@ int rtDiagScenePrepares(rt_kernel k, uint64_t* full, uint64_t* refits) {
     if (full) *full = k->scene.full_prepares();
     if (refits) *refits = k->scene.refits();
     return RT_SUCCESS;
+}
+
+// ---- motion records (rt_motion.hip, rt_motion.hpp; the plans: rt_motion_plan.cpp) ------------------
+
+int rtEnqueueExtractVertices(rt_context ctx, rt_mem tris, size_t first_tri, size_t n_tris, rt_mem positions,
+                             rt_mem normals) {
+    int rc = ensure_device(ctx);
+    if (rc) return rc;
+    rtp::ExtractIn in{};
+    in.tris_ok = tris && tris->ctx == ctx, in.positions_ok = positions && positions->ctx == ctx;
+    in.normals_given = normals != nullptr, in.normals_ok = normals && normals->ctx == ctx;
+    in.out_is_tris = tris && (positions == tris || normals == tris);
+    in.outs_same = positions && positions == normals;
+    in.tris_bytes = in.tris_ok ? tris->size : 0, in.positions_bytes = in.positions_ok ? positions->size : 0;
+    in.normals_bytes = in.normals_ok ? normals->size : 0;
+    in.first_tri = first_tri, in.n_tris = n_tris;
+    rtp::ExtractPlan p;
+    rc = rtp::extract_plan(in, &p);
+    if (rc || p.nothing) return rc;
+    // coalesced frames launch first: they were enqueued before this snapshot
+    rc = flush_first(ctx);
+    if (rc) return rc;
+    const hipError_t e = rtmo::launch_extract_vertices(static_cast<const rt_cl_triangle*>(tris->dptr), p,
+                                                       static_cast<float4*>(positions->dptr),
+                                                       normals ? static_cast<float4*>(normals->dptr) : nullptr, qs(ctx));
+    if (e != hipSuccess) return map_hip(e);
+    mark_device_write(positions, true);
+    if (normals) mark_device_write(normals, true);
+    return pending_error(ctx, RT_SUCCESS);
+}
+
+// the prev_* arguments of the two motion calls as their plans take them
+static rtp::PrevIn prev_inputs(rt_context ctx, rt_mem prev_positions, rt_mem prev_normals, size_t first_tri,
+                               size_t n_tris, rt_mem out) {
+    rtp::PrevIn in{};
+    in.positions_given = prev_positions != nullptr, in.positions_ok = prev_positions && prev_positions->ctx == ctx;
+    in.normals_given = prev_normals != nullptr, in.normals_ok = prev_normals && prev_normals->ctx == ctx;
+    in.is_out = out && (prev_positions == out || prev_normals == out);
+    in.positions_bytes = in.positions_ok ? prev_positions->size : 0;
+    in.normals_bytes = in.normals_ok ? prev_normals->size : 0;
+    in.first_tri = first_tri, in.n_tris = n_tris;
+    return in;
+}
+
+int rtEnqueueHitMotion(rt_context ctx, rt_kernel k, rt_mem hits, size_t first, size_t n, rt_mem prev_positions,
+                       rt_mem prev_normals, size_t first_tri, size_t n_tris, rt_mem motion) {
+    // 1. the handles and the ranges: no scene is packed and nothing launched on an error
+    int rc = queue_head(ctx, k, {hits});
+    if (rc) return rc;
+    rtp::HitMotionIn in{};
+    in.first = first, in.n = n;
+    in.hits_bytes = hits->size;
+    in.out_ok = motion && motion->ctx == ctx;
+    in.out_bytes = in.out_ok ? motion->size : 0;
+    in.out_is_hits = motion == hits;
+    in.scene_bound = k->args.has({RT_ARG_BUFFER_SCENE, RT_ARG_BUFFER_NODE});
+    in.scene_tris = in.scene_bound ? k->args.tris()->size / sizeof(rt_cl_triangle) : 0;
+    in.prev = prev_inputs(ctx, prev_positions, prev_normals, first_tri, n_tris, motion);
+    rtp::HitMotionPlan p;
+    rc = rtp::hit_motion_plan(in, &p);
+    if (rc || p.nothing) return pending_error(ctx, rc);
+    // 2. the scene, packed and validated as a query does (materials only when bound)
+    rc = prepare_scene(k, k->args);
+    if (rc) return rc;
+    if ((uint64_t)p.first_tri + p.n_tris > k->scene.n_tris()) return RT_INVALID_BUFFER_SIZE;
+    // 3. the launch, on the context's stream after the pending accumulations and gathers
+    rtmo::HitMotionArgs a{};
+    a.hits = static_cast<const float4*>(hits->dptr);
+    a.tris = static_cast<const rt_cl_triangle*>(k->args.tris()->dptr);
+    a.n_scene = k->scene.n_tris();
+    a.prev_positions = p.n_tris ? static_cast<const float4*>(prev_positions->dptr) : nullptr;
+    a.prev_normals = p.n_tris && prev_normals ? static_cast<const float4*>(prev_normals->dptr) : nullptr;
+    a.out = static_cast<float4*>(motion->dptr);
+    return launch_on_queue(ctx, k, motion, [&](hipStream_t st) { return rtmo::launch_hit_motion(a, p, st); });
+}
+
+int rtEnqueueFrameMotion(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem prev_positions,
+                         rt_mem prev_normals, size_t first_tri, size_t n_tris, rt_mem motion) {
+    // 1. the handles and the arguments: nothing is packed or launched on an error
+    int rc = queue_head(ctx, k, {motion});
+    if (rc) return rc;
+    rtp::FrameMotionIn in{};
+    in.args_bound = k->args.has({RT_ARG_BUFFER_SCENE, RT_ARG_BUFFER_NODE, RT_ARG_WIDTH, RT_ARG_HEIGHT,
+                                 RT_ARG_CAMERA_POS, RT_ARG_CAMERA_FRONT, RT_ARG_CAMERA_UP});
+    rtk::KernelArgs cam;
+    std::memset(&cam, 0, sizeof(cam));
+    if (in.args_bound) {
+        fill_camera(k->args, 0, &cam);
+        in.scene_tris = k->args.tris()->size / sizeof(rt_cl_triangle);
+    }
+    in.width = cam.width, in.height = cam.height;
+    for (int c = 0; c < 3; ++c) in.cam.pos[c] = cam.camPos[c], in.cam.front[c] = cam.camFront[c], in.cam.up[c] = cam.camUp[c];
+    in.global_work_size = global_work_size;
+    in.out_bytes = motion->size;
+    in.prev = prev_inputs(ctx, prev_positions, prev_normals, first_tri, n_tris, motion);
+    rtp::FrameMotionPlan mp;
+    rc = rtp::frame_motion_plan(in, &mp);
+    if (rc) return pending_error(ctx, rc);
+    // 2. the scene, and the plan of the closest-hit query over one ray per pixel (RT_INVALID_OPERATION:
+    // a leaf of more than 127 triangles, as for queries)
+    rc = prepare_scene(k, k->args);
+    if (rc) return rc;
+    if ((uint64_t)mp.first_tri + mp.n_tris > k->scene.n_tris()) return RT_INVALID_BUFFER_SIZE;
+    const size_t gws = global_work_size;
+    const rtp::QueryIn qin =
+        query_inputs(ctx, k, gws * rtp::kRayBytes, 0, gws, RT_QUERY_CLOSEST, gws * rtp::kHitBytes, false, true);
+    rtp::QueryPlan qp;
+    rc = rtp::query_shape(qin, &qp);
+    if (rc) return rc;
+    rtp::query_grid(qin, k->occ.get(rtk::Family::Motion, qp.variant, qp.smem), &qp);
+    // 3. the arguments: the query's, the current vertices and the image width
+    rtk::KernelArgs a;
+    rtk::QueryArgs q;
+    fill_query_args(k, qp, nullptr, nullptr, &a, &q);
+    a.trisFull = static_cast<const rt_cl_triangle*>(k->args.tris()->dptr);
+    a.width = cam.width, a.height = cam.height;
+    rtk::MotionArgs m{};
+    m.prevPositions = mp.n_tris ? static_cast<const float4*>(prev_positions->dptr) : nullptr;
+    m.prevNormals = mp.n_tris && prev_normals ? static_cast<const float4*>(prev_normals->dptr) : nullptr;
+    m.out = static_cast<float4*>(motion->dptr);
+    m.firstTri = mp.first_tri, m.nTris = mp.n_tris;
+    m.count = mp.count, m.nUnits = qp.nUnits, m.refillMin = qp.refillMin;
+    m.k = mp.k;
+    // 4. one launch, on the context's stream after the pending accumulations and gathers
+    k->last_lds = qp.variant.lds();
+    return launch_on_queue(ctx, k, motion,
+                           [&](hipStream_t st) { return rtk::launch_motion(a, m, qp.variant, qp.grid, qp.smem, st); });
 }
 
 // the host waits for the context's queue

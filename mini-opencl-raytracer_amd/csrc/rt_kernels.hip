@@ -115,13 +115,15 @@ static const Policy& policy(int math) {
                                      pack_mats,
                                      hit_surfaces<MathDeviceLib, false>, hit_surfaces<MathDeviceLib, true>,
                                      trace_pick<MathDeviceLib>, camera_paths<MathDeviceLib>,
-                                     camera_paths_for<MathDeviceLib>, sample_pick<MathDeviceLib>};
+                                     camera_paths_for<MathDeviceLib>, sample_pick<MathDeviceLib>,
+                                     motion_pick<MathDeviceLib>};
     static const Policy pinned = {pick_entry<MathPinned>,   wf_pick<MathPinned>,  query_pick<MathPinned>,
                                   accum_frames<MathPinned>, accum_key<MathPinned>, camera_rays<MathPinned>,
                                   pack_mats,
                                   hit_surfaces<MathPinned, false>, hit_surfaces<MathPinned, true>,
                                      trace_pick<MathPinned>, camera_paths<MathPinned>,
-                                     camera_paths_for<MathPinned>, sample_pick<MathPinned>};
+                                     camera_paths_for<MathPinned>, sample_pick<MathPinned>,
+                                     motion_pick<MathPinned>};
     return math == MathShipped::kId ? shipped_policy() : math == MathDeviceLib::kId ? devicelib : pinned;
 }
 
@@ -158,6 +160,13 @@ hipError_t launch_wavefront(const KernelArgs& a, WfArgs w, float4* const q[2], u
 hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, const Variant& v, unsigned grid, size_t smem,
                         hipStream_t st) {
     hipLaunchKernelGGL(policy(v.math).query(v), dim3(grid), dim3(kQueryThreads), smem, st, a, q);
+    return hipGetLastError();
+}
+
+// ---- motion records of the camera's centre rays (rt_motion.hpp) ------------------------------------
+hipError_t launch_motion(const KernelArgs& a, const MotionArgs& m, const Variant& v, unsigned grid, size_t smem,
+                         hipStream_t st) {
+    hipLaunchKernelGGL(policy(v.math).motion(v), dim3(grid), dim3(kQueryThreads), smem, st, a, m);
     return hipGetLastError();
 }
 
@@ -217,6 +226,7 @@ int OccupancyCache::get(Family f, const Variant& v, size_t smem) {
         case Family::Query: fn = reinterpret_cast<const void*>(p.query(v)), threads = kQueryThreads; break;
         case Family::Trace: fn = reinterpret_cast<const void*>(p.trace(v)), threads = kTraceThreads; break;
         case Family::Sample: fn = reinterpret_cast<const void*>(p.sample(v)), threads = kTraceThreads; break;
+        case Family::Motion: fn = reinterpret_cast<const void*>(p.motion(v)), threads = kQueryThreads; break;
     }
     int blocks = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, threads, smem) != hipSuccess) blocks = 1;

@@ -8,6 +8,7 @@
 
 #include "../../include/rt_cl_types.h"
 #include "rt_layout.hpp"
+#include "rt_temporal_math.hpp"
 
 namespace rtk {
 
@@ -122,6 +123,22 @@ hipError_t launch_query(const KernelArgs& a, const QueryArgs& q, const Variant& 
 // rtEnqueueCameraRays: width, height, frameCount and the camera slots of `a`; one rt_ray per work-item
 hipError_t launch_camera_rays(const KernelArgs& a, float4* rays, uint32_t n, int math, hipStream_t st);
 
+// ---- motion records of the camera's centre rays (rt_motion.hpp) ------------------------------------
+// rtEnqueueFrameMotion: KernelArgs carries what a query's does plus trisFull (the current vertices).
+struct MotionArgs {
+    const float4* prevPositions;  // rt_tri_points of triangles [firstTri, firstTri + nTris); null: nTris == 0
+    const float4* prevNormals;    // null: the current normals
+    float4* out;                  // rt_pixel_motion records as 2 x float4, one per pixel
+    uint32_t firstTri, nTris;     // the moved range, inside the scene's triangles
+    uint32_t count;               // pixels [0, count)
+    uint32_t nUnits;              // 64-pixel units (the last one may be partial)
+    uint32_t refillMin;           // take new pixels once this many lanes are free
+    rtt::TemporalConsts k;        // the host constants of the centre ray (the current view's)
+};
+using MotionKernelFn = void (*)(KernelArgs, MotionArgs);
+hipError_t launch_motion(const KernelArgs& a, const MotionArgs& m, const Variant& v, unsigned grid, size_t smem,
+                         hipStream_t st);
+
 // ---- path tracing over caller rays (rt_trace.hpp) -------------------------------------------------
 // rtEnqueueTracePaths: KernelArgs carries the packed scene with its shading and material records
 // (packedTris, octNodes, shadeTris, shadeMats, nNodes, nTris, nMats, octStride, octB, octRecords),
@@ -190,13 +207,13 @@ hipError_t launch_pack(const rt_cl_triangle* tris, uint32_t n_tris, float4* pt, 
 // Workgroups per CU of a kernel at a dynamic LDS size, remembered per (kernel family, variant): the
 // runtime is asked on the first use and again when the LDS size differs.  The kernel is picked as
 // the launch picks it, from the same Variant.
-enum class Family : int { Entry, WfExtend, WfShade, Query, Trace, Sample };
+enum class Family : int { Entry, WfExtend, WfShade, Query, Trace, Sample, Motion };
 struct OccupancyCache {
     struct Entry {
         int blocks;   // 0: not asked yet
         size_t smem;
     };
-    Entry e[(int)Family::Sample + 1][kVariantSlots] = {};
+    Entry e[(int)Family::Motion + 1][kVariantSlots] = {};
     int get(Family f, const Variant& v, size_t smem);
 };
 
@@ -216,6 +233,7 @@ struct Policy {
     void (*camera_paths)(KernelArgs, float4*, uint32_t*, uint32_t);
     void (*camera_paths_for)(KernelArgs, const uint32_t*, uint32_t, uint32_t, float4*, uint32_t*);
     SampleKernelFn (*sample)(const Variant&);
+    MotionKernelFn (*motion)(const Variant&);
 };
 const Policy& shipped_policy();
 // the step schedule's entry points are specialised per launch kind (step_body kMode: 1 fused, 2

@@ -1957,4 +1957,5 @@ __device__ __forceinline__ void material_record(const rt_cl_material& m, float4*
 #include "rt_query.hpp"
 #include "rt_trace.hpp"
 #include "rt_sample.hpp"
+#include "rt_motion.hpp"
 #include "rt_surface.hpp"

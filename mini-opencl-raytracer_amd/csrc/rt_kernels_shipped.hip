@@ -64,7 +64,8 @@ const Policy& shipped_policy() {
                                    pack_mats_shipped,
                                    hit_surfaces<MathShipped, false>, hit_surfaces<MathShipped, true>,
                                    trace_pick<MathShipped>, camera_paths<MathShipped>,
-                                   camera_paths_for<MathShipped>, sample_pick<MathShipped>};
+                                   camera_paths_for<MathShipped>, sample_pick<MathShipped>,
+                                   motion_pick<MathShipped>};
     return shipped;
 }
 

@@ -15,7 +15,9 @@
 // node and triangle steps in bursts chosen by the step weights.  Two scene paths: octant records
 // and packed triangles staged in LDS, or both read from HBM/L2 (no shading records either way).
 // The walk uses record indices (oct_step), not LDS byte addresses, so it does not depend on where
-// the dynamic LDS starts.
+// the dynamic LDS starts.  The loop takes its two ends -- where a unit of rays comes from, where a
+// finished walk goes -- as a parameter (QueryEnds here; rt_motion.hpp's MotionEnds make the rays from
+// pixel indices and store motion records).
 #pragma once
 
 namespace rtk {
@@ -41,8 +43,32 @@ __device__ __forceinline__ bool query_triangle(const float4* tri, int32_t idx, c
     return ok;
 }
 
-template <class M, bool kStats, bool kBofs, bool kGlobalOct, bool kAny>
-__device__ __forceinline__ void query_body(const KernelArgs& a, const QueryArgs& q) {
+// The query's two ends, which rtEnqueueFrameMotion replaces (rt_motion.hpp: MotionEnds), the way
+// rtEnqueueSamplePixels replaces the trace's:
+//   n_units  64-ray units of the launch;
+//   base     the position (`pos` below) of the first ray of the unit whose first ray is u0;
+//   fill     the wave's ring takes that unit: returns its ray count;
+//   finish   the lane's walk of ray `pos` ended with h (prim -1: a miss) and the barycentrics u, v.
+struct QueryEnds {
+    const QueryArgs& q;
+    __device__ __forceinline__ uint32_t n_units() const { return q.nUnits; }
+    // the unit's records as 128 float4s, two coalesced loads per lane (the last unit of the range may
+    // be partial)
+    __device__ __forceinline__ uint32_t base(uint32_t u0) const { return q.first + u0; }
+    __device__ __forceinline__ uint32_t fill(uint32_t u0, uint32_t lane, float4* ring) const {
+        const uint32_t n = min(64u, q.count - u0);
+        const float4* src = q.rays + 2 * (size_t)base(u0);
+        if (lane < 2u * n) ring[lane] = src[lane];
+        if (lane + 64u < 2u * n) ring[lane + 64u] = src[lane + 64u];
+        return n;
+    }
+    __device__ __forceinline__ void finish(uint32_t pos, const Traversal& h, float u, float v) const {
+        q.hits[pos] = make_float4(__int_as_float(h.prim), h.t, u, v);
+    }
+};
+
+template <class M, bool kStats, bool kBofs, bool kGlobalOct, bool kAny, class Ends>
+__device__ __forceinline__ void query_body(const KernelArgs& a, const Ends& q, uint32_t refillMin) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     const uint32_t tid = threadIdx.x, nthr = blockDim.x;
     SceneView sc;
@@ -90,32 +116,27 @@ __device__ __forceinline__ void query_body(const KernelArgs& a, const QueryArgs&
                 v = e.v;
                 if (kStats) ++st.hits;
             }
-            q.hits[pos] = make_float4(__int_as_float(h.prim), h.t, u, v);
+            q.finish(pos, h, u, v);
             cur = kNotWalking;
         }
         uint32_t n_trav = popc_ballot(cur < kLeafMin);
         uint32_t n_leaf = popc_ballot((int32_t)cur >= (int32_t)kLeafMin);
-        if (!exhausted && 64u - (n_trav + n_leaf) >= q.refillMin) {
+        if (!exhausted && 64u - (n_trav + n_leaf) >= refillMin) {
             // ---- free lanes take rays from the ring; an empty ring loads the next unit ----------
             for (;;) {
                 const bool idle = cur == kNotWalking;
                 const unsigned long long im = __ballot(idle);
                 if (im == 0ull) break;
                 if (rc_n == 0u) {
-                    if (unit >= q.nUnits) {
+                    if (unit >= q.n_units()) {
                         exhausted = true;
                         break;
                     }
-                    // the unit's records as 128 float4s, two coalesced loads per lane (the last
-                    // unit of the range may be partial)
                     const uint32_t u0 = unit * 64u;
                     unit += nwaves;
-                    rc_base = q.first + u0;
-                    rc_n = min(64u, q.count - u0);
+                    rc_base = q.base(u0);
+                    rc_n = q.fill(u0, lane, ring);
                     rc_head = 0;
-                    const float4* src = q.rays + 2 * (size_t)rc_base;
-                    if (lane < 2u * rc_n) ring[lane] = src[lane];
-                    if (lane + 64u < 2u * rc_n) ring[lane + 64u] = src[lane + 64u];
                 }
                 const uint32_t rank = lane_rank(im);
                 const uint32_t take = min((uint32_t)__popcll(im), rc_n);
@@ -192,7 +213,7 @@ __device__ __forceinline__ void camera_rays_body(const KernelArgs& a, float4* ra
 template <class M, bool kStats, bool kBofs, bool kGlobalOct, bool kAny>
 __global__ __launch_bounds__(kQueryThreads) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void query_rays(KernelArgs a, QueryArgs q) {
-    query_body<M, kStats, kBofs, kGlobalOct, kAny>(a, q);
+    query_body<M, kStats, kBofs, kGlobalOct, kAny>(a, QueryEnds{q}, q.refillMin);
 }
 template <class M>
 __global__ __launch_bounds__(256) void camera_rays(KernelArgs a, float4* rays, uint32_t n) {

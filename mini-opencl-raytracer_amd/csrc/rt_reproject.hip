@@ -14,6 +14,9 @@
 // inside the image, independent of one another, and then the statistics of those taps only whose
 // features passed the surface tests -- across a disocclusion edge or off the image nothing more is read.
 //
+// The motion variant (rtEnqueueReprojectSamplesMotion) takes step 2's point and step 5's centre normal from a
+// 32-B rt_pixel_motion stream instead of the depth.
+//
 // Steps 2-4 -- where a depth read from a buffer decides an address -- are rt_temporal_math.hpp, and the
 // merge is rt_reproject_math.hpp: the texts a CPU program runs under sanitizers.  A tap's index exists
 // only after its integer coordinates were tested against the image; no value of the statistics takes
@@ -26,13 +29,16 @@ namespace rtrs {
 
 namespace {
 
-__global__ __launch_bounds__(rtt::kThreads) void reproject_samples(ReprojectArgs a) {
+template <bool kMotion>
+__device__ __forceinline__ void reproject_body(const ReprojectArgs& a, const float4* motion) {
     const rtt::Pixel px = rtt::tile_pixel(a.tilesX);
     const uint64_t x = px.x, y = px.y;
     if (x >= a.width || y >= a.height) return;
     const uint64_t p = y * a.width + x;
     const float4 fa = a.cur_features[2 * p], fn = a.cur_features[2 * p + 1];  // {albedo, depth}, {normal, coverage}
-    const rtt::Centre ce = rtt::centre_of(rtt::reproject(a.k, (uint32_t)x, (uint32_t)y, fa.w), fn, a.depth_tolerance);
+    const rtt::Centre ce =
+        kMotion ? rtt::centre_of_motion(a.k, motion[2 * p], motion[2 * p + 1], fn.w, a.depth_tolerance)
+                : rtt::centre_of(rtt::reproject(a.k, (uint32_t)x, (uint32_t)y, fa.w), fn, a.depth_tolerance);
     const rtt::Reprojection& r = ce.r;
     // the features of the taps inside the image, then the statistics of those on the centre's surface
     uint64_t q[4];
@@ -68,13 +74,22 @@ __global__ __launch_bounds__(rtt::kThreads) void reproject_samples(ReprojectArgs
     a.out_stats[2 * p + 1] = o1;
 }
 
+__global__ __launch_bounds__(rtt::kThreads) void reproject_samples(ReprojectArgs a) { reproject_body<false>(a, nullptr); }
+__global__ __launch_bounds__(rtt::kThreads) void reproject_samples_motion(ReprojectArgs a, const float4* motion) {
+    reproject_body<true>(a, motion);
+}
+
 }  // namespace
 
-hipError_t launch_reproject(const ReprojectArgs& a, const rtp::ReprojectPlan& p, hipStream_t st) {
+hipError_t launch_reproject(const ReprojectArgs& a, const float4* motion, const rtp::ReprojectPlan& p, hipStream_t st) {
     if (p.grid == 0 || a.width != p.width || a.height != p.height || a.tilesX != p.tiles_x ||
-        (uint64_t)p.tiles_x * p.tiles_y != p.grid || !a.hist_stats || !a.hist_features || !a.cur_features || !a.out_stats)
+        (uint64_t)p.tiles_x * p.tiles_y != p.grid || !a.hist_stats || !a.hist_features || !a.cur_features ||
+        !a.out_stats || p.has_motion != (motion != nullptr))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(reproject_samples, dim3(p.grid), dim3(rtt::kThreads), 0, st, a);
+    if (p.has_motion)
+        hipLaunchKernelGGL(reproject_samples_motion, dim3(p.grid), dim3(rtt::kThreads), 0, st, a, motion);
+    else
+        hipLaunchKernelGGL(reproject_samples, dim3(p.grid), dim3(rtt::kThreads), 0, st, a);
     return hipGetLastError();
 }
 

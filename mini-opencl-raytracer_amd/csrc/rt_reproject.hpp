@@ -21,6 +21,8 @@ struct ReprojectArgs {
 
 // One launch over p.grid workgroups on `st`.  hipErrorInvalidValue for a plan that does not match
 // the arguments: nothing is launched.
-hipError_t launch_reproject(const ReprojectArgs& a, const rtp::ReprojectPlan& p, hipStream_t st);
+// `motion` (rt_pixel_motion as two float4 per pixel) is non-null exactly when the plan has motion; it is a
+// kernel argument of its own, so the plain kernel keeps its arguments.
+hipError_t launch_reproject(const ReprojectArgs& a, const float4* motion, const rtp::ReprojectPlan& p, hipStream_t st);
 
 }  // namespace rtrs

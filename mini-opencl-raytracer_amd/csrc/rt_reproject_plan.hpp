@@ -26,10 +26,14 @@ struct ReprojectIn {
     bool hist_stats_ok, hist_features_ok, cur_features_ok, out_ok;  // each a buffer of this context
     bool out_is_input;                                              // `out_stats` is one of the three inputs
     uint64_t hist_stats_bytes, hist_features_bytes, cur_features_bytes, out_bytes;
+    // rtEnqueueReprojectSamplesMotion (all false / zero: rtEnqueueReprojectSamples itself)
+    bool motion_given, motion_ok;   // the handle is not NULL; a buffer of this context
+    uint64_t motion_bytes;
 };
 
 struct ReprojectPlan {
     uint32_t width, height;
+    bool has_motion;                // step 2 is motion[p].prev_point (rt_pixel_motion records)
     rtt::TemporalConsts k;
     float max_history, depth_tolerance, normal_threshold;
     uint32_t tiles_x, tiles_y;
@@ -39,8 +43,8 @@ struct ReprojectPlan {
 // RT_SUCCESS, or, in this order: RT_INVALID_VALUE (no params; width or height zero; width * height >
 // 2^31; a camera component not finite; max_history not finite, not an integer value, < 1 or > 2^20;
 // depth_tolerance not finite or outside [0, 1]; normal_threshold not finite or outside [-1, 1]),
-// RT_INVALID_MEM_OBJECT (a buffer that is not this context's; `out_stats` one of the inputs),
-// RT_INVALID_BUFFER_SIZE (any buffer below 32 B per pixel).
+// RT_INVALID_MEM_OBJECT (a buffer that is not this context's; `out_stats` one of the inputs, `motion` among
+// them), RT_INVALID_BUFFER_SIZE (any buffer below 32 B per pixel).
 int reproject_plan(const ReprojectIn& in, ReprojectPlan* out);
 
 }  // namespace rtp

@@ -12,7 +12,8 @@
 // reproject to neighbouring history pixels, and the 4 rows of a tile share their taps' rows.
 //
 // Steps 2-4 -- where a depth read from a buffer decides an address -- are rt_temporal_math.hpp, the
-// text a CPU program sweeps under sanitizers.  A tap's index exists only after its integer
+// text a CPU program sweeps under sanitizers.  The motion variant (rtEnqueueTemporalAccumulateMotion)
+// takes step 2's point and step 5's centre normal from a 32-B rt_pixel_motion stream instead.  A tap's index exists only after its integer
 // coordinates were tested against the image; taps that do not count are dropped by select.
 #include "rt_temporal.hpp"
 
@@ -20,8 +21,8 @@ namespace rtt {
 
 namespace {
 
-template <bool kHistory>
-__global__ __launch_bounds__(kThreads) void temporal_accumulate(TemporalArgs a) {
+template <bool kHistory, bool kMotion>
+__device__ __forceinline__ void temporal_body(const TemporalArgs& a, const float4* motion) {
     const Pixel px = tile_pixel(a.tilesX);
     const uint64_t x = px.x, y = px.y;
     if (x >= a.width || y >= a.height) return;
@@ -30,7 +31,8 @@ __global__ __launch_bounds__(kThreads) void temporal_accumulate(TemporalArgs a) 
     float4 o = make_float4(c.x, c.y, c.z, a.cur_frames);  // every "no history" row
     if (kHistory) {
         const float4 fa = a.cur_features[2 * p], fn = a.cur_features[2 * p + 1];  // {albedo, depth}, {normal, coverage}
-        const Centre ce = centre_of(reproject(a.k, (uint32_t)x, (uint32_t)y, fa.w), fn, a.depth_tolerance);
+        const Centre ce = kMotion ? centre_of_motion(a.k, motion[2 * p], motion[2 * p + 1], fn.w, a.depth_tolerance)
+                                  : centre_of(reproject(a.k, (uint32_t)x, (uint32_t)y, fa.w), fn, a.depth_tolerance);
         const Reprojection& r = ce.r;
         float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sn = 0.0f;
 #pragma unroll
@@ -65,16 +67,27 @@ __global__ __launch_bounds__(kThreads) void temporal_accumulate(TemporalArgs a) 
     a.out[p] = o;
 }
 
+template <bool kHistory>
+__global__ __launch_bounds__(kThreads) void temporal_accumulate(TemporalArgs a) {
+    temporal_body<kHistory, false>(a, nullptr);
+}
+__global__ __launch_bounds__(kThreads) void temporal_accumulate_motion(TemporalArgs a, const float4* motion) {
+    temporal_body<true, true>(a, motion);
+}
+
 }  // namespace
 
-hipError_t launch_temporal(const TemporalArgs& a, const rtp::TemporalPlan& p, hipStream_t st) {
+hipError_t launch_temporal(const TemporalArgs& a, const float4* motion, const rtp::TemporalPlan& p, hipStream_t st) {
     if (p.grid == 0 || a.width != p.width || a.height != p.height || a.tilesX != p.tiles_x ||
         (uint64_t)p.tiles_x * p.tiles_y != p.grid || p.has_history != (a.hist != nullptr) ||
         (a.hist != nullptr) != (a.hist_features != nullptr))
         return hipErrorInvalidValue;
-    if (p.has_history)
+    if (p.has_motion != (motion != nullptr)) return hipErrorInvalidValue;
+    if (p.has_history && p.has_motion)
+        hipLaunchKernelGGL(temporal_accumulate_motion, dim3(p.grid), dim3(kThreads), 0, st, a, motion);
+    else if (p.has_history)
         hipLaunchKernelGGL((temporal_accumulate<true>), dim3(p.grid), dim3(kThreads), 0, st, a);
-    else
+    else  // (no history: the motion records were validated and are not read)
         hipLaunchKernelGGL((temporal_accumulate<false>), dim3(p.grid), dim3(kThreads), 0, st, a);
     return hipGetLastError();
 }

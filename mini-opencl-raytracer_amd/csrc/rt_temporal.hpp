@@ -44,9 +44,21 @@ __device__ __forceinline__ Centre centre_of(Reprojection r, float4 fn, float dep
     r.ok = r.ok && fn.w > 0.0f;
     return Centre{r, {fn.x, fn.y, fn.z}, depth_tolerance * r.de};
 }
+// The motion variants' centre: the point is the record's prev_point (any bit pattern), a record without
+// a hit (prim < 0) has no history, and the taps are tested against the record's prev_normal.  `coverage`
+// is the current features'.
+__device__ __forceinline__ Centre centre_of_motion(const TemporalConsts& k, float4 m0, float4 m1, float coverage,
+                                                   float depth_tolerance) {
+    const float X[3] = {m0.x, m0.y, m0.z};
+    Reprojection r = reproject_point(k, X);
+    r.ok = r.ok && coverage > 0.0f && __float_as_int(m0.w) >= 0;
+    return Centre{r, {m1.x, m1.y, m1.z}, depth_tolerance * r.de};
+}
 
 // One launch over p.grid workgroups on `st`.  hipErrorInvalidValue for a plan that does not match
 // the arguments: nothing is launched.
-hipError_t launch_temporal(const TemporalArgs& a, const rtp::TemporalPlan& p, hipStream_t st);
+// `motion` (rt_pixel_motion as two float4 per pixel: {prev_point, prim}, {prev_normal, flags}) is non-null
+// exactly when the plan has motion; it is a kernel argument of its own, so the plain kernels keep theirs.
+hipError_t launch_temporal(const TemporalArgs& a, const float4* motion, const rtp::TemporalPlan& p, hipStream_t st);
 
 }  // namespace rtt

@@ -1,6 +1,9 @@
 // rt_temporal_math.hpp -- steps 2-4 of rtEnqueueTemporalAccumulate's definition (include/rt_hip.h):
 // the world point of a pixel, its projection into the previous view, the range test and the tap
-// indices; and step 5's surface test of a tap, which rtEnqueueReprojectSamples shares.  This is where a value read from a buffer (a depth) ends up deciding an address, so the
+// indices; and step 5's surface test of a tap, which rtEnqueueReprojectSamples shares.  Step 2 (the point)
+// and step 3 (project_point) are separate, because the motion variants take the point from a motion record
+// and rtEnqueueFrameMotion takes step 2's direction as its ray.  This is where a value read from a buffer (a
+// depth, a previous point) ends up deciding an address, so the
 // kernel (rt_temporal.hip) and a CPU program (tests/native/temporal_plan_main.cpp, built with
 // sanitizers) compile this same text: the address logic is swept on the CPU over every class of
 // bit pattern before a GPU runs it.
@@ -53,16 +56,25 @@ struct Projection {
     float de;       // its distance from the previous camera
 };
 
-// Steps 2 and 3 for pixel (x, y) with the current view's depth: floating point only, any bit pattern.
-RT_TM_FN Projection project(const TemporalConsts& k, uint32_t x, uint32_t y, float depth) {
-    // 2: the world point
+// Step 2's direction d of pixel (x, y)'s centre ray in the current view, not normalised (additions and
+// products only: the same in a translation unit with relaxed division; rtEnqueueFrameMotion's ray).
+RT_TM_FN void centre_dir(const TemporalConsts& k, uint32_t x, uint32_t y, float* d) {
     const float sx = ((2.0f * (((float)x + 0.5f) * k.invW) - 1.0f) * k.A) * k.asp;
     const float sy = (2.0f * (((float)y + 0.5f) * k.invH) - 1.0f) * k.A;
-    float d[3], X[3], v[3];
     for (int c = 0; c < 3; ++c) d[c] = (k.cright[c] * sx + k.cup[c] * sy) + k.cfront[c];
+}
+
+// Step 2: the world point of pixel (x, y) at the current view's depth.
+RT_TM_FN void world_point(const TemporalConsts& k, uint32_t x, uint32_t y, float depth, float* X) {
+    float d[3];
+    centre_dir(k, x, y, d);
     const float rl = 1.0f / sqrtf(dot3(d, d));
     for (int c = 0; c < 3; ++c) X[c] = k.cpos[c] + (d[c] * rl) * depth;
-    // 3: into the previous view
+}
+
+// Step 3 for the world point X: floating point only, any bit pattern.
+RT_TM_FN Projection project_point(const TemporalConsts& k, const float* X) {
+    float v[3];
     for (int c = 0; c < 3; ++c) v[c] = X[c] - k.ppos[c];
     Projection p;
     p.zf = dot3(v, k.pfront);
@@ -73,9 +85,15 @@ RT_TM_FN Projection project(const TemporalConsts& k, uint32_t x, uint32_t y, flo
     return p;
 }
 
-// Steps 2-4.  Defined for every bit pattern of `depth`.
-RT_TM_FN Reprojection reproject(const TemporalConsts& k, uint32_t x, uint32_t y, float depth) {
-    const Projection p = project(k, x, y, depth);
+// Steps 2 and 3 for pixel (x, y) with the current view's depth.
+RT_TM_FN Projection project(const TemporalConsts& k, uint32_t x, uint32_t y, float depth) {
+    float X[3];
+    world_point(k, x, y, depth, X);
+    return project_point(k, X);
+}
+
+// Step 4 on a projection.  Defined for every bit pattern in `p`.
+RT_TM_FN Reprojection in_range(const TemporalConsts& k, const Projection& p) {
     Reprojection r;
     r.ok = false, r.x0 = 0, r.y0 = 0, r.tx = 0.0f, r.ty = 0.0f, r.de = p.de;
     if (!(p.zf > 0.0f)) return r;
@@ -86,6 +104,17 @@ RT_TM_FN Reprojection reproject(const TemporalConsts& k, uint32_t x, uint32_t y,
     r.x0 = (int32_t)x0f, r.y0 = (int32_t)y0f;
     r.ok = true;
     return r;
+}
+
+// Steps 2-4.  Defined for every bit pattern of `depth`.
+RT_TM_FN Reprojection reproject(const TemporalConsts& k, uint32_t x, uint32_t y, float depth) {
+    return in_range(k, project(k, x, y, depth));
+}
+
+// Steps 3 and 4 of the motion variants, whose step 2 is X = motion[p].prev_point.  Defined for every bit
+// pattern of X.
+RT_TM_FN Reprojection reproject_point(const TemporalConsts& k, const float* X) {
+    return in_range(k, project_point(k, X));
 }
 
 // Tap (i, j) of a reprojection that passed: true and its record index when it lies inside the W x H

@@ -61,6 +61,7 @@ int temporal_plan(const TemporalIn& in, TemporalPlan* out) {
     if (in.hist_given != in.hist_features_given) return RT_INVALID_MEM_OBJECT;
     if (!in.cur_ok || !in.cur_features_ok || !in.out_ok) return RT_INVALID_MEM_OBJECT;
     if (in.hist_given && (!in.hist_ok || !in.hist_features_ok)) return RT_INVALID_MEM_OBJECT;
+    if (in.motion_given && !in.motion_ok) return RT_INVALID_MEM_OBJECT;
     if (in.out_is_input) return RT_INVALID_MEM_OBJECT;
 
     const uint64_t pixels = in.width * in.height;
@@ -70,9 +71,11 @@ int temporal_plan(const TemporalIn& in, TemporalPlan* out) {
     if (in.hist_given &&
         (pixels > in.hist_bytes / kTemporalPixelBytes || pixels > in.hist_features_bytes / kTemporalFeatureBytes))
         return RT_INVALID_BUFFER_SIZE;
+    if (in.motion_given && pixels > in.motion_bytes / kTemporalMotionBytes) return RT_INVALID_BUFFER_SIZE;
 
     p.width = (uint32_t)in.width, p.height = (uint32_t)in.height;
     p.has_history = in.hist_given;
+    p.has_motion = in.motion_given;
     p.k = view_consts(in.width, in.height, in.cur, in.prev);
     p.cur_frames = in.cur_frames, p.history_frames = in.history_frames, p.max_history = in.max_history;
     p.depth_tolerance = in.depth_tolerance, p.normal_threshold = in.normal_threshold;

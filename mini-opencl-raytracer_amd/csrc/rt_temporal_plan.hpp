@@ -17,7 +17,7 @@ namespace rtp {
 constexpr uint64_t kTemporalMaxPixels = 1ull << 31;
 constexpr uint32_t kTemporalTileW = 64, kTemporalTileH = 4;
 constexpr uint32_t kTemporalThreads = kTemporalTileW * kTemporalTileH;
-constexpr uint32_t kTemporalPixelBytes = 16, kTemporalFeatureBytes = 32;
+constexpr uint32_t kTemporalPixelBytes = 16, kTemporalFeatureBytes = 32, kTemporalMotionBytes = 32;
 constexpr float kTemporalMaxFrames = 0x1p20f;   // of cur_frames, history_frames and max_history
 constexpr float kTemporalMinWeight = 0x1p-6f;   // step 6: the least sum of counted bilinear weights
 
@@ -35,11 +35,15 @@ struct TemporalIn {
     bool hist_ok, hist_features_ok;                   // (looked at only when given)
     bool out_is_input;                                // `out` is one of the four inputs
     uint64_t cur_bytes, cur_features_bytes, hist_bytes, hist_features_bytes, out_bytes;
+    // rtEnqueueTemporalAccumulateMotion (all false / zero: rtEnqueueTemporalAccumulate itself)
+    bool motion_given, motion_ok;                     // the handle is not NULL; a buffer of this context
+    uint64_t motion_bytes;
 };
 
 struct TemporalPlan {
     uint32_t width, height;
     bool has_history;
+    bool has_motion;                // step 2 is motion[p].prev_point (rt_pixel_motion records)
     rtt::TemporalConsts k;
     float cur_frames, history_frames, max_history, depth_tolerance, normal_threshold;
     uint32_t tiles_x, tiles_y;
@@ -60,7 +64,8 @@ void temporal_tiles(uint64_t width, uint64_t height, uint32_t* tiles_x, uint32_t
 // not finite, in (0, 1) or > 2^20; max_history not finite, < cur_frames or > 2^20; depth_tolerance not
 // finite or outside [0, 1]; normal_threshold not finite or outside [-1, 1]), RT_INVALID_MEM_OBJECT
 // (exactly one of hist and hist_features given; a required or given buffer that is not this context's;
-// `out` one of the inputs), RT_INVALID_BUFFER_SIZE (an image below 16 B per pixel, features below 32 B).
+// `out` one of the inputs, `motion` among them), RT_INVALID_BUFFER_SIZE (an image below 16 B per pixel,
+// features or motion records below 32 B).
 int temporal_plan(const TemporalIn& in, TemporalPlan* out);
 
 }  // namespace rtp
