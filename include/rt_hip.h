@@ -256,6 +256,30 @@ typedef struct rt_node_collapse_info {
 } rt_node_collapse_info;
 int rtKernelGetNodeCollapse(rt_kernel k, rt_node_collapse_info* out);
 
+/* The octant cull (the same walks as the node collapse).  RayTriangle rejects det < 1e-8, and for a
+ * triangle in an axis plane the sign of det is the sign of one direction component: no ray of four of
+ * the eight octants can hit it.  A host certificate (csrc/rt_octant_cull.cpp) decides per triangle and
+ * octant whether every evaluation of det, under every math mode, is below 1e-8 or NaN; the packed scene
+ * keeps a third set of records, built from the collapsed one, in which no link of an octant leads to a
+ * leaf -- or a whole subtree -- whose triangles are all certified for it.  Launches walk it: the same
+ * accepted hits, the same results, without the box tests and triangle tests that could accept nothing.
+ * The certificate refuses what it cannot prove through fp32 rounding: triangles whose det has two
+ * products of one direction component that cancel only in exact arithmetic (the side faces of a box
+ * rotated about an axis), triangles so thin that the component's margin is under 2^-18, and vertices
+ * that are not finite or lie beyond 2^20.  Launches with stats on walk the plain records, and so does
+ * every launch after rtRefitBVH until the next full preparation, since moved vertices are not certified.
+ * pruned_links: link words the third set changes against the collapsed one; contracted_links: words
+ * changed by contracting interior nodes with one live child (always 0: not built); scene_certified: the
+ * set may be walked as of the last preparation (0 after rtRefitBVH, and in builds with RT_OCTANT_CULL=0);
+ * launch_pruned: whether the kernel's last launch -- render, ray query or path trace -- walked it
+ * (rtKernelGetNodeCollapse's launch_collapsed is 1 as well then: the set contains the collapse).
+ * Flushes coalesced frames; does not wait for the device. */
+typedef struct rt_octant_cull_info {
+    uint32_t pruned_links, contracted_links;
+    int32_t scene_certified, launch_pruned;
+} rt_octant_cull_info;
+int rtKernelGetOctantCull(rt_kernel k, rt_octant_cull_info* out);
+
 /* ---- batched ray queries over caller rays ------------------------------------------------
  * The scene is the one bound to `k` (BUFFER_SCENE, BUFFER_NODE), packed and validated exactly as
  * a render launch does (rtValidateBVH first: RT_INVALID_MEM_OBJECT on a bad tree).  A query runs

@@ -139,6 +139,12 @@ class NodeCollapseInfo(ctypes.Structure):
                 ("launch_collapsed", ctypes.c_int32)]
 
 
+class OctantCullInfo(ctypes.Structure):
+    """rt_octant_cull_info (rt_hip.h)."""
+    _fields_ = [("pruned_links", ctypes.c_uint32), ("contracted_links", ctypes.c_uint32),
+                ("scene_certified", ctypes.c_int32), ("launch_pruned", ctypes.c_int32)]
+
+
 class TRACE_PARAMS(ctypes.Structure):
     """rt_trace_params (rt_hip.h): rtEnqueueTracePaths' seed base (used without a seed buffer) and the
     encoding of the radiance it writes."""
@@ -287,6 +293,7 @@ _HIP_PROTOS = {
     "rtKernelResetStats": (ctypes.c_int, [_vp]),
     "rtKernelGetPathKill": (ctypes.c_int, [_vp, ctypes.POINTER(PathKillInfo)]),
     "rtKernelGetNodeCollapse": (ctypes.c_int, [_vp, ctypes.POINTER(NodeCollapseInfo)]),
+    "rtKernelGetOctantCull": (ctypes.c_int, [_vp, ctypes.POINTER(OctantCullInfo)]),
     "rtKernelGetSceneInLDS": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "rtKernelForceGlobalScene": (ctypes.c_int, [_vp, ctypes.c_int]),
     "rtBuildBVH": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint, _vp, ctypes.POINTER(ctypes.c_size_t)]),

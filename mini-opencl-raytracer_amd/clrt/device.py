@@ -471,6 +471,15 @@ class CLKernel:
         return {"collapsed_links": int(s.collapsed_links), "scene_collapsible": bool(s.scene_collapsible),
                 "launch_collapsed": bool(s.launch_collapsed)}
 
+    def octant_cull(self) -> dict:
+        """rtKernelGetOctantCull: the link words the scene's pruned record set changes (culled subtrees;
+        contracted single-child nodes, always 0), whether the set may be walked (not after a device
+        refit), and whether the last launch walked it."""
+        s = N.OctantCullInfo()
+        check(self._lib.rtKernelGetOctantCull(self.handle, ctypes.byref(s)), "octant cull")
+        return {"pruned_links": int(s.pruned_links), "contracted_links": int(s.contracted_links),
+                "scene_certified": bool(s.scene_certified), "launch_pruned": bool(s.launch_pruned)}
+
     def scene_prepares(self) -> tuple:
         """rtDiagScenePrepares: (full host-side scene preparations, device refits) since creation."""
         full, refits = ctypes.c_uint64(), ctypes.c_uint64()

@@ -71,6 +71,11 @@ constexpr size_t kHitPad = RT_TIMELINE ? 192 : 0;
 #ifndef RT_NODE_COLLAPSE_STATS
 #define RT_NODE_COLLAPSE_STATS 0
 #endif
+// ... and (-DRT_OCTANT_CULL_STATS=1) the pruned links: node_visits and tri_tests against the default
+// build's are the exact lane visits and tests the octant cull removes
+#ifndef RT_OCTANT_CULL_STATS
+#define RT_OCTANT_CULL_STATS 0
+#endif
 
 }  // namespace
 
@@ -94,6 +99,7 @@ struct rt_kernel_s {
     bool last_lds = false;
     bool last_kill = false;            // the last render launch carried the path kill (rtKernelGetPathKill)
     bool last_collapsed = false;       // the last launch walked the collapsed links (rtKernelGetNodeCollapse)
+    bool last_pruned = false;          // ... the pruned links, which contain them (rtKernelGetOctantCull)
     // the device resources, each with its own invariant (rt_device_scene.hpp, rt_kernel_state.hpp,
     // rt_internal.hpp, rt_kernels.hpp)
     rti::DeviceScene scene;  // the derived packed scene
@@ -523,11 +529,17 @@ static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, const LaunchArgs& la
 // The octant records a launch of walk `w` reads: the collapsed link set (rt_scene_pack.cpp,
 // collapse_oct_links) unless the launch reports traversal counters -- a stats launch's visits stay the
 // reference's -- or the scene's boxes were moved by a device refit since they were packed.  The kernels
-// are the same either way: only this pointer differs.  Remembers the choice for rtKernelGetNodeCollapse.
+// are the same either way: only this pointer differs.  Where the octant-cull certificate is known too
+// (rt_octant_cull.cpp) the launch takes the pruned set (prune_oct_links), which is the collapsed set less
+// the links into subtrees no ray of the octant can hit, under the same two conditions.  Remembers the
+// choice for rtKernelGetNodeCollapse and rtKernelGetOctantCull.
 static const float4* oct_records(rt_kernel k, rtk::Walk w, bool regrouped) {
     const rti::DeviceScene& sc = k->scene;
-    const bool collapsed = sc.collapse_ok() && (!k->stats || RT_NODE_COLLAPSE_STATS);
+    const bool pruned = sc.cull_ok() && (!k->stats || RT_OCTANT_CULL_STATS);
+    const bool collapsed = sc.collapse_ok() && (!k->stats || RT_NODE_COLLAPSE_STATS || pruned);
     k->last_collapsed = collapsed && w != rtk::Walk::GlobalNodes;
+    k->last_pruned = pruned && w != rtk::Walk::GlobalNodes;
+    if (pruned) return regrouped ? sc.goct_pruned() : sc.oct_nodes_pruned();
     if (collapsed) return regrouped ? sc.goct_collapsed() : sc.oct_nodes_collapsed();
     return regrouped ? sc.goct() : sc.oct_nodes();
 }
@@ -1847,6 +1859,16 @@ int rtKernelGetNodeCollapse(rt_kernel k, rt_node_collapse_info* out) {
     out->collapsed_links = k->scene.collapsed_links();
     out->scene_collapsible = k->scene.collapse_ok() ? 1 : 0;
     out->launch_collapsed = k->last_collapsed ? 1 : 0;
+    return RT_SUCCESS;
+}
+
+int rtKernelGetOctantCull(rt_kernel k, rt_octant_cull_info* out) {
+    if (!k || !out) return RT_INVALID_VALUE;
+    flush_kernel(k);
+    out->pruned_links = k->scene.pruned_links();
+    out->contracted_links = 0;  // single-child interior nodes are not contracted (rt_scene_pack.cpp)
+    out->scene_certified = k->scene.cull_ok() ? 1 : 0;
+    out->launch_pruned = k->last_pruned ? 1 : 0;
     return RT_SUCCESS;
 }
 

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "rt_kernels.hpp"
+#include "rt_octant_cull.hpp"
 #include "rt_path_kill.hpp"
 #include "rt_refit.hpp"
 #include "rt_scene_pack.hpp"
@@ -47,7 +48,8 @@ hipError_t upload(void* dst, const std::vector<uint32_t>& src, hipStream_t st) {
 
 }  // namespace
 
-int DeviceScene::allocate(uint32_t nn, uint32_t nt, uint32_t nmat, size_t goct_words, bool collapsed) {
+int DeviceScene::allocate(uint32_t nn, uint32_t nt, uint32_t nmat, size_t goct_words, bool collapsed,
+                          bool pruned) {
     int rc = ensure_dev(g_nodes_, g_nodes_cap_, (size_t)nn * 4);
     if (!rc) rc = ensure_dev(refit_links_, refit_links_cap_, (size_t)nn * 2);
     if (!rc) rc = ensure_dev(refit_arrivals_, refit_arrivals_cap_, (size_t)nn);
@@ -55,6 +57,8 @@ int DeviceScene::allocate(uint32_t nn, uint32_t nt, uint32_t nmat, size_t goct_w
     if (!rc) rc = ensure_dev(goct_nodes_, goct_nodes_cap_, goct_words / 4);
     if (!rc && collapsed) rc = ensure_dev(oct_collapsed_, oct_collapsed_cap_, (size_t)rtp::oct_records(nn));
     if (!rc && collapsed) rc = ensure_dev(goct_collapsed_, goct_collapsed_cap_, goct_words / 4);
+    if (!rc && pruned) rc = ensure_dev(oct_pruned_, oct_pruned_cap_, (size_t)rtp::oct_records(nn));
+    if (!rc && pruned) rc = ensure_dev(goct_pruned_, goct_pruned_cap_, goct_words / 4);
     if (!rc) rc = ensure_dev(packed_tris_, packed_tris_cap_, (size_t)nt * 3);
     if (!rc) rc = ensure_dev(shade_tris_, shade_tris_cap_, (size_t)nt * 3);
     // two material tables: IEEE divisions (pinned, devicelib), then the shipped policy's
@@ -78,9 +82,17 @@ int DeviceScene::prepare(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     rtp::HostPack p;
     rc = rtp::pack_scene_host(in, top_limit, &p);
     if (rc) return rc;
+    // the octant-cull certificate per triangle, on the vertices the device packs its edges from, and the
+    // pruned link set it allows
+    if (RT_OCTANT_CULL && p.oct_ok) {
+        std::vector<uint8_t> tri_octants(p.n_tris);
+        rtp::octant_cull_masks(reinterpret_cast<const rt_cl_triangle*>(in.tris), p.n_tris, tri_octants.data());
+        rtp::pack_pruned_links(tri_octants.data(), &p);
+    }
     // the device half: from here on the records are no longer those of the scene remembered
     invalidate();
-    rc = allocate(p.n_nodes, p.n_tris, p.n_mats, p.goct_nodes.size(), p.collapsed_links != 0);
+    rc = allocate(p.n_nodes, p.n_tris, p.n_mats, p.goct_nodes.size(), p.collapsed_links != 0,
+                  p.pruned_links != 0);
     if (rc) return rc;
     hipStream_t st = qs(ctx);
     hipError_t e = upload(g_nodes_, p.global_nodes, st);
@@ -89,6 +101,8 @@ int DeviceScene::prepare(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     if (e == hipSuccess && !p.goct_nodes.empty()) e = upload(goct_nodes_, p.goct_nodes, st);
     if (e == hipSuccess && p.collapsed_links) e = upload(oct_collapsed_, p.oct_nodes_collapsed, st);
     if (e == hipSuccess && !p.goct_nodes_collapsed.empty()) e = upload(goct_collapsed_, p.goct_nodes_collapsed, st);
+    if (e == hipSuccess && p.pruned_links) e = upload(oct_pruned_, p.oct_nodes_pruned, st);
+    if (e == hipSuccess && !p.goct_nodes_pruned.empty()) e = upload(goct_pruned_, p.goct_nodes_pruned, st);
     if (e == hipSuccess)
         e = rtk::launch_pack(static_cast<const rt_cl_triangle*>(tm->dptr), p.n_tris, packed_tris_, shade_tris_,
                              mm ? static_cast<const rt_cl_material*>(mm->dptr) : nullptr, p.n_mats, shade_mats_, st);
@@ -99,6 +113,7 @@ int DeviceScene::prepare(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     n_nodes_ = p.n_nodes, n_tris_ = p.n_tris, n_mats_ = p.n_mats, n_top_ = p.n_top;
     oct_ok_ = p.oct_ok, goct_b_ = p.goct_b;
     collapsed_links_ = p.collapsed_links, collapse_known_ = RT_NODE_COLLAPSE != 0;
+    pruned_links_ = p.pruned_links, cull_known_ = RT_OCTANT_CULL != 0 && p.oct_ok;
     root_known_ = p.n_nodes > 0 && in.nodes_size >= sizeof(rt_cl_bvh_node);
     if (root_known_) {
         rt_cl_bvh_node root;
@@ -150,6 +165,7 @@ int DeviceScene::refit(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     a.g_nodes = g_nodes_;
     root_known_ = false;  // the refit moves the root's bounds on the device
     collapse_known_ = false;  // ... and every box, in the plain records only: equal boxes may now differ
+    cull_known_ = false;  // ... and the triangles the octant-cull certificate was evaluated on
     kill_known_ = false;  // ... and reads vertices and normals the host has not seen
     hipStream_t st = qs(ctx);
     hipError_t e = rtr::launch_refit(a, st);
@@ -168,7 +184,8 @@ int DeviceScene::refit(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
 
 void DeviceScene::release() {
     for (void* p : {(void*)packed_tris_, (void*)shade_tris_, (void*)shade_mats_, (void*)oct_nodes_, (void*)goct_nodes_,
-                    (void*)oct_collapsed_, (void*)goct_collapsed_, (void*)g_nodes_, (void*)refit_links_,
+                    (void*)oct_collapsed_, (void*)goct_collapsed_, (void*)oct_pruned_, (void*)goct_pruned_,
+                    (void*)g_nodes_, (void*)refit_links_,
                     (void*)refit_arrivals_})
         if (p) (void)hipFree(p);
     *this = DeviceScene();

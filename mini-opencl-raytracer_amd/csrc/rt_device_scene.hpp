@@ -55,6 +55,17 @@ public:
     uint32_t collapsed_links() const { return collapsed_links_; }  // link words the set changes
     const float4* oct_nodes_collapsed() const { return collapsed_links_ ? oct_collapsed_ : oct_nodes_; }
     const float4* goct_collapsed() const { return collapsed_links_ && goct_b_ ? goct_collapsed_ : goct(); }
+    // The pruned link set (rtp::prune_oct_links over the collapsed set): per octant, no link leads to a
+    // subtree whose triangles every ray of the octant rejects (rt_octant_cull.hpp).  cull_ok(): the set
+    // may be walked -- triangles and boxes are as the host saw them at the last full preparation.  False
+    // after a device refit (rtRefitBVH, rtEnqueueUpdateVertices), which moves vertices without the host
+    // looking, until the next full preparation; false throughout in a build with RT_OCTANT_CULL=0.  A
+    // launch that reports traversal counters never walks it.  The two accessors return the collapsed
+    // accessors' records where the pruning changes no link word.
+    bool cull_ok() const { return cull_known_; }
+    uint32_t pruned_links() const { return pruned_links_; }  // link words the pruning changes
+    const float4* oct_nodes_pruned() const { return pruned_links_ ? oct_pruned_ : oct_nodes_collapsed(); }
+    const float4* goct_pruned() const { return pruned_links_ && goct_b_ ? goct_pruned_ : goct_collapsed(); }
     // The root node's bounds (nodes[0]: min xyz, max xyz) as the host last saw them: read at every full
     // preparation, so a launch after a vertex or node write sees the new ones.  Null after a device
     // refit, which moves them without the host looking: such launches do without the view cull.
@@ -81,7 +92,7 @@ private:
         return for_tris_ == tris && for_nodes_ == nodes && tris_struct_ == tris->structural &&
                nodes_struct_ == nodes->structural;
     }
-    int allocate(uint32_t n_nodes, uint32_t n_tris, uint32_t n_mats, size_t goct_words, bool collapsed);
+    int allocate(uint32_t n_nodes, uint32_t n_tris, uint32_t n_mats, size_t goct_words, bool collapsed, bool pruned);
 
     // provenance: the buffers packed from, their generations then, their structural generations at
     // the last full preparation
@@ -94,6 +105,8 @@ private:
     float root_bounds_[6] = {};
     bool collapse_known_ = false;
     uint32_t collapsed_links_ = 0;
+    bool cull_known_ = false;
+    uint32_t pruned_links_ = 0;
     bool kill_known_ = false;
     bool kill_ok_[2] = {false, false};  // [0] the IEEE material table, [1] the shipped policy's
     uint64_t full_prepares_ = 0, refits_ = 0;
@@ -105,6 +118,9 @@ private:
     // the collapsed copies of the two octant layouts (allocated for scenes whose set changes a link)
     float4 *oct_collapsed_ = nullptr, *goct_collapsed_ = nullptr;
     size_t oct_collapsed_cap_ = 0, goct_collapsed_cap_ = 0;
+    // ... and the pruned copies (for scenes whose pruning changes a link)
+    float4 *oct_pruned_ = nullptr, *goct_pruned_ = nullptr;
+    size_t oct_pruned_cap_ = 0, goct_pruned_cap_ = 0;
     // device refit: node -> parent, then node -> g_nodes record (n_nodes words each), uploaded by the
     // full preparation; the climb's arrival counters
     uint32_t *refit_links_ = nullptr, *refit_arrivals_ = nullptr;

@@ -203,6 +203,75 @@ uint32_t collapse_oct_links(const std::vector<uint32_t>& oct, uint32_t n, std::v
     return changed;
 }
 
+// The pruned link set: a copy of `base` -- the collapsed set, or the plain one where the collapse changes
+// nothing -- in which, per octant, no link leads to a subtree whose triangles every ray of that octant
+// rejects; returns the number of words it changes.  `oct` is the plain set of the same scene (n nodes,
+// every leaf inline), which still shows the tree: node i's near child under o is its plain hit_next c,
+// its far child is c's miss_next.  tri_octants[t] bit o: triangle t is certified for octant o
+// (rt_octant_cull.hpp: every evaluation of its test on a ray of octant o rejects or is NaN).
+//   * A leaf is culled under o when every triangle of it is certified for o; an interior node when both
+//     children are.  (Children have larger indices: one backward sweep.)
+//   * Every hit_next or miss_next word of octant o that targets a culled node x is replaced by x's own
+//     miss_next, repeated while the target is culled.  miss_next words strictly advance in the octant's
+//     depth-first order and END is never culled, so the chain ends.
+// Why a walk over these links computes what the walk over `base` computes.  A walk that arrives at a
+// culled leaf x either fails x's box test and goes to x's miss_next, or passes it, tests x's triangles --
+// each test accepts nothing, by the certificate, so {t, prim, u, v} are what they were -- and goes to the
+// visited record's miss_next: the same word.  A walk that arrives at a culled interior node x leaves
+// through x's miss_next if the box fails; if it passes, every leaf below x is culled, t does not change,
+// and every way through the subtree ends at the skip of x's subtree, which is x's miss_next again.  So the
+// state after x is the state before x with the position moved to x's miss_next, whatever the ray does:
+// going there at once leaves out x's box test and every triangle test below x, all of which accept
+// nothing, and nothing else.  That holds for closest-hit and any-hit walks alike (an any-hit walk ends at
+// an accepted test; none is removed).  By induction over the replaced words the triangle tests that
+// remain are the base walk's in its order, and the final {t, prim, u, v} are its bits.
+//   * The collapsed links in `base` stay valid: a collapsed hit_next i -> c stands for box tests known to
+//     pass; if c is culled the argument above applies to the arrival at c.
+//   * If the root is culled under o, octant o's links stay as they are (a walk must start somewhere; such
+//     a scene shows that octant nothing and is not worth a special entry).
+//   * Planes, leaf codes and END are base's, word for word; a partly culled leaf keeps its whole code.
+// The certificate is a property of the triangles as the host saw them, and the collapse of the boxes: after
+// a device refit or a vertex update only the plain set may be walked until the next full preparation.
+uint32_t prune_oct_links(const std::vector<uint32_t>& oct, const std::vector<uint32_t>& base, uint32_t n,
+                         const uint8_t* tri_octants, std::vector<uint32_t>& out) {
+    const uint32_t stride = oct_stride(n), bofs = oct_b(n);
+    out = base;
+    uint32_t changed = 0;
+    std::vector<uint8_t> culled(n);
+    for (uint32_t o = 0; o < 8; ++o) {
+        const size_t plane = ((size_t)bofs + (size_t)o * stride) * 4;
+        const uint32_t* pb = &oct[plane];
+        for (uint32_t i = n; i-- > 0;) {
+            const uint32_t hn = pb[(size_t)i * 4 + 2];
+            if (hn >= kLeafMin) {
+                const uint32_t first = hn & (kLeafMin - 1), count = hn >> 24;
+                bool all = true;
+                for (uint32_t t = first; t < first + count; ++t) all = all && ((tri_octants[t] >> o) & 1u);
+                culled[i] = all;
+            } else {
+                const uint32_t farc = pb[(size_t)hn * 4 + 3];  // the near child's skip: the far child
+                culled[i] = culled[hn] && farc < n && culled[farc];
+            }
+        }
+        if (culled[0]) continue;
+        auto live = [&](uint32_t x) {
+            while (x < n && culled[x]) x = pb[(size_t)x * 4 + 3];
+            return x;
+        };
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t k = 2; k < 4; ++k) {
+                uint32_t& w = out[plane + (size_t)i * 4 + k];
+                if (w >= kLeafMin) continue;  // a leaf code
+                const uint32_t to = live(w);
+                if (to != w) {
+                    w = to;
+                    ++changed;
+                }
+            }
+    }
+    return changed;
+}
+
 // The same octant records regrouped for the walk over HBM/L2 (RT_GOCT_GROUP = G > 0): blocks of G
 // consecutive nodes, each block laid out octant-major ([block][octant][G nodes], A planes then B
 // planes), so G = 1 puts the eight octants' records of a node in one 128-B line (lanes of different
@@ -344,6 +413,24 @@ int pack_scene_host(const SceneBytes& in, uint32_t top_limit, HostPack* out) {
         }
     }
     return RT_SUCCESS;
+}
+
+// The pruned set of both layouts over the collapsed one (the plain one where there is none), kept only
+// where it differs from it.
+void pack_pruned_links(const uint8_t* tri_octants, HostPack* pack) {
+    HostPack& p = *pack;
+    p.pruned_links = 0;
+    p.oct_nodes_pruned.clear();
+    p.goct_nodes_pruned.clear();
+    if (!RT_OCTANT_CULL || !p.oct_ok || !tri_octants) return;
+    const std::vector<uint32_t>& base = p.collapsed_links ? p.oct_nodes_collapsed : p.oct_nodes;
+    p.pruned_links = prune_oct_links(p.oct_nodes, base, p.n_nodes, tri_octants, p.oct_nodes_pruned);
+    if (p.pruned_links == 0) {
+        p.oct_nodes_pruned.clear();
+    } else if (!p.goct_nodes.empty()) {
+        uint32_t b = 0;
+        build_oct_nodes_grouped(p.oct_nodes_pruned, p.n_nodes, RT_GOCT_GROUP, p.goct_nodes_pruned, &b);
+    }
 }
 
 }  // namespace rtp

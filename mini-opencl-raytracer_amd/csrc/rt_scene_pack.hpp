@@ -30,6 +30,9 @@ inline uint32_t oct_records(uint32_t n) { return oct_b(n) + 8u * oct_stride(n); 
 #ifndef RT_NODE_COLLAPSE
 #define RT_NODE_COLLAPSE 1  // launches without counters walk the collapsed links (collapse_oct_links)
 #endif
+#ifndef RT_OCTANT_CULL
+#define RT_OCTANT_CULL 1  // ... and the pruned links (prune_oct_links), which contain the collapse
+#endif
 #ifndef RT_GOCT_GROUP
 #define RT_GOCT_GROUP 1  // node-major: bunny proxy fused 1.405 -> 1.393 ms/frame (profiles/r03/goct_layout_ab.txt)
 #endif
@@ -44,6 +47,8 @@ bool build_oct_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uin
 void build_oct_nodes_grouped(const std::vector<uint32_t>& oct, uint32_t n, uint32_t G, std::vector<uint32_t>& out,
                              uint32_t* b_ofs);
 uint32_t collapse_oct_links(const std::vector<uint32_t>& oct, uint32_t n, std::vector<uint32_t>& out);
+uint32_t prune_oct_links(const std::vector<uint32_t>& oct, const std::vector<uint32_t>& base, uint32_t n,
+                         const uint8_t* tri_octants, std::vector<uint32_t>& out);
 void build_global_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
                         uint32_t top, std::vector<uint32_t>& out, uint32_t* n_top,
                         std::vector<uint32_t>* slot_of = nullptr);
@@ -73,10 +78,19 @@ struct HostPack {
     // word (collapsed_links 0) -- the plain records then serve as both sets
     uint32_t collapsed_links = 0;
     std::vector<uint32_t> oct_nodes_collapsed, goct_nodes_collapsed;
+    // the pruned link set (prune_oct_links over the collapsed set, so it contains the collapse) of both
+    // layouts, filled by pack_pruned_links: empty when the pruning changes no link word (pruned_links 0)
+    // -- the collapsed records then serve
+    uint32_t pruned_links = 0;
+    std::vector<uint32_t> oct_nodes_pruned, goct_nodes_pruned;
 };
 
 // Validate the scene and pack every record (top_limit: build_global_nodes' `top`).  On an error
 // `out` holds nothing to be used.
 int pack_scene_host(const SceneBytes& in, uint32_t top_limit, HostPack* out);
+// The third record set of a scene pack_scene_host accepted: tri_octants[t] (n_tris bytes) holds for
+// triangle t the octants whose every ray fails its test (rt_octant_cull.hpp: the caller evaluates the
+// certificate, this file stays free of it).  Nothing in a build with RT_OCTANT_CULL=0.
+void pack_pruned_links(const uint8_t* tri_octants, HostPack* pack);
 
 }  // namespace rtp

@@ -55,4 +55,11 @@ for name in scheds:
         nc = r.k.node_collapse()
         print(f"  node collapse: {nc['collapsed_links']} link words, scene collapsible: {nc['scene_collapsible']}, "
               f"this launch walked the collapsed links: {nc['launch_collapsed']}")
+        # the octant cull (rtKernelGetOctantCull): likewise, except in a -DRT_OCTANT_CULL_STATS=1 build, whose
+        # visits and tests against the default build's are the ones the pruned links remove
+        oc = r.k.octant_cull()
+        print(f"  octant cull: {oc['pruned_links']} pruned + {oc['contracted_links']} contracted link words, "
+              f"scene certified: {oc['scene_certified']}, this launch walked the pruned links: {oc['launch_pruned']}")
+        print(f"  decisions: node {u['node_steps']} tri {u['tri_steps']} shade {u['shade_rounds']} "
+              f"lanes node {u['node_lanes']} tri {u['tri_lanes']}")
         r.close()
