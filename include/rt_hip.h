@@ -1305,6 +1305,18 @@ int rtBandPackPlan(unsigned width, unsigned height, unsigned period, unsigned ph
 #define RT_PINNED_OP_COS 6
 int rtDiagPinnedMath(int device_index, int op, const float* a, const float* b, float* out, size_t n);
 
+/* The gamma code's pow for literal exponents and its frame-1 shortcut, checked on the GPU over the operand
+ * bit patterns first .. first + count - 1 (count <= 2^32 - first) under one math mode (for tests).
+ *   RT_GAMMA_CHECK_POW:   the step kernels' pow for the literal `exponent` (0: 2.2f, 1: 0.454545f,
+ *                         2: 0.45454545f) against the mode's plain pow(x, literal), bit for bit;
+ *   RT_GAMMA_CHECK_LEMMA: bits(pow(x, 2.2f) * 0.0f) against +0 (`exponent` is not read).
+ * *mismatches = patterns that differ, *first_bad = the smallest of them (UINT32_MAX: none),
+ * *first_bits = the compared bits (the new pow's / the product's) at `first`.  Blocking. */
+#define RT_GAMMA_CHECK_POW 0
+#define RT_GAMMA_CHECK_LEMMA 1
+int rtDiagGammaPow(int device_index, int math, int check, int exponent, uint32_t first, uint64_t count,
+                   uint64_t* mismatches, uint32_t* first_bad, uint32_t* first_bits);
+
 /* Library identification (for smoke checks): returns a static string. */
 const char* rtGetBuildInfo(void);
 

@@ -330,6 +330,8 @@ _HIP_PROTOS = {
                                       ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t)]),
     "rtGetBuildInfo": (ctypes.c_char_p, []),
     "rtDiagPinnedMath": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t]),
+    "rtDiagGammaPow": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
+                                      ctypes.c_uint64, _vp, _vp, _vp]),
 }
 HIP_EXPORTS = tuple(_HIP_PROTOS)
 
@@ -400,3 +402,20 @@ def pinned_math(op: str, a, b=None, device: int = 0) -> np.ndarray:
                                      None if bb is None else bb.ctypes.data, out.ctypes.data, a.size),
           f"pinned math {op}")
     return out
+
+
+GAMMA_EXPONENTS = {"2.2f": 0, "0.454545f": 1, "0.45454545f": 2}
+
+
+def gamma_pow_check(math: int, kind: str, exponent: str = "2.2f", first: int = 0, count: int = 1 << 32,
+                    device: int = 0):
+    """rtDiagGammaPow: sweep the operand bit patterns first .. first + count - 1 on the GPU (tests).
+
+    kind "pow": the step kernels' pow for the literal `exponent` against the mode's plain pow;
+    kind "lemma": bits(pow(x, 2.2f) * 0.0f) against +0.
+    Returns (mismatches, first mismatching pattern or None, the compared bits at `first`)."""
+    bad, first_bad, bits = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
+    check(hip_lib().rtDiagGammaPow(int(device), int(math), {"pow": 0, "lemma": 1}[kind], GAMMA_EXPONENTS[exponent],
+                                      int(first), int(count), ctypes.byref(bad), ctypes.byref(first_bad),
+                                      ctypes.byref(bits)), "gamma pow check")
+    return bad.value, (first_bad.value if bad.value else None), bits.value

@@ -1997,6 +1997,31 @@ int rtDiagPinnedMath(int device_index, int op, const float* a, const float* b, f
     return map_hip(e);
 }
 
+int rtDiagGammaPow(int device_index, int math, int check, int exponent, uint32_t first, uint64_t count,
+                   uint64_t* mismatches, uint32_t* first_bad, uint32_t* first_bits) {
+    if (math < RT_MATH_PINNED || math > RT_MATH_SHIPPED || check < RT_GAMMA_CHECK_POW || check > RT_GAMMA_CHECK_LEMMA ||
+        exponent < 0 || exponent > 2 || !mismatches || !first_bad || !first_bits)
+        return RT_INVALID_VALUE;
+    if (count > ((uint64_t)1 << 32) - first) return RT_INVALID_VALUE;  // the sweep stays inside 2^32 patterns
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return RT_DEVICE_NOT_FOUND;
+    if (device_index < 0 || device_index >= ndev) return RT_INVALID_DEVICE;
+    hipError_t e = hipSetDevice(device_index);
+    unsigned long long* d = nullptr;
+    unsigned long long h[3] = {0ull, 0xffffffffull, 0ull};
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d), sizeof h);
+    if (e == hipSuccess) e = hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = rtk::launch_gamma_check(rtk::GammaCheckArgs{d, count, first, (uint32_t)check, (uint32_t)exponent}, math, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
+    if (d) (void)hipFree(d);
+    if (e != hipSuccess) return map_hip(e);
+    *mismatches = h[0];
+    *first_bad = (uint32_t)h[1];
+    *first_bits = (uint32_t)h[2];
+    return RT_SUCCESS;
+}
+
 const char* rtGetBuildInfo(void) {
     return "librt_hip: KernelEntry for gfx950 (HIP), math modes pinned|devicelib|shipped, scene in LDS or HBM";
 }

@@ -107,6 +107,10 @@ template <class M>
 __global__ void accum_key(KernelArgs a, uint32_t* key) {
     accum_key_body<M>(a, key);
 }
+template <class M>
+__global__ __launch_bounds__(256) void gamma_check(GammaCheckArgs g) {
+    gamma_check_body<M>(g);
+}
 
 // the kernels of a math policy (pack_mats: the IEEE material records serve both policies of this TU)
 static const Policy& policy(int math) {
@@ -116,14 +120,14 @@ static const Policy& policy(int math) {
                                      hit_surfaces<MathDeviceLib, false>, hit_surfaces<MathDeviceLib, true>,
                                      trace_pick<MathDeviceLib>, camera_paths<MathDeviceLib>,
                                      camera_paths_for<MathDeviceLib>, sample_pick<MathDeviceLib>,
-                                     motion_pick<MathDeviceLib>};
+                                     motion_pick<MathDeviceLib>, gamma_check<MathDeviceLib>};
     static const Policy pinned = {pick_entry<MathPinned>,   wf_pick<MathPinned>,  query_pick<MathPinned>,
                                   accum_frames<MathPinned>, accum_key<MathPinned>, camera_rays<MathPinned>,
                                   pack_mats,
                                   hit_surfaces<MathPinned, false>, hit_surfaces<MathPinned, true>,
                                      trace_pick<MathPinned>, camera_paths<MathPinned>,
                                      camera_paths_for<MathPinned>, sample_pick<MathPinned>,
-                                     motion_pick<MathPinned>};
+                                     motion_pick<MathPinned>, gamma_check<MathPinned>};
     return math == MathShipped::kId ? shipped_policy() : math == MathDeviceLib::kId ? devicelib : pinned;
 }
 
@@ -251,6 +255,12 @@ __global__ void pinned_math_kernel(int op, const float* __restrict__ a, const fl
         default: r = MathPinned::cos(x); break;
     }
     out[i] = r;
+}
+
+hipError_t launch_gamma_check(const GammaCheckArgs& g, int math, hipStream_t st) {
+    // grid-stride: a fixed grid whatever the count
+    if (g.count) hipLaunchKernelGGL(policy(math).gamma_check, dim3(256u * 8u), dim3(256), 0, st, g);
+    return hipGetLastError();
 }
 
 hipError_t launch_pinned_math(int op, const float* a, const float* b, float* out, size_t n, hipStream_t st) {

@@ -200,6 +200,15 @@ hipError_t launch_kernel_entry(const KernelArgs& a, const Variant& v, unsigned g
 // accumulate the fused frames' radiances into the output (one pixel per lane)
 // (`key`: 4 words of per-kernel state for the sky shortcut, zeroed once; accum_key_body)
 hipError_t launch_accum_frames(const KernelArgs& a, int math, uint32_t* key, hipStream_t st);
+// rtDiagGammaPow (tests): gamma_check_body's sweep; `out` is 3 device words {mismatches, UINT32_MAX, 0}
+struct GammaCheckArgs {
+    unsigned long long* out;
+    unsigned long long count;  // operand bit patterns first .. first + count - 1, count <= 2^32
+    uint32_t first;
+    uint32_t check;     // 0: pow_gamma against the policy's pow; 1: the frame-1 lemma
+    uint32_t exponent;  // 0: 2.2f, 1: 0.454545f, 2: 0.45454545f (check 0)
+};
+hipError_t launch_gamma_check(const GammaCheckArgs& g, int math, hipStream_t st);
 hipError_t launch_pinned_math(int op, const float* a, const float* b, float* out, size_t n, hipStream_t st);
 hipError_t launch_pack(const rt_cl_triangle* tris, uint32_t n_tris, float4* pt, float4* ps,
                        const rt_cl_material* mats, uint32_t n_mats, float4* pm, hipStream_t st);
@@ -234,6 +243,7 @@ struct Policy {
     void (*camera_paths_for)(KernelArgs, const uint32_t*, uint32_t, uint32_t, float4*, uint32_t*);
     SampleKernelFn (*sample)(const Variant&);
     MotionKernelFn (*motion)(const Variant&);
+    void (*gamma_check)(GammaCheckArgs);
 };
 const Policy& shipped_policy();
 // the step schedule's entry points are specialised per launch kind (step_body kMode: 1 fused, 2

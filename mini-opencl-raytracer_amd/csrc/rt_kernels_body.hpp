@@ -695,15 +695,55 @@ __device__ __forceinline__ F3 gamma_out(uint32_t frameCount, F3 old, F3 rad) {
     return F3{M::pow(acc.x, 0.454545f), M::pow(acc.y, 0.454545f), M::pow(acc.z, 0.454545f)};
 }
 
-// write (frameCount 0) or gamma-accumulate one work-item's result
+// The step family's gamma code (gamma_out_step, gamma_out_serial) computes the same bits with two
+// pieces of work removed; the tile schedule above keeps the plain form and is what the tests replay.
+//  * the pows are the policy's pow_gamma (rt_math.hpp);
+//  * frame number 1 multiplies FromGamma(old) by (float)(1 - 1) = 0.0f: for every stored value in
+//    the safe set -- bits <= 0x5C000000 (+0 .. 2^57; 2^(57 * 2.2) is finite) or -0 -- pow(old, 2.2f)
+//    is finite and not negative, the product is +0 whatever it was, and the three pow are skipped
+//    with +0 in their place (the multiply-add, the division and ToGamma's pow stay as operations).
+//    The lemma is checked for each policy over the whole set (tests/test_gamma_pow_gpu.py).  The
+//    frame number is wave-uniform and the set test is one ballot over the active lanes: a wave with
+//    any other stored value (NaN, inf, negative, huge: a stale image) takes the plain path.
+__device__ __forceinline__ bool gamma_old_safe(float v) {
+    const uint32_t b = __float_as_uint(v);
+    return b <= 0x5C000000u || b == 0x80000000u;
+}
+__device__ __forceinline__ bool gamma_skip_from(uint32_t frameCount, F3 old) {
+    if (!RT_GAMMA_FAST || __builtin_amdgcn_readfirstlane(frameCount) != 1u) return false;
+    return __ballot(!(gamma_old_safe(old.x) && gamma_old_safe(old.y) && gamma_old_safe(old.z))) == 0ull;
+}
+// one component; `skip`: gamma_skip_from of the work-item's three stored components
 template <class M>
+__device__ __forceinline__ float gamma_out_step1(uint32_t frameCount, float old, float rad, bool skip) {
+    if (frameCount == 0) return M::template pow_gamma<GammaExp::kTo0>(rad);
+    const float fm1 = (float)(frameCount - 1), fc = (float)frameCount;
+    float lin = 0.0f;
+    if (!skip) lin = M::template pow_gamma<GammaExp::kFrom>(old);
+    return M::template pow_gamma<GammaExp::kTo>(M::div(madd<M>(lin, fm1, rad), fc));
+}
+template <class M>
+__device__ __forceinline__ F3 gamma_out_step(uint32_t frameCount, F3 old, F3 rad) {
+    const bool skip = gamma_skip_from(frameCount, old);
+    return F3{gamma_out_step1<M>(frameCount, old.x, rad.x, skip), gamma_out_step1<M>(frameCount, old.y, rad.y, skip),
+              gamma_out_step1<M>(frameCount, old.z, rad.z, skip)};
+}
+// a sky key: the value gamma_out_step gives a work-item whose stored value and radiance have three equal
+// components, computed for one of them (same operands, same operations)
+template <class M>
+__device__ __forceinline__ float gamma_out_key(uint32_t frameCount, float old, float rad) {
+    return gamma_out_step1<M>(frameCount, old, rad, gamma_skip_from(frameCount, f3s(old)));
+}
+
+// write (frameCount 0) or gamma-accumulate one work-item's result (kStep: the step family's form)
+template <class M, bool kStep = false>
 __device__ __forceinline__ void finish_color(const KernelArgs& a, uint32_t gid, F3 rad) {
     F3 old = f3s(0.0f);
     if (a.frameCount != 0) {
         const float4 o = a.result[gid];
         old = F3{o.x, o.y, o.z};
     }
-    const F3 out = gamma_out<M>(a.frameCount, old, rad);
+    const F3 out = kStep ? gamma_out_step<M>(a.frameCount, old, rad) : gamma_out<M>(a.frameCount, old, rad);
     a.result[gid] = make_float4(out.x, out.y, out.z, 0.0f);
 }
 
@@ -916,7 +956,7 @@ template <class M>
 __device__ __forceinline__ void finish_queued(const KernelArgs& a, const float4* fq, uint32_t n, uint32_t lane) {
     if (lane < n) {
         const float4 e = fq[lane];
-        finish_color<M>(a, __float_as_uint(e.w), F3{e.x, e.y, e.z});
+        finish_color<M, true>(a, __float_as_uint(e.w), F3{e.x, e.y, e.z});
     }
 }
 // steps of the chosen kind per scheduling decision (thresholds are re-checked after each
@@ -926,6 +966,13 @@ __device__ __forceinline__ void finish_queued(const KernelArgs& a, const float4*
 #endif
 #ifndef RT_NODE_BURST
 #define RT_NODE_BURST 7  // LDS walk (6 before work stealing; 5 / 8 slower: profiles/r03/burst_sweep.txt)
+#endif
+// the step schedule's own LDS-walk burst (the ray-query, trace and wavefront walks keep RT_NODE_BURST, not
+// re-swept): 5 since the path kill, the node collapse and the octant cull shortened the walks -- 5 / 6 / 7 on
+// the 4K Cornell headline 0.4579 / 0.4584 / 0.4631 ms/frame, six alternating runs each, every run of 5 and 6
+// faster than every run of 7 (profiles/r13/node_burst_ab.txt)
+#ifndef RT_STEP_NODE_BURST
+#define RT_STEP_NODE_BURST 5
 #endif
 // diagnostic (stats variant, scripts/timeline.py): wave start/end timeline instead of the
 // lane-wait counters
@@ -1144,7 +1191,7 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
     // the radiance of a primary miss, max(1 * 0.5*skybox + 0, 0) per component (kernel_bvh.cl:360, :383)
     const float krad = M::max(madd<M>(1.0f, 0.5f * a.skyboxIntensity, 0.0f), 0.0f);
     // per-frame launches: a finished path with radiance (K_rad, K_rad, K_rad) over a stored value
-    // of (K_old, K_old, K_old) gets gamma_out(frameCount, K_old, K_rad), computed once per wave
+    // of (K_old, K_old, K_old) gets gamma_out_key(frameCount, K_old, K_rad), computed once per wave
     // here -- the same operations on the same bits as finish_color -- instead of 6 pow in the
     // finish queue (56 % of the 16:9 Cornell view is sky).  Bit equality decides, so the key
     // chain (launch to launch, pfKeyIn -> pfKeyOut) only affects how often the shortcut applies.
@@ -1153,7 +1200,7 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
         k_old = __uint_as_float(*a.pfKeyIn);
         // three equal components; wave-uniform, kept in scalar registers
         k_out = __uint_as_float(__builtin_amdgcn_readfirstlane(
-            __float_as_uint(gamma_out<M>(a.frameCount, f3s(k_old), f3s(krad)).x)));
+            __float_as_uint(gamma_out_key<M>(a.frameCount, k_old, krad))));
         if (blockIdx.x == 0 && tid == 0) *a.pfKeyOut = __float_as_uint(k_out);
     }
     const uint32_t rowEnd = a.rowBegin + a.rowCount;
@@ -1578,7 +1625,7 @@ __device__ __forceinline__ void step_body(const KernelArgs& a) {
                     u_nlanes += n_trav;
                 }
             }
-            constexpr int kNodeBurst = kGlobalOct ? RT_ONODE_BURST : kLdsScene ? RT_NODE_BURST : RT_GNODE_BURST;
+            constexpr int kNodeBurst = kGlobalOct ? RT_ONODE_BURST : kLdsScene ? RT_STEP_NODE_BURST : RT_GNODE_BURST;
             constexpr int kTriBurst = kGlobalOct ? RT_OTRI_BURST : kLdsScene ? RT_TRI_BURST : RT_GTRI_BURST;
             if (!leaf_step) {
 #pragma unroll
@@ -1831,21 +1878,31 @@ template <class M>
 __device__ __forceinline__ F3 gamma_out_serial(uint32_t frameCount, F3 old, F3 rad) {
     if (frameCount == 0) {
         F3 o;
-        o.x = M::pow(rad.x, 0.45454545f);
+        o.x = M::template pow_gamma<GammaExp::kTo0>(rad.x);
         __builtin_amdgcn_sched_barrier(0);
-        o.y = M::pow(rad.y, 0.45454545f);
+        o.y = M::template pow_gamma<GammaExp::kTo0>(rad.y);
         __builtin_amdgcn_sched_barrier(0);
-        o.z = M::pow(rad.z, 0.45454545f);
+        o.z = M::template pow_gamma<GammaExp::kTo0>(rad.z);
         return o;
     }
     const float fm1 = (float)(frameCount - 1), fc = (float)frameCount;
     float c[3] = {old.x, old.y, old.z};
     const float r[3] = {rad.x, rad.y, rad.z};
+    // gamma_out_step's frame-1 shortcut (wave-uniform), as a path of its own: the stored values are
+    // dead on it, and one path with `lin` either +0 or a pow cost the pinned kernel a 33rd register
+    if (gamma_skip_from(frameCount, old)) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            c[i] = M::template pow_gamma<GammaExp::kTo>(M::div(madd<M>(0.0f, fm1, r[i]), fc));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        return F3{c[0], c[1], c[2]};
+    }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const float lin = M::pow(c[i], 2.2f);
+        const float lin = M::template pow_gamma<GammaExp::kFrom>(c[i]);
         __builtin_amdgcn_sched_barrier(0);
-        c[i] = M::pow(M::div(madd<M>(lin, fm1, r[i]), fc), 0.454545f);
+        c[i] = M::template pow_gamma<GammaExp::kTo>(M::div(madd<M>(lin, fm1, r[i]), fc));
         __builtin_amdgcn_sched_barrier(0);
     }
     return F3{c[0], c[1], c[2]};
@@ -1889,12 +1946,51 @@ __device__ __forceinline__ void accum_key_body(const KernelArgs& a, uint32_t* ke
     }
     const float krad = M::max(madd<M>(1.0f, 0.5f * a.skyboxIntensity, 0.0f), 0.0f);
     const float kold = key[0] == 1u ? __uint_as_float(key[3]) : 0.0f;
-    F3 v = f3s(kold);
-    for (uint32_t s = 0; s < a.nFrames; ++s) v = gamma_out<M>(a.frameCount + s, v, f3s(krad));
+    float v = kold;
+    for (uint32_t s = 0; s < a.nFrames; ++s) v = gamma_out_key<M>(a.frameCount + s, v, krad);
     key[1] = __float_as_uint(krad);
     key[2] = __float_as_uint(kold);
-    key[3] = __float_as_uint(v.x);  // three equal components: same inputs, same operations
+    key[3] = __float_as_uint(v);  // three equal components: same inputs, same operations
     key[0] = 1u;
+}
+
+// rtDiagGammaPow (tests): sweep the operand bit patterns first .. first + count - 1 (grid-stride) and
+// compare, per check,
+//   0: bits(pow_gamma<E>(x)) with bits(pow(x, literal E)), the policy's plain pow;
+//   1: bits(pow(x, 2.2f) * 0.0f) with those of +0 (gamma_skip_from's lemma).
+// out[0] += mismatches, out[1] = min(mismatching pattern), out[2] = the compared bits at `first`.
+template <class M, GammaExp E>
+__device__ __forceinline__ void gamma_check_one(uint32_t check, uint32_t b, uint32_t& got, uint32_t& want) {
+    const float x = __uint_as_float(b);
+    if (check == 0u) {
+        got = __float_as_uint(M::template pow_gamma<E>(x));
+        want = __float_as_uint(M::pow(x, gamma_exp<E>()));
+    } else {
+        got = __float_as_uint(M::pow(x, 2.2f) * 0.0f);
+        want = 0u;
+    }
+}
+template <class M>
+__device__ __forceinline__ void gamma_check_body(const GammaCheckArgs& g) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long bad = 0ull;
+    uint32_t firstBad = 0xffffffffu;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.count; i += stride) {
+        const uint32_t b = g.first + (uint32_t)i;
+        uint32_t got, want;
+        if (g.exponent == 0u) gamma_check_one<M, GammaExp::kFrom>(g.check, b, got, want);
+        else if (g.exponent == 1u) gamma_check_one<M, GammaExp::kTo>(g.check, b, got, want);
+        else gamma_check_one<M, GammaExp::kTo0>(g.check, b, got, want);
+        if (i == 0u) g.out[2] = got;
+        if (got != want) {
+            ++bad;
+            firstBad = firstBad < b ? firstBad : b;
+        }
+    }
+    if (bad != 0ull) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(g.out), bad);
+        atomicMin(reinterpret_cast<uint32_t*>(g.out + 1), firstBad);
+    }
 }
 
 // a register cap that fits one accumulation wave per SIMD beside the render grid (5 waves of

@@ -44,6 +44,7 @@ __global__ __launch_bounds__(256) RT_ACCUM_OCC void accum_frames_shipped(KernelA
 __global__ void accum_key_shipped(KernelArgs a, uint32_t* key) {
     accum_key_body<MathShipped>(a, key);
 }
+__global__ __launch_bounds__(256) void gamma_check_shipped(GammaCheckArgs g) { gamma_check_body<MathShipped>(g); }
 
 template <>
 struct StepEntry<MathShipped> {
@@ -65,7 +66,7 @@ const Policy& shipped_policy() {
                                    hit_surfaces<MathShipped, false>, hit_surfaces<MathShipped, true>,
                                    trace_pick<MathShipped>, camera_paths<MathShipped>,
                                    camera_paths_for<MathShipped>, sample_pick<MathShipped>,
-                                   motion_pick<MathShipped>};
+                                   motion_pick<MathShipped>, gamma_check_shipped};
     return shipped;
 }
 

@@ -60,6 +60,20 @@ __device__ __forceinline__ F3 operator-(F3 a) { return F3{-a.x, -a.y, -a.z}; }
 #ifndef RT_PINNED_DIAG_TRIG
 #define RT_PINNED_DIAG_TRIG 0
 #endif
+// ---------------------------------------------------------------------------------------
+// The three literal exponents of the gamma code (kernel_bvh.cl:449-455): FromGamma's 2.2f, ToGamma's
+// 0.454545f and frame 0's 0.45454545f.  Each policy has pow_gamma<E>(x): for every one of the 2^32
+// bit patterns of x the bits its pow(x, literal) returns (tests/test_gamma_pow_gpu.py, exhaustive).
+// RT_GAMMA_FAST=0 (A/B builds, scripts/build_variant.sh): the plain pow, and no frame-1 shortcut.
+#ifndef RT_GAMMA_FAST
+#define RT_GAMMA_FAST 1
+#endif
+enum class GammaExp { kFrom, kTo, kTo0 };
+template <GammaExp E>
+__device__ __forceinline__ constexpr float gamma_exp() {
+    return E == GammaExp::kFrom ? 2.2f : E == GammaExp::kTo ? 0.454545f : 0.45454545f;
+}
+
 struct MathPinned {
     static constexpr int kId = 0;
     static constexpr bool kContract = false;
@@ -126,6 +140,11 @@ struct MathPinned {
     // (out of line; inlining the BRDF's call into the render costs 13 %: profiles/r06/pinned_ab.txt)
     __device__ __forceinline__ static float pow(float x, float y) { return pm_pow(x, y); }
 #endif
+    // (the pinned fp64 pow stays as it is)
+    template <GammaExp E>
+    __device__ __forceinline__ static float pow_gamma(float x) {
+        return pow(x, gamma_exp<E>());
+    }
     // pow(x, 2.0f) call sites of the reference (kernel_bvh.cl:224, :275): pinned as the
     // exact square, as LLVM's libcall simplifiers fold it (rt_pinned_math.h)
     __device__ __forceinline__ static float pow2(float x) { return pm_sq(x); }
@@ -161,6 +180,28 @@ struct MathDeviceLib {
     }
     __device__ __forceinline__ static float rsqrt(float d) { return ::rsqrtf(d); }
     __device__ __forceinline__ static float pow(float x, float y) { return ::powf(x, y); }
+    // ::powf(x, Y) for a literal Y that is positive, finite and no integer.  The library opens with
+    // y = (x == 1) ? 1 : y, after which y is no constant to the compiler and every call classifies it
+    // at run time (integer? odd? sign transfer, negative base) with selects.  Here the ordinary
+    // operands -- positive, finite, not 1 -- take the library call behind a branch on exactly those
+    // facts, written as the float comparisons the library itself makes so that its selects fold (the
+    // log, the product and the exp remain: 137 VALU and 2 for the test against 157); the others get
+    // the library's results for them, read off its source and checked over all 2^32 operands:
+    // 1 -> 1, +-0 -> +0, +-inf -> +inf, negative or NaN -> the canonical quiet NaN.
+    template <GammaExp E>
+    __device__ __forceinline__ static float pow_gamma(float x) {
+#if RT_GAMMA_FAST
+        if (x > 0.0f && x < __builtin_inff() && !(x == 1.0f)) return ::powf(x, gamma_exp<E>());
+        const uint32_t b = __float_as_uint(x), mag = b & 0x7fffffffu;
+        float r = __uint_as_float(0x7fc00000u);
+        if (b == 0x3f800000u) r = 1.0f;
+        if (mag == 0u) r = 0.0f;
+        if (mag == 0x7f800000u) r = __builtin_inff();
+        return r;
+#else
+        return ::powf(x, gamma_exp<E>());
+#endif
+    }
     // the AMD OpenCL compiler folds pow(x, 2.0f) to x*x (AMDGPU libcall simplification;
     // visible in the reference's IR: DistributionGGX, SampleSpecular)
     __device__ __forceinline__ static float pow2(float x) { return x * x; }

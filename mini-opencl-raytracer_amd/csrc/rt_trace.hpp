@@ -66,7 +66,7 @@ struct TraceEnds {
     __device__ __forceinline__ void first_hit(int32_t prim) { prim0 = prim; }
     template <class M>
     __device__ __forceinline__ void finish(F3 r) {
-        if (q.encoding != 0) r = gamma_out<M>(0u, f3s(0.0f), r);
+        if (q.encoding != 0) r = gamma_out_step<M>(0u, f3s(0.0f), r);
         q.out[pos] = make_float4(r.x, r.y, r.z, __int_as_float(prim0));
     }
 };
