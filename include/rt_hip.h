@@ -389,9 +389,48 @@ typedef struct rt_trace_params {
     uint32_t seed_base;
     int encoding;
 } rt_trace_params;
+/* (kernel_bvh.cl:378, the analytic light's term, follows rtKernelSetShadowRays below) */
 int rtEnqueueTracePaths(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem seeds /* may be NULL */, size_t first,
                         size_t n, const rt_trace_params* params, rt_mem out);
 int rtEnqueueCameraPaths(rt_context ctx, rt_kernel k, size_t global_work_size, rt_mem rays, rt_mem seeds);
+
+/* ---- shadow rays for the analytic light (extension) ---------------------------------------------
+ * The reference's Render adds lightPixel(...) * diffuse * beta at every shaded hit (kernel_bvh.cl:378) and
+ * casts no shadow ray: its light shines through walls.  rtKernelSetShadowRays(k, 1) makes
+ * rtEnqueueTracePaths and rtEnqueueSamplePixels test that term against the scene first; 0, the default,
+ * is the reference.  It is a kernel setting like the math mode: it flushes the held frames as every
+ * kernel setting does and costs nothing until one of those two calls reads it.
+ * rtEnqueueKernel, rtEnqueueKernelFrames under every schedule, the ray queries, the surface, feature and
+ * motion passes do not read it: they are the reference's KernelEntry and stay bit for bit what they are
+ * whatever the setting.
+ *
+ * With the setting on, Render is the reference's with one change at line 378.  Let lp be lightPixel's
+ * value for the hit, evaluated exactly where the reference evaluates it (after beta *= mul).
+ *   !(lp > 0.0f)  (zero, negative, NaN): line 378 executes as in the reference.  No shadow ray is traced
+ *                 and nothing is counted.
+ *   otherwise     one shadow ray is answered with the semantics of RT_QUERY_ANY for the rt_ray
+ *                 {origin = isect.pos, tmin = 0.01f, dir = L, tmax = T} in k's math mode: isect.pos is the
+ *                 hit position ray.origin + ray.dir * t, the value the next ray's origin is formed from;
+ *                 for LIGHT_TYPE <= 0, L = -lightDirection = (0.5, -0.4, 0.1) and T = 100000.0f; for
+ *                 LIGHT_TYPE >= 1, L = lightPosition - X, the vector lightPixel forms, and
+ *                 T = sqrt(dot(L, L)).  The query's InitRay normalises L, so t is in world units.  The
+ *                 triangle test is the reference's one-sided RayTriangle with the query's two
+ *                 generalisations (isect.t starts at T; an accepted triangle also needs t >= tmin) and
+ *                 nothing else: an occluder blocks only if the reference's test would accept it, and hits
+ *                 with t < 0.01 -- the surface itself, a duplicated face -- are discarded.
+ *                 If the query hits, line 378 is skipped: radiance keeps its bits.  If it misses, line 378
+ *                 executes as in the reference.
+ * No RNG draw is added or moved; beta, the next ray (line 379) and every later segment are the
+ * reference's.  The shadow ray is cast wherever line 378 is reached, on the last bounce too.
+ * With rtKernelSetStats on, each shadow ray adds one to rays plus the node visits and triangle tests it
+ * walked (an any-hit walk counts only what it walked); hits stays the count of shaded surface hits.
+ * Shadow walks read the record set of the launch's other walks (plain, collapsed or pruned; after a
+ * refit the moved boxes).  With the setting off every result and every counter is what it was before the
+ * setting existed.
+ * Errors: a NULL kernel RT_INVALID_KERNEL; `enable` other than 0 or 1, or a NULL `enable` pointer,
+ * RT_INVALID_VALUE (the setting keeps its value). */
+int rtKernelSetShadowRays(rt_kernel k, int enable);
+int rtKernelGetShadowRays(rt_kernel k, int* enable);
 
 /* ---- adaptive sampling: per-pixel sample statistics and selection (extension) ------------------
  * Four calls that let a progressive renderer put its paths where the noise is: per-pixel statistics
@@ -532,6 +571,7 @@ int rtEnqueueResolveSamples(rt_context ctx, rt_kernel k, rt_mem stats, unsigned 
  * WIDTH or HEIGHT zero, the scene, node or material slot unbound, or LIGHT_BOUNCES, LIGHT_TYPE or
  * SKYBOX_INTENSITY unset RT_INVALID_KERNEL_ARGS; n == 0 RT_SUCCESS with nothing prepared or launched; then
  * the scene preparation's own errors, and a leaf of more than 127 triangles RT_INVALID_OPERATION. */
+/* (the analytic light's term follows rtKernelSetShadowRays, as in rtEnqueueTracePaths) */
 int rtEnqueueSamplePixels(rt_context ctx, rt_kernel k, rt_mem ids, rt_mem count /* may be NULL */, size_t first,
                           size_t n, size_t n_pixels, rt_mem stats);
 

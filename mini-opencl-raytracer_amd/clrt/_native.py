@@ -279,6 +279,8 @@ _HIP_PROTOS = {
     "rtFinish": (ctypes.c_int, [_vp]),
     "rtEnqueueCopyBufferToPointer": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rtKernelSetMathMode": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "rtKernelSetShadowRays": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "rtKernelGetShadowRays": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "rtKernelSetWorkRange": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64]),
     "rtKernelSetSchedule": (ctypes.c_int, [_vp, ctypes.c_int]),
     "rtKernelSetRowInterleave": (ctypes.c_int, [_vp, ctypes.c_uint, ctypes.c_uint]),

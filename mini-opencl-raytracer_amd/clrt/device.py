@@ -400,6 +400,15 @@ class CLKernel:
     def set_math_mode(self, mode: int) -> None:
         check(self._lib.rtKernelSetMathMode(self.handle, int(mode)), "math mode")
 
+    def set_shadow_rays(self, enable: bool) -> None:
+        """rtKernelSetShadowRays: TracePaths and SamplePixels test the analytic light's term against the scene."""
+        check(self._lib.rtKernelSetShadowRays(self.handle, int(bool(enable))), "shadow rays")
+
+    def get_shadow_rays(self) -> bool:
+        v = ctypes.c_int()
+        check(self._lib.rtKernelGetShadowRays(self.handle, ctypes.byref(v)), "shadow rays")
+        return bool(v.value)
+
     def set_schedule(self, sched: int) -> None:
         check(self._lib.rtKernelSetSchedule(self.handle, int(sched)), "schedule")
 

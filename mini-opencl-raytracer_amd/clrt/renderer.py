@@ -44,6 +44,7 @@ class Raytracer:
         self.kernel: CLKernel | None = None
         self.output: Buffer | None = None
         self.pixels = np.zeros((self.height * self.width, 4), np.float32)
+        self._shadow_rays = False             # shadow_rays before Init()
         self._scene_bufs: list = []
         self._cast_bufs: tuple | None = None  # (capacity in rays, ray buffer, hit buffer) of cast()
         self._surf_buf: tuple | None = None   # (capacity in records, surface buffer) of surfaces()
@@ -69,7 +70,21 @@ class Raytracer:
     def Init(self) -> None:
         self.ctx = CLContext(self.device)
         self.kernel = CLKernel(self.ctx, "KernelEntry")
+        self.kernel.set_shadow_rays(self._shadow_rays)
         self.SetupBuffers()
+
+    @property
+    def shadow_rays(self) -> bool:
+        """Shadow rays for the analytic light (rtKernelSetShadowRays): trace(), render_adaptive() and whatever
+        else goes through TracePaths or SamplePixels follow it; RenderFrame and the other KernelEntry renders
+        stay the reference's.  Default False."""
+        return self.kernel.get_shadow_rays() if self.kernel is not None else self._shadow_rays
+
+    @shadow_rays.setter
+    def shadow_rays(self, enable: bool) -> None:
+        self._shadow_rays = bool(enable)
+        if self.kernel is not None:
+            self.kernel.set_shadow_rays(self._shadow_rays)
 
     # CLRaytracer::SetupBuffers (CLRaytracer.cpp:122-137)
     def SetupBuffers(self) -> None:

@@ -94,6 +94,7 @@ struct rt_kernel_s {
     bool comm_sharded = false;  // bands set by rtCommShardKernel: the gather's plan needs the whole frame
     rt_mem hit_ids = nullptr, hit_t = nullptr;
     bool stats = false, timing = false, force_global = false;
+    bool shadow_rays = false;  // rtKernelSetShadowRays: read by rtEnqueueTracePaths and rtEnqueueSamplePixels alone
     uint64_t launches = 0;
     uint64_t pf_waits = ~0ull;         // ctx->host_waits at the previous per-frame step launch
     bool last_lds = false;
@@ -883,7 +884,7 @@ int rtEnqueueTracePaths(rt_context ctx, rt_kernel k, rt_mem rays, rt_mem seeds, 
     rc = prepare_scene(k, k->args);
     if (rc) return rc;
     // 4. the plan, with the kernel's occupancy at the LDS size it chose
-    in.math = k->math, in.stats = k->stats;
+    in.math = k->math, in.stats = k->stats, in.shadow_rays = k->shadow_rays;
     const rti::DeviceScene& sc = k->scene;
     in.n_nodes = sc.n_nodes(), in.n_tris = sc.n_tris(), in.n_mats = sc.n_mats();
     in.oct_ok = sc.oct_ok();
@@ -1370,7 +1371,7 @@ int rtEnqueueSamplePixels(rt_context ctx, rt_kernel k, rt_mem ids, rt_mem count,
     if (rc) return rc;
     // 4. the plan, with the kernel's occupancy at the LDS size it chose
     rtp::TraceIn& t = in.scene;
-    t.math = k->math, t.stats = k->stats;
+    t.math = k->math, t.stats = k->stats, t.shadow_rays = k->shadow_rays;
     const rti::DeviceScene& sc = k->scene;
     t.n_nodes = sc.n_nodes(), t.n_tris = sc.n_tris(), t.n_mats = sc.n_mats();
     t.oct_ok = sc.oct_ok();
@@ -1675,6 +1676,21 @@ int rtKernelSetMathMode(rt_kernel k, int mode) {
     flush_kernel(k);
     if (mode != RT_MATH_PINNED && mode != RT_MATH_DEVICELIB && mode != RT_MATH_SHIPPED) return RT_INVALID_VALUE;
     k->math = mode;
+    return RT_SUCCESS;
+}
+
+int rtKernelSetShadowRays(rt_kernel k, int enable) {
+    if (!k) return RT_INVALID_KERNEL;
+    flush_kernel(k);
+    if (enable != 0 && enable != 1) return RT_INVALID_VALUE;
+    k->shadow_rays = enable == 1;
+    return RT_SUCCESS;
+}
+
+int rtKernelGetShadowRays(rt_kernel k, int* enable) {
+    if (!k) return RT_INVALID_KERNEL;
+    if (!enable) return RT_INVALID_VALUE;
+    *enable = k->shadow_rays ? 1 : 0;
     return RT_SUCCESS;
 }
 

@@ -663,6 +663,92 @@ __device__ __forceinline__ bool shade_bounce(const Traversal& h, Ray& ray, F3& r
     return true;
 }
 
+// What a bounce that goes on leaves for kernel_bvh.cl:378-379 when the light's term waits for a shadow
+// ray (rtKernelSetShadowRays): the hit's position, the sampled direction, lightPixel's value and that
+// value times the material's diffuse colour.
+struct Lit {
+    F3 pos, wi, term;
+    float lp;
+};
+
+// shade_bounce up to lightPixel (kernel_bvh.cl:358-377), operation for operation: a sibling, not a split,
+// so that shade_bounce compiles to what it compiled to before this one existed.  Returns false where
+// shade_bounce does; otherwise `l` holds what lines 378-379 read, `radiance` has not received the light's
+// term and `ray` is still the segment that hit.
+template <class M, bool kStats>
+__device__ __forceinline__ bool shade_surface(const Traversal& h, const Ray& ray, F3& radiance, F3& beta,
+                                              uint32_t& seed, const SceneView& sc, const KernelArgs& a,
+                                              LaneStats& st, Lit& l) {
+    constexpr bool kScalarRec = false;
+    if (h.prim < 0) {
+        radiance = madd<M>(beta, f3s(0.5f * a.skyboxIntensity), radiance);
+        return false;
+    }
+    if (kStats) ++st.hits;
+    // hit record of the last accepted triangle (kernel_bvh.cl:142-147), from the packed
+    // shading records (bit copies of the normals, mtlIndex and material fields)
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const float4* rec = sc.stris + 3 * h.prim;
+    v4f s1, s2;
+    v2f s3;
+    // (records in HBM/L2, kScalarRec: a round whose lanes all hit one triangle, or all use one
+    // material, reads that record through the scalar cache -- oct_step_g; bunny proxy -0.3 %,
+    // profiles/r05/goct_scalar_ab.txt)
+    const uint32_t p0 = kScalarRec ? (uint32_t)__builtin_amdgcn_readfirstlane(h.prim) : 0u;
+    if (kScalarRec && __ballot((uint32_t)h.prim != p0) == 0ull) {
+        const cv4f* cp = (const cv4f*)(sc.stris + 3u * p0);
+        s1 = cp[0];
+        s2 = cp[1];
+        s3 = *((__attribute__((address_space(4))) const v2f*)(sc.stris + 3u * p0 + 2u));
+    } else {
+        s1 = *reinterpret_cast<const v4f*>(rec);
+        s2 = *reinterpret_cast<const v4f*>(rec + 1);
+        s3 = *reinterpret_cast<const v2f*>(rec + 2);
+    }
+    const F3 normal = shading_normal<M>(F3{s1.x, s1.y, s1.z}, F3{s2.x, s2.y, s2.z}, F3{s2.w, s3.x, s3.y}, h.u, h.v);
+    const F3 pos = hit_position<M>(ray, h.t);
+    const uint32_t mi = 4u * __float_as_uint(s1.w);
+    v4f m0, m1, m2;
+    const uint32_t mi0 = kScalarRec ? __builtin_amdgcn_readfirstlane(mi) : 0u;
+    if (kScalarRec && __ballot(mi != mi0) == 0ull) {
+        const cv4f* cp = (const cv4f*)(sc.smats + mi0);
+        m0 = cp[0];
+        m1 = cp[1];
+        m2 = cp[2];
+    } else {
+        m0 = *reinterpret_cast<const v4f*>(sc.smats + mi);
+        m1 = *reinterpret_cast<const v4f*>(sc.smats + mi + 1);
+        m2 = *reinterpret_cast<const v4f*>(sc.smats + mi + 2);
+    }
+    MatView m{F3{m0.x, m0.y, m0.z}, F3{m1.x, m1.y, m1.z}, F3{m2.x, m2.y, m2.z}, m0.w, m1.w, m2.w};
+
+    radiance = madd<M>(beta * m.emission, 50.0f, radiance);
+    F3 wi = f3s(0.0f);
+    float pdf = 0.0f;
+    const F3 f = sample_brdf<M>(-ray.d, wi, pdf, normal, m, seed);
+    if (pdf <= 0.0f || pdf != pdf) return false;
+    const F3 fd = f * M::dot(wi, normal);
+    const F3 mul{M::div(fd.x, pdf), M::div(fd.y, pdf), M::div(fd.z, pdf)};
+    beta = beta * mul;
+    const float lp = light_pixel<M>(ray, h.t, normal, a.lightType);
+    l = Lit{pos, wi, f3s(lp) * m.diffuse, lp};
+    return true;
+}
+
+// The shadow ray of rtKernelSetShadowRays (rt_hip.h) from the hit position `pos`: its raw direction --
+// -lightDirection, or lightPosition - X, the vector lightPixel forms -- and its tmax.
+template <class M>
+__device__ __forceinline__ F3 shadow_dir(F3 pos, int lightType, float& tmax) {
+    if (lightType <= 0) {
+        tmax = kMaxDist;
+        return F3{0.5f, -0.4f, 0.1f};
+    }
+    const F3 L = F3{0.0f, -10.0f, 16.0f} - pos;
+    tmax = M::sqrt(M::dot(L, L));
+    return L;
+}
+
 // kernel_bvh.cl:349-384 (Render)
 template <class M, bool kOct, bool kStats>
 __device__ __forceinline__ F3 render(const SceneView& sc, Ray ray,

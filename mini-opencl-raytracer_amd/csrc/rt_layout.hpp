@@ -69,11 +69,15 @@ struct Variant {
     bool stats;   // rt_stats counters
     bool fused;   // the launch writes radiance slots (step schedule: the entry points' kMode)
     bool any;     // ray queries: any-hit
+    bool shadow = false;  // path traces and fused samples: shadow rays (rtKernelSetShadowRays)
     bool lds() const { return walk == Walk::Lds || walk == Walk::LdsB; }
-    // dense index for per-variant caches, < kVariantSlots (schedules 0, 2, 4; maths 0..2)
-    int slot() const { return (((((sched >> 1) * 3 + math) * 4 + (int)walk) * 2 + stats) * 2 + fused) * 2 + any; }
+    // dense index for per-variant caches, < kVariantSlots (schedules 0, 2, 4; maths 0..2); shadow is the
+    // highest-order factor, so a variant without it has the slot it had before the bit existed
+    int slot() const {
+        return (((((shadow * 3 + (sched >> 1)) * 3 + math) * 4 + (int)walk) * 2 + stats) * 2 + fused) * 2 + any;
+    }
 };
-constexpr int kVariantSlots = 3 * 3 * 4 * 2 * 2 * 2;
+constexpr int kVariantSlots = 2 * 3 * 3 * 4 * 2 * 2 * 2;
 static_assert((kSchedTiles >> 1) == 0 && (kSchedStep >> 1) == 1 && (kSchedWavefront >> 1) == 2, "Variant::slot");
 
 // ---- wavefront schedule (rt_wavefront.hpp) ----

@@ -108,7 +108,14 @@ template <class M, bool kStats, bool kBofs, bool kGlobalOct>
 __global__ __launch_bounds__(kTraceThreads) __attribute__((amdgpu_waves_per_eu(RT_TRACE_WAVES, 8)))
 void sample_pixels(KernelArgs a, SampleArgs q) {
     SampleEnds<M> e(a, q);
-    trace_loop<M, kStats, kBofs, kGlobalOct>(a, e, q.refillMin, q.shadeMin);
+    trace_loop<M, kStats, kBofs, kGlobalOct, false>(a, e, q.refillMin, q.shadeMin);
+}
+// rtKernelSetShadowRays(k, 1): the trace's shadow walks between the same two ends
+template <class M, bool kStats, bool kBofs, bool kGlobalOct>
+__global__ __launch_bounds__(kTraceThreads) __attribute__((amdgpu_waves_per_eu(RT_TRACE_WAVES, 8)))
+void sample_pixels_shadow(KernelArgs a, SampleArgs q) {
+    SampleEnds<M> e(a, q);
+    trace_loop<M, kStats, kBofs, kGlobalOct, true>(a, e, q.refillMin, q.shadeMin);
 }
 
 template <class M, bool S>
@@ -117,8 +124,15 @@ SampleKernelFn sample_pick_s(Walk w) {
            : w == Walk::Lds ? sample_pixels<M, S, false, false>
                             : sample_pixels<M, S, false, true>;
 }
+template <class M, bool S>
+SampleKernelFn sample_pick_shadow_s(Walk w) {
+    return w == Walk::LdsB  ? sample_pixels_shadow<M, S, true, false>
+           : w == Walk::Lds ? sample_pixels_shadow<M, S, false, false>
+                            : sample_pixels_shadow<M, S, false, true>;
+}
 template <class M>
 SampleKernelFn sample_pick(const Variant& v) {
+    if (v.shadow) return v.stats ? sample_pick_shadow_s<M, true>(v.walk) : sample_pick_shadow_s<M, false>(v.walk);
     return v.stats ? sample_pick_s<M, true>(v.walk) : sample_pick_s<M, false>(v.walk);
 }
 

@@ -71,7 +71,17 @@ struct TraceEnds {
     }
 };
 
-template <class M, bool kStats, bool kBofs, bool kGlobalOct, class Ends>
+//
+// kShadow (rtKernelSetShadowRays, rt_hip.h): a bounce that goes on with lightPixel > 0 does not add the
+// light's term.  The lane keeps the term and the sampled direction, and walks the shadow ray from the hit
+// position first -- [0.01, T], ended at its first acceptance like the query's any-hit walk, in the same
+// node and triangle bursts as its neighbours' path walks.  When that walk ends the lane resolves at the top
+// of the loop, without waiting for a shading round: the term is added if nothing was hit, then the next
+// segment starts from the shadow ray's origin (the hit position) or, after the last bounce, the path
+// finishes.  `sh` is 0 on a path walk, kShadowGoOn / kShadowLast on a shadow walk.
+constexpr uint32_t kShadowGoOn = 1u, kShadowLast = 2u;
+
+template <class M, bool kStats, bool kBofs, bool kGlobalOct, bool kShadow, class Ends>
 __device__ __forceinline__ void trace_loop(const KernelArgs& a, Ends& e, uint32_t refillMin, uint32_t shadeMin) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     const uint32_t tid = threadIdx.x, nthr = blockDim.x;
@@ -112,11 +122,29 @@ __device__ __forceinline__ void trace_loop(const KernelArgs& a, Ends& e, uint32_
     F3 radiance = f3s(0.0f), beta = f3s(1.0f);
     float tmin = 0.0f;
     uint32_t seed = 0, bounce = 0;
+    // kShadow: the pending term and the sampled direction of the lane's shadow walk
+    F3 term = f3s(0.0f), swi = f3s(0.0f);
+    uint32_t sh = 0u;
     // the walk word as in query_body: node < 2^24, leaf code, END (a.nNodes: the walk is over, the lane
     // waits for its shading round), kNotWalking (the lane is free)
     uint32_t cur = kNotWalking, skip = 0u;
 
     for (;;) {
+        if (kShadow && cur == a.nNodes && sh != 0u) {
+            // ---- a shadow walk ended: kernel_bvh.cl:378 unless occluded, then :379 or the path's end --
+            if (h.prim < 0) radiance = madd<M>(term, beta, radiance);
+            if (sh == kShadowGoOn) {
+                ray = init_ray<M>(madd<M>(swi, 0.01f, ray.o), swi);
+                tmin = -__builtin_inff();
+                h = Traversal{kMaxDist, -1, 0.0f, 0.0f};
+                cur = 0u;
+                if (kStats) ++st.rays;
+            } else {
+                e.template finish<M>(F3{M::max(radiance.x, 0.0f), M::max(radiance.y, 0.0f), M::max(radiance.z, 0.0f)});
+                cur = kNotWalking;
+            }
+            sh = 0u;
+        }
         uint32_t n_trav = popc_ballot(cur < kLeafMin && cur != a.nNodes);
         uint32_t n_leaf = popc_ballot((int32_t)cur >= (int32_t)kLeafMin);
         uint32_t n_ready = popc_ballot(cur == a.nNodes);
@@ -175,9 +203,34 @@ __device__ __forceinline__ void trace_loop(const KernelArgs& a, Ends& e, uint32_
                     hu.v = ev.v;
                 }
                 if (bounce == 0u) e.first_hit(h.prim);
-                const bool go = shade_bounce<M, kStats>(hu, ray, radiance, beta, seed, sc, a, st);
+                bool go;
+                if (kShadow) {
+                    Lit l;
+                    go = shade_surface<M, kStats>(hu, ray, radiance, beta, seed, sc, a, st, l);
+                    if (go && l.lp > 0.0f) {
+                        // the shadow ray {pos, 0.01, L, T}; what follows it waits in term, swi and sh
+                        float tmax;
+                        const F3 L = shadow_dir<M>(l.pos, a.lightType, tmax);
+                        term = l.term;
+                        swi = l.wi;
+                        sh = bounce + 1u < bounces ? kShadowGoOn : kShadowLast;
+                        ray = init_ray<M>(l.pos, L);
+                        tmin = 0.01f;
+                        h = Traversal{tmax, -1, 0.0f, 0.0f};
+                        cur = 0u;
+                        if (kStats) ++st.rays;
+                    } else if (go) {
+                        // !(lp > 0): lines 378-379 as the reference executes them
+                        radiance = madd<M>(l.term, beta, radiance);
+                        ray = init_ray<M>(madd<M>(l.wi, 0.01f, l.pos), l.wi);
+                    }
+                } else {
+                    go = shade_bounce<M, kStats>(hu, ray, radiance, beta, seed, sc, a, st);
+                }
                 ++bounce;
-                if (go && bounce < bounces) {
+                if (kShadow && sh != 0u) {
+                    // (the lane walks its shadow ray)
+                } else if (go && bounce < bounces) {
                     // the next segment is the reference's Intersect
                     tmin = -__builtin_inff();
                     h = Traversal{kMaxDist, -1, 0.0f, 0.0f};
@@ -212,9 +265,10 @@ __device__ __forceinline__ void trace_loop(const KernelArgs& a, Ends& e, uint32_
                 if ((int32_t)cur >= (int32_t)kLeafMin) {
                     if (kStats) ++st.tests;
                     const uint32_t idx = cur & 0x00ffffffu;
-                    (void)query_triangle<M>(sc.tris + 3 * (size_t)idx, (int32_t)idx, ray, tmin, h);
+                    const bool ok = query_triangle<M>(sc.tris + 3 * (size_t)idx, (int32_t)idx, ray, tmin, h);
                     cur += 1u - kLeafMin;
                     if (cur < kLeafMin) cur = skip;
+                    if (kShadow && ok && sh != 0u) cur = a.nNodes;  // any-hit: the shadow walk ends here
                 }
             }
         }
@@ -222,10 +276,10 @@ __device__ __forceinline__ void trace_loop(const KernelArgs& a, Ends& e, uint32_
     if (kStats) flush_stats(a, st, (int)lane);
 }
 
-template <class M, bool kStats, bool kBofs, bool kGlobalOct>
+template <class M, bool kStats, bool kBofs, bool kGlobalOct, bool kShadow>
 __device__ __forceinline__ void trace_body(const KernelArgs& a, const TraceArgs& q) {
     TraceEnds e{q};
-    trace_loop<M, kStats, kBofs, kGlobalOct>(a, e, q.refillMin, q.shadeMin);
+    trace_loop<M, kStats, kBofs, kGlobalOct, kShadow>(a, e, q.refillMin, q.shadeMin);
 }
 
 // camera_rays_body's record for work-item gid, and the RNG state CreateRay leaves behind: gid +
@@ -255,7 +309,13 @@ __device__ __forceinline__ void camera_paths_body(const KernelArgs& a, float4* r
 template <class M, bool kStats, bool kBofs, bool kGlobalOct>
 __global__ __launch_bounds__(kTraceThreads) __attribute__((amdgpu_waves_per_eu(RT_TRACE_WAVES, 8)))
 void trace_paths(KernelArgs a, TraceArgs q) {
-    trace_body<M, kStats, kBofs, kGlobalOct>(a, q);
+    trace_body<M, kStats, kBofs, kGlobalOct, false>(a, q);
+}
+// rtKernelSetShadowRays(k, 1): the same budget (profiles/shadows/register_report.txt)
+template <class M, bool kStats, bool kBofs, bool kGlobalOct>
+__global__ __launch_bounds__(kTraceThreads) __attribute__((amdgpu_waves_per_eu(RT_TRACE_WAVES, 8)))
+void trace_paths_shadow(KernelArgs a, TraceArgs q) {
+    trace_body<M, kStats, kBofs, kGlobalOct, true>(a, q);
 }
 template <class M>
 __global__ __launch_bounds__(256) void camera_paths(KernelArgs a, float4* rays, uint32_t* seeds, uint32_t n) {
@@ -290,8 +350,15 @@ TraceKernelFn trace_pick_s(Walk w) {
            : w == Walk::Lds ? trace_paths<M, S, false, false>
                             : trace_paths<M, S, false, true>;
 }
+template <class M, bool S>
+TraceKernelFn trace_pick_shadow_s(Walk w) {
+    return w == Walk::LdsB  ? trace_paths_shadow<M, S, true, false>
+           : w == Walk::Lds ? trace_paths_shadow<M, S, false, false>
+                            : trace_paths_shadow<M, S, false, true>;
+}
 template <class M>
 TraceKernelFn trace_pick(const Variant& v) {
+    if (v.shadow) return v.stats ? trace_pick_shadow_s<M, true>(v.walk) : trace_pick_shadow_s<M, false>(v.walk);
     return v.stats ? trace_pick_s<M, true>(v.walk) : trace_pick_s<M, false>(v.walk);
 }
 

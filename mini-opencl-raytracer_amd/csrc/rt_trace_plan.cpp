@@ -64,6 +64,8 @@ int trace_shape(const TraceIn& in, TracePlan* out) {
     }
     const rtk::Walk walk = lds ? (p.octB == rtk::kOctB ? rtk::Walk::LdsB : rtk::Walk::Lds) : rtk::Walk::GlobalOct;
     p.variant = rtk::Variant{0, in.math, walk, in.stats, false, false};
+    // (the kernel's setting names the instance; nothing else of the plan depends on it)
+    p.variant.shadow = in.shadow_rays;
     p.smem = (lds ? scene_bytes : 0) + rings;
     p.refillMin = in.tune.trace_refill_min;
     p.shadeMin = in.tune.trace_shade_min;

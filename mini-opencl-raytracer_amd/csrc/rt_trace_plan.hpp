@@ -32,6 +32,7 @@ struct TraceIn {
     // ---- the kernel's settings and its packed scene (trace_shape) ----
     int math;                            // RT_MATH_*
     bool stats;                          // rt_stats counters on
+    bool shadow_rays;                    // rtKernelSetShadowRays: the kernel that walks shadow rays
     uint32_t n_nodes, n_tris, n_mats;    // the packed scene
     bool oct_ok;                         // every leaf fits the octant records
     bool goct_available;                 // regrouped octant records exist ...
