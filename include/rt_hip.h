@@ -256,6 +256,23 @@ typedef struct rt_node_collapse_info {
 } rt_node_collapse_info;
 int rtKernelGetNodeCollapse(rt_kernel k, rt_node_collapse_info* out);
 
+/* The gate skip (the same walks as the node collapse, which it contains).  In a tree whose every box lies
+ * inside its parent's box plane by plane, an interior node's box test decides no result: where it fails,
+ * every box below fails too, leaves included, and leaves keep their test.  For such scenes the second set
+ * of records leads past the interior nodes whose test costs more visits than it saves (a surface-area
+ * estimate, csrc/rt_scene_pack.cpp), in hit and miss links alike, and the third set is built from it: the
+ * same leaves and triangles in the same order, the same results.  The conditions are the collapse's: stats
+ * launches and launches after rtRefitBVH walk the plain records.
+ * gate_links: link words the set changes against the plain one (the collapsed ones among them; 0: the
+ * tree does not nest, or a build with RT_GATE_SKIP=0); scene_nested: the scene has such a set and it may be
+ * walked as of the last preparation; launch_gate_skipped: whether the kernel's last launch walked it
+ * (launch_collapsed is 1 as well then).  Flushes coalesced frames; does not wait for the device. */
+typedef struct rt_gate_skip_info {
+    uint32_t gate_links;
+    int32_t scene_nested, launch_gate_skipped;
+} rt_gate_skip_info;
+int rtKernelGetGateSkip(rt_kernel k, rt_gate_skip_info* out);
+
 /* The octant cull (the same walks as the node collapse).  RayTriangle rejects det < 1e-8, and for a
  * triangle in an axis plane the sign of det is the sign of one direction component: no ray of four of
  * the eight octants can hit it.  A host certificate (csrc/rt_octant_cull.cpp) decides per triangle and
@@ -268,7 +285,8 @@ int rtKernelGetNodeCollapse(rt_kernel k, rt_node_collapse_info* out);
  * rotated about an axis), triangles so thin that the component's margin is under 2^-18, and vertices
  * that are not finite or lie beyond 2^20.  Launches with stats on walk the plain records, and so does
  * every launch after rtRefitBVH until the next full preparation, since moved vertices are not certified.
- * pruned_links: link words the third set changes against the collapsed one; contracted_links: words
+ * pruned_links: link words the third set changes against the collapsed one (counted there also for a scene
+ * with a gate-skipped set, whose launches walk the pruned form of that set); contracted_links: words
  * changed by contracting interior nodes with one live child (always 0: not built); scene_certified: the
  * set may be walked as of the last preparation (0 after rtRefitBVH, and in builds with RT_OCTANT_CULL=0);
  * launch_pruned: whether the kernel's last launch -- render, ray query or path trace -- walked it

@@ -139,6 +139,12 @@ class NodeCollapseInfo(ctypes.Structure):
                 ("launch_collapsed", ctypes.c_int32)]
 
 
+class GateSkipInfo(ctypes.Structure):
+    """rt_gate_skip_info (rt_hip.h)."""
+    _fields_ = [("gate_links", ctypes.c_uint32), ("scene_nested", ctypes.c_int32),
+                ("launch_gate_skipped", ctypes.c_int32)]
+
+
 class OctantCullInfo(ctypes.Structure):
     """rt_octant_cull_info (rt_hip.h)."""
     _fields_ = [("pruned_links", ctypes.c_uint32), ("contracted_links", ctypes.c_uint32),
@@ -295,6 +301,7 @@ _HIP_PROTOS = {
     "rtKernelResetStats": (ctypes.c_int, [_vp]),
     "rtKernelGetPathKill": (ctypes.c_int, [_vp, ctypes.POINTER(PathKillInfo)]),
     "rtKernelGetNodeCollapse": (ctypes.c_int, [_vp, ctypes.POINTER(NodeCollapseInfo)]),
+    "rtKernelGetGateSkip": (ctypes.c_int, [_vp, ctypes.POINTER(GateSkipInfo)]),
     "rtKernelGetOctantCull": (ctypes.c_int, [_vp, ctypes.POINTER(OctantCullInfo)]),
     "rtKernelGetSceneInLDS": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "rtKernelForceGlobalScene": (ctypes.c_int, [_vp, ctypes.c_int]),

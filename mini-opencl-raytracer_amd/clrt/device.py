@@ -480,6 +480,15 @@ class CLKernel:
         return {"collapsed_links": int(s.collapsed_links), "scene_collapsible": bool(s.scene_collapsible),
                 "launch_collapsed": bool(s.launch_collapsed)}
 
+    def gate_skip(self) -> dict:
+        """rtKernelGetGateSkip: the link words the scene's gate-skipped record set changes against the plain
+        one (0: the tree's boxes do not nest), whether the scene has the set and it may be walked (not after
+        a device refit), and whether the last launch walked it."""
+        s = N.GateSkipInfo()
+        check(self._lib.rtKernelGetGateSkip(self.handle, ctypes.byref(s)), "gate skip")
+        return {"gate_links": int(s.gate_links), "scene_nested": bool(s.scene_nested),
+                "launch_gate_skipped": bool(s.launch_gate_skipped)}
+
     def octant_cull(self) -> dict:
         """rtKernelGetOctantCull: the link words the scene's pruned record set changes (culled subtrees;
         contracted single-child nodes, always 0), whether the set may be walked (not after a device

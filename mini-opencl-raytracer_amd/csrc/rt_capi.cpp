@@ -67,7 +67,9 @@ constexpr uint64_t kKnownFlags =
 constexpr size_t kHitPad = RT_TIMELINE ? 192 : 0;
 // diagnostic count builds (-DRT_NODE_COLLAPSE_STATS=1): stats launches walk the collapsed links too, so
 // their node_visits against the default build's is the exact number of visits the collapse removes
-// (the other counters stay; such a build's visits are not the reference's)
+// (the other counters stay; such a build's visits are not the reference's).  "The collapsed links" are the
+// gate-skipped ones where the scene has them: with -DRT_GATE_SKIP=0, or -DRT_GATE_SELECT=1, the same launch
+// counts the collapse alone, or the plain-ratio selection (profiles/r14/removed_visits.txt)
 #ifndef RT_NODE_COLLAPSE_STATS
 #define RT_NODE_COLLAPSE_STATS 0
 #endif
@@ -532,8 +534,10 @@ static rtp::PlanIn plan_inputs(rt_context ctx, rt_kernel k, const LaunchArgs& la
 // reference's -- or the scene's boxes were moved by a device refit since they were packed.  The kernels
 // are the same either way: only this pointer differs.  Where the octant-cull certificate is known too
 // (rt_octant_cull.cpp) the launch takes the pruned set (prune_oct_links), which is the collapsed set less
-// the links into subtrees no ray of the octant can hit, under the same two conditions.  Remembers the
-// choice for rtKernelGetNodeCollapse and rtKernelGetOctantCull.
+// the links into subtrees no ray of the octant can hit, under the same two conditions.  For a scene whose
+// boxes nest, "the collapsed set" is the gate-skipped one (gate_skip_oct_links), which contains it, and the
+// pruned set is built over that: rti::DeviceScene hands out whichever the scene has.  Remembers the
+// choice for rtKernelGetNodeCollapse, rtKernelGetGateSkip and rtKernelGetOctantCull.
 static const float4* oct_records(rt_kernel k, rtk::Walk w, bool regrouped) {
     const rti::DeviceScene& sc = k->scene;
     const bool pruned = sc.cull_ok() && (!k->stats || RT_OCTANT_CULL_STATS);
@@ -1875,6 +1879,15 @@ int rtKernelGetNodeCollapse(rt_kernel k, rt_node_collapse_info* out) {
     out->collapsed_links = k->scene.collapsed_links();
     out->scene_collapsible = k->scene.collapse_ok() ? 1 : 0;
     out->launch_collapsed = k->last_collapsed ? 1 : 0;
+    return RT_SUCCESS;
+}
+
+int rtKernelGetGateSkip(rt_kernel k, rt_gate_skip_info* out) {
+    if (!k || !out) return RT_INVALID_VALUE;
+    flush_kernel(k);
+    out->gate_links = k->scene.gate_links();
+    out->scene_nested = k->scene.gate_skipped() && k->scene.collapse_ok() ? 1 : 0;
+    out->launch_gate_skipped = k->scene.gate_skipped() && k->last_collapsed ? 1 : 0;
     return RT_SUCCESS;
 }
 

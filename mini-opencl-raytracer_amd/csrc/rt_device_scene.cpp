@@ -91,18 +91,24 @@ int DeviceScene::prepare(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     }
     // the device half: from here on the records are no longer those of the scene remembered
     invalidate();
-    rc = allocate(p.n_nodes, p.n_tris, p.n_mats, p.goct_nodes.size(), p.collapsed_links != 0,
-                  p.pruned_links != 0);
+    // the second and third record sets a launch walks: the gate-skipped set and its pruned form where the
+    // scene has one, else the collapsed set and the pruned set over it
+    const bool gated = !p.oct_nodes_gated.empty();
+    const std::vector<uint32_t>& oct2 = gated ? p.oct_nodes_gated : p.oct_nodes_collapsed;
+    const std::vector<uint32_t>& goct2 = gated ? p.goct_nodes_gated : p.goct_nodes_collapsed;
+    const std::vector<uint32_t>& oct3 = gated ? p.oct_nodes_gated_pruned : p.oct_nodes_pruned;
+    const std::vector<uint32_t>& goct3 = gated ? p.goct_nodes_gated_pruned : p.goct_nodes_pruned;
+    rc = allocate(p.n_nodes, p.n_tris, p.n_mats, p.goct_nodes.size(), !oct2.empty(), !oct3.empty());
     if (rc) return rc;
     hipStream_t st = qs(ctx);
     hipError_t e = upload(g_nodes_, p.global_nodes, st);
     if (e == hipSuccess) e = upload(refit_links_, p.refit_links, st);
     if (e == hipSuccess) e = upload(oct_nodes_, p.oct_nodes, st);
     if (e == hipSuccess && !p.goct_nodes.empty()) e = upload(goct_nodes_, p.goct_nodes, st);
-    if (e == hipSuccess && p.collapsed_links) e = upload(oct_collapsed_, p.oct_nodes_collapsed, st);
-    if (e == hipSuccess && !p.goct_nodes_collapsed.empty()) e = upload(goct_collapsed_, p.goct_nodes_collapsed, st);
-    if (e == hipSuccess && p.pruned_links) e = upload(oct_pruned_, p.oct_nodes_pruned, st);
-    if (e == hipSuccess && !p.goct_nodes_pruned.empty()) e = upload(goct_pruned_, p.goct_nodes_pruned, st);
+    if (e == hipSuccess && !oct2.empty()) e = upload(oct_collapsed_, oct2, st);
+    if (e == hipSuccess && !goct2.empty()) e = upload(goct_collapsed_, goct2, st);
+    if (e == hipSuccess && !oct3.empty()) e = upload(oct_pruned_, oct3, st);
+    if (e == hipSuccess && !goct3.empty()) e = upload(goct_pruned_, goct3, st);
     if (e == hipSuccess)
         e = rtk::launch_pack(static_cast<const rt_cl_triangle*>(tm->dptr), p.n_tris, packed_tris_, shade_tris_,
                              mm ? static_cast<const rt_cl_material*>(mm->dptr) : nullptr, p.n_mats, shade_mats_, st);
@@ -114,6 +120,8 @@ int DeviceScene::prepare(rt_context ctx, rt_mem tm, rt_mem nm, rt_mem mm) {
     oct_ok_ = p.oct_ok, goct_b_ = p.goct_b;
     collapsed_links_ = p.collapsed_links, collapse_known_ = RT_NODE_COLLAPSE != 0;
     pruned_links_ = p.pruned_links, cull_known_ = RT_OCTANT_CULL != 0 && p.oct_ok;
+    gate_links_ = p.gate_links, gate_skipped_ = gated;
+    has_collapsed_ = !oct2.empty(), has_pruned_ = !oct3.empty();
     root_known_ = p.n_nodes > 0 && in.nodes_size >= sizeof(rt_cl_bvh_node);
     if (root_known_) {
         rt_cl_bvh_node root;

@@ -53,8 +53,16 @@ public:
     // changes no link word.
     bool collapse_ok() const { return collapse_known_; }
     uint32_t collapsed_links() const { return collapsed_links_; }  // link words the set changes
-    const float4* oct_nodes_collapsed() const { return collapsed_links_ ? oct_collapsed_ : oct_nodes_; }
-    const float4* goct_collapsed() const { return collapsed_links_ && goct_b_ ? goct_collapsed_ : goct(); }
+    const float4* oct_nodes_collapsed() const { return has_collapsed_ ? oct_collapsed_ : oct_nodes_; }
+    const float4* goct_collapsed() const { return has_collapsed_ && goct_b_ ? goct_collapsed_ : goct(); }
+    // The gate-skipped link set (rtp::gate_skip_oct_links), which contains the collapse: where the scene
+    // has one (its boxes nest, and it differs from the collapsed set) the two accessors above return it in
+    // the collapsed set's place, and the two below its own pruned form, under the same conditions --
+    // collapse_ok() and cull_ok() -- since a device refit leaves the nesting unknown like the equality.
+    // gate_links(): the link words it changes against the plain set (0: no certificate, or a build with
+    // RT_GATE_SKIP=0); gate_skipped(): launches that walk "the collapsed links" walk these.
+    uint32_t gate_links() const { return gate_links_; }
+    bool gate_skipped() const { return gate_skipped_; }
     // The pruned link set (rtp::prune_oct_links over the collapsed set): per octant, no link leads to a
     // subtree whose triangles every ray of the octant rejects (rt_octant_cull.hpp).  cull_ok(): the set
     // may be walked -- triangles and boxes are as the host saw them at the last full preparation.  False
@@ -64,8 +72,8 @@ public:
     // accessors' records where the pruning changes no link word.
     bool cull_ok() const { return cull_known_; }
     uint32_t pruned_links() const { return pruned_links_; }  // link words the pruning changes
-    const float4* oct_nodes_pruned() const { return pruned_links_ ? oct_pruned_ : oct_nodes_collapsed(); }
-    const float4* goct_pruned() const { return pruned_links_ && goct_b_ ? goct_pruned_ : goct_collapsed(); }
+    const float4* oct_nodes_pruned() const { return has_pruned_ ? oct_pruned_ : oct_nodes_collapsed(); }
+    const float4* goct_pruned() const { return has_pruned_ && goct_b_ ? goct_pruned_ : goct_collapsed(); }
     // The root node's bounds (nodes[0]: min xyz, max xyz) as the host last saw them: read at every full
     // preparation, so a launch after a vertex or node write sees the new ones.  Null after a device
     // refit, which moves them without the host looking: such launches do without the view cull.
@@ -107,6 +115,9 @@ private:
     uint32_t collapsed_links_ = 0;
     bool cull_known_ = false;
     uint32_t pruned_links_ = 0;
+    uint32_t gate_links_ = 0;
+    bool gate_skipped_ = false;
+    bool has_collapsed_ = false, has_pruned_ = false;  // the two pairs of copies below hold a set
     bool kill_known_ = false;
     bool kill_ok_[2] = {false, false};  // [0] the IEEE material table, [1] the shipped policy's
     uint64_t full_prepares_ = 0, refits_ = 0;
@@ -115,10 +126,11 @@ private:
     float4 *oct_nodes_ = nullptr, *goct_nodes_ = nullptr, *g_nodes_ = nullptr;
     size_t packed_tris_cap_ = 0, shade_tris_cap_ = 0, shade_mats_cap_ = 0;
     size_t oct_nodes_cap_ = 0, goct_nodes_cap_ = 0, g_nodes_cap_ = 0;
-    // the collapsed copies of the two octant layouts (allocated for scenes whose set changes a link)
+    // the collapsed copies of the two octant layouts (allocated for scenes whose set changes a link), or
+    // the gate-skipped ones
     float4 *oct_collapsed_ = nullptr, *goct_collapsed_ = nullptr;
     size_t oct_collapsed_cap_ = 0, goct_collapsed_cap_ = 0;
-    // ... and the pruned copies (for scenes whose pruning changes a link)
+    // ... and the pruned copies of whichever they hold (for scenes whose pruning changes a link)
     float4 *oct_pruned_ = nullptr, *goct_pruned_ = nullptr;
     size_t oct_pruned_cap_ = 0, goct_pruned_cap_ = 0;
     // device refit: node -> parent, then node -> g_nodes record (n_nodes words each), uploaded by the

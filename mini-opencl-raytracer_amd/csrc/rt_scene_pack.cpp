@@ -3,6 +3,7 @@
 #include "rt_scene_pack.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <limits>
 
@@ -212,8 +213,8 @@ uint32_t collapse_oct_links(const std::vector<uint32_t>& oct, uint32_t n, std::v
 //   * A leaf is culled under o when every triangle of it is certified for o; an interior node when both
 //     children are.  (Children have larger indices: one backward sweep.)
 //   * Every hit_next or miss_next word of octant o that targets a culled node x is replaced by x's own
-//     miss_next, repeated while the target is culled.  miss_next words strictly advance in the octant's
-//     depth-first order and END is never culled, so the chain ends.
+//     miss_next in `base`, repeated while the target is culled.  miss_next words strictly advance in the
+//     octant's depth-first order and END is never culled, so the chain ends.
 // Why a walk over these links computes what the walk over `base` computes.  A walk that arrives at a
 // culled leaf x either fails x's box test and goes to x's miss_next, or passes it, tests x's triangles --
 // each test accepts nothing, by the certificate, so {t, prim, u, v} are what they were -- and goes to the
@@ -227,6 +228,11 @@ uint32_t collapse_oct_links(const std::vector<uint32_t>& oct, uint32_t n, std::v
 // remain are the base walk's in its order, and the final {t, prim, u, v} are its bits.
 //   * The collapsed links in `base` stay valid: a collapsed hit_next i -> c stands for box tests known to
 //     pass; if c is culled the argument above applies to the arrival at c.
+//   * So do the gate-skipped links where `base` is that set (gate_skip_oct_links).  The argument about the
+//     arrival at a culled node x is unaffected: it reads no box test but x's own, and "the skip of x's
+//     subtree" is, in that set, the word x's own miss_next holds there -- every link out of the subtree was
+//     redirected alike -- which is why the chain above follows base's miss_next and not the plain one.  Base's
+//     words never target a removed node, so neither do these.
 //   * If the root is culled under o, octant o's links stay as they are (a walk must start somewhere; such
 //     a scene shows that octant nothing and is not worth a special entry).
 //   * Planes, leaf codes and END are base's, word for word; a partly culled leaf keeps its whole code.
@@ -254,8 +260,9 @@ uint32_t prune_oct_links(const std::vector<uint32_t>& oct, const std::vector<uin
             }
         }
         if (culled[0]) continue;
+        const uint32_t* bb = &base[plane];  // (base's miss_next: the plain word but over the gate-skipped set)
         auto live = [&](uint32_t x) {
-            while (x < n && culled[x]) x = pb[(size_t)x * 4 + 3];
+            while (x < n && culled[x]) x = bb[(size_t)x * 4 + 3];
             return x;
         };
         for (uint32_t i = 0; i < n; ++i)
@@ -263,6 +270,199 @@ uint32_t prune_oct_links(const std::vector<uint32_t>& oct, const std::vector<uin
                 uint32_t& w = out[plane + (size_t)i * 4 + k];
                 if (w >= kLeafMin) continue;  // a leaf code
                 const uint32_t to = live(w);
+                if (to != w) {
+                    w = to;
+                    ++changed;
+                }
+            }
+    }
+    return changed;
+}
+
+// The certificate of the gate-skipped link set: every plane of the tree [0, n) is finite, and every node
+// but the root nests in its parent plane by plane -- pmin_child >= pmin_parent and pmax_child <= pmax_parent
+// on the three axes, compared as float values (+0 and -0 are equal) on the bounds the octant records are
+// bitwise copies of.  A builder that forms a parent's box as the exact min / max of its children's nests by
+// construction.  One node that does not and the scene has no such set: nothing is repaired.
+bool boxes_nest(const rt_cl_bvh_node* nd, uint32_t n) {
+    auto planes = [&](uint32_t i, float* lo, float* hi) {
+        lo[0] = nd[i].bounds.pmin.x, lo[1] = nd[i].bounds.pmin.y, lo[2] = nd[i].bounds.pmin.z;
+        hi[0] = nd[i].bounds.pmax.x, hi[1] = nd[i].bounds.pmax.y, hi[2] = nd[i].bounds.pmax.z;
+    };
+    for (uint32_t i = 0; i < n; ++i) {
+        float lo[3], hi[3];
+        planes(i, lo, hi);
+        for (int ax = 0; ax < 3; ++ax)
+            if (!std::isfinite(lo[ax]) || !std::isfinite(hi[ax])) return false;
+        if (nd[i].nPrimitives > 0) continue;
+        for (uint32_t c : {i + 1, nd[i].offset}) {
+            float clo[3], chi[3];
+            planes(c, clo, chi);
+            for (int ax = 0; ax < 3; ++ax)
+                if (!(clo[ax] >= lo[ax]) || !(chi[ax] <= hi[ax])) return false;
+        }
+    }
+    return true;
+}
+
+namespace {
+
+// a triangle test against a node visit, in VALU instructions of the shipped fused LDS-walk kernel: 52 for
+// the test (profiles/r06/tuning_sweep.txt), 19 for the visit (profiles/HISTORY.md, round 13)
+constexpr double kGateTriCost = 52.0 / 19.0;
+// the longest run of removed nodes between a node and its gate that the programme weighs; a longer run
+// (of equal-box nodes, which are removed whatever it says) is weighed as one of this length
+constexpr uint32_t kGateMaxRun = 8;
+
+double box_area(const rt_cl_bvh_node& x) {
+    const double d[3] = {(double)x.bounds.pmax.x - x.bounds.pmin.x, (double)x.bounds.pmax.y - x.bounds.pmin.y,
+                         (double)x.bounds.pmax.z - x.bounds.pmin.z};
+    return 2.0 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
+}
+
+// the share of the rays through g's box that go through i's (i nests in g): the surface-area ratio
+double pass_share(const std::vector<double>& area, uint32_t i, uint32_t g) {
+    return area[g] > 0.0 ? std::min(1.0, std::max(0.0, area[i] / area[g])) : 1.0;
+}
+
+// the six bound words are equal as uint32_t (the collapse's comparison: +0.0 and -0.0 differ)
+bool same_bounds(const rt_cl_bvh_node& a, const rt_cl_bvh_node& b) {
+    const float* x[6] = {&a.bounds.pmin.x, &a.bounds.pmin.y, &a.bounds.pmin.z, &a.bounds.pmax.x, &a.bounds.pmax.y, &a.bounds.pmax.z};
+    const float* y[6] = {&b.bounds.pmin.x, &b.bounds.pmin.y, &b.bounds.pmin.z, &b.bounds.pmax.x, &b.bounds.pmax.y, &b.bounds.pmax.z};
+    for (int k = 0; k < 6; ++k)
+        if (std::memcmp(x[k], y[k], 4) != 0) return false;
+    return true;
+}
+
+}  // namespace
+
+// The interior nodes the gate-skipped set removes (removed[i] = 1), for a tree that holds boxes_nest; one
+// set for the eight octants.  The root is kept: the ring fill's root test and its sky decision read the
+// root's record.  Leaves are kept: their box test is part of the result (a leaf entered is a leaf whose
+// triangles are tested), and the kernels take a leaf's continuation from the visited record.  An interior
+// node whose box is bitwise its parent's is removed whatever the cost says -- its test is the collapse's,
+// known to pass -- so the set contains the collapsed one.  The rest is a choice of cost alone, since the
+// lemma of gate_skip_oct_links allows any of them:
+//   RT_GATE_SELECT 0, the SAH programme.  With p = area(node) / area(nearest kept ancestor g), the share of
+//   g's passing rays that reach into the node's box, the expected cost of a subtree under gate g is
+//     kept interior      1 + p * (cost of the two children under the node)
+//     removed interior   the cost of the two children under g
+//     leaf               1 + p * count * kGateTriCost
+//   and a node is removed where that is strictly cheaper.  Children have larger indices than their parent:
+//   one backward sweep fills cost[node][distance to the gate], a forward sweep reads the choices off.
+//   RT_GATE_SELECT 1, the plain ratio: a node is removed when p >= RT_GATE_RATIO_PCT / 100.
+void select_gate_skips(const rt_cl_bvh_node* nd, uint32_t n, std::vector<uint8_t>& removed) {
+    removed.assign(n, 0);
+    if (n == 0) return;
+    std::vector<uint32_t> parent(n, 0xffffffffu), depth(n, 0);
+    std::vector<double> area(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        area[i] = box_area(nd[i]);
+        if (nd[i].nPrimitives > 0) continue;
+        for (uint32_t c : {i + 1, nd[i].offset}) parent[c] = i, depth[c] = depth[i] + 1;
+    }
+    auto forced = [&](uint32_t i) { return i > 0 && nd[i].nPrimitives == 0 && same_bounds(nd[i], nd[parent[i]]); };
+    auto ancestor = [&](uint32_t i, uint32_t k) {
+        while (k-- > 0) i = parent[i];
+        return i;
+    };
+    const uint32_t K = kGateMaxRun + 1;  // gate distances 1..K
+    if (RT_GATE_SELECT == 1) {
+        std::vector<uint32_t> gate(n, 0);  // the nearest kept ancestor
+        for (uint32_t i = 1; i < n; ++i) {
+            gate[i] = removed[parent[i]] ? gate[parent[i]] : parent[i];
+            if (nd[i].nPrimitives == 0)
+                removed[i] = forced(i) || pass_share(area, i, gate[i]) * 100.0 >= (double)RT_GATE_RATIO_PCT;
+        }
+        return;
+    }
+    std::vector<double> cost((size_t)n * (K + 1), 0.0);
+    std::vector<uint8_t> skip((size_t)n * (K + 1), 0);
+    for (uint32_t i = n; i-- > 0;) {
+        for (uint32_t k = 1; k <= std::min(K, depth[i]); ++k) {
+            const double p = pass_share(area, i, ancestor(i, k));
+            double& c = cost[(size_t)i * (K + 1) + k];
+            if (nd[i].nPrimitives > 0) {
+                c = 1.0 + p * (double)nd[i].nPrimitives * kGateTriCost;
+                continue;
+            }
+            const uint32_t a = i + 1, b = nd[i].offset, kk = std::min(k + 1, K);
+            const double kept = 1.0 + p * (cost[(size_t)a * (K + 1) + 1] + cost[(size_t)b * (K + 1) + 1]);
+            const double gone = cost[(size_t)a * (K + 1) + kk] + cost[(size_t)b * (K + 1) + kk];
+            const bool s = forced(i) || (k < K && gone < kept);
+            skip[(size_t)i * (K + 1) + k] = s;
+            c = s ? gone : kept;
+        }
+    }
+    std::vector<uint32_t> dist(n, 1);  // distance to the nearest kept ancestor, as the programme weighed it
+    for (uint32_t i = 1; i < n; ++i) {
+        const uint32_t q = parent[i];
+        dist[i] = removed[q] ? std::min(dist[q] + 1, K) : 1;
+        removed[i] = skip[(size_t)i * (K + 1) + dist[i]];
+    }
+}
+
+// The gate-skipped link set: a copy of the plain records `oct` (n nodes, every leaf inline) in which, per
+// octant o, every hit_next and miss_next word that targets a removed interior node c (select_gate_skips)
+// is replaced by c's near child under o -- c's plain hit_next -- repeated while the target is removed;
+// returns the number of words it changes.  (Children have larger indices: the chain is finite and ends at
+// a kept node, which may be a leaf.)  The tree must hold boxes_nest.
+//
+// Why a walk over these links computes what the plain walk computes.  The lemma: for a ray of octant o and
+// a node c with a descendant x, if x's box test passes at some t' <= t then c's passes at t.  The node step
+// (oct_step, oct_step_w and oct_step_g of rt_kernels_body.hpp are one arithmetic, and the three math
+// policies differ only in the reciprocal `inv` they formed once per ray) computes per axis a near term
+// fl(fl(near - o_k) * inv_k) and a far term fl(fl(far - o_k) * inv_k) on the planes the record holds for o,
+// t0 = max(0, near terms), t1 = min(t, far terms), and passes when t1 >= t0.
+//   * Under o, the near plane is pmin where inv_k >= 0 and pmax where inv_k < 0 (the octant bit is
+//     `inv_k < 0`, so d_k = -0 with inv_k = -inf counts as negative and d_k = +0 as positive).  Nesting moves
+//     x's near plane along the ray against c's and x's far plane against it: fl(b - o_k) is monotone in b,
+//     and fl(y * inv_k) is monotone in y with the direction inv_k's sign gives, so x's near term >= c's and
+//     x's far term <= c's, whatever inv_k's value -- an exact quotient, a hardware reciprocal an ulp off, or
+//     an infinity.  min(t, .) is monotone in t.  Hence t0(c) <= t0(x) <= t1(x) <= t1(c).
+//   * NaN.  __builtin_fmaxf / fminf return the other operand when one is NaN, so a NaN term constrains
+//     nothing, and `t1 >= t0` is false on a NaN.  t0 is never NaN (it starts from 0).  With finite planes a
+//     term is NaN when inv_k is NaN (then it is for c and x alike) or as 0 * inf: plane == o_k on an axis
+//     with d_k = +-0.  If x's term is NaN and c's is not, c's plane lies on the side nesting allows: its
+//     near term is -inf and its far term +inf, which constrain nothing either.  If c's term is NaN and
+//     x's is not, c is the less strict of the two.  A NaN t with every far term NaN fails x and c alike; x
+//     passing needs a far term that is a number, and c's term on that axis is no smaller (a NaN there would
+//     put x's far plane behind the origin: far term -inf, and x fails).
+//   * +0 and -0 planes: fl(b - o_k) differs for them only in the sign of a zero, which max, min and >= do not
+//     see and which gives NaN for both against an infinite inv_k.  The certificate compares values.
+// Equivalently: c fails implies every node below c fails, at the same t.  Now take a word redirected from c
+// to c's near child a.  If c's test would have passed, the plain walk goes to a: the same position, one
+// visit less.  If it would have failed, the plain walk goes to c's miss_next with t untouched; the walk over
+// these links visits a, which fails, goes on to a's miss_next -- c's far child b, or b's near child where b
+// is removed -- and so on: every kept node below c is visited at most once, fails (kept leaves have their
+// own box test, and it fails), no triangle is tested, t does not change, and the last miss_next of the
+// subtree is the word c's own miss_next is in this set.  Either way the state after c's subtree is the plain
+// walk's.  By induction over the redirected words every leaf entered, every triangle tested and the final
+// {t, prim, u, v} are the plain walk's, in its order, for closest-hit and any-hit walks alike (they differ in
+// what a triangle step does, and t only shrinks, which the lemma allows).  Only the visits differ: one less
+// per passage of a passing removed node, up to the subtree's kept nodes more per passage of a failing one,
+// which is what select_gate_skips weighs.
+//   * The collapse is the case of a removed node with its parent's planes; every collapsed word is on the
+//     chain followed here, so a word of this set differs from the collapsed set's only where that one still
+//     targets a removed node.
+//   * Planes, leaf codes and END are the plain set's, word for word.  The root's record stays; so does every
+//     removed node's, which no link leads to.
+// Like the collapse, the certificate is a property of the planes as packed: after a device refit only the
+// plain set may be walked until the next full preparation (rti::DeviceScene).
+uint32_t gate_skip_oct_links(const std::vector<uint32_t>& oct, uint32_t n, const std::vector<uint8_t>& removed,
+                             std::vector<uint32_t>& out) {
+    const uint32_t stride = oct_stride(n), bofs = oct_b(n);
+    out = oct;
+    uint32_t changed = 0;
+    for (uint32_t o = 0; o < 8; ++o) {
+        const size_t plane = ((size_t)bofs + (size_t)o * stride) * 4;
+        const uint32_t* pb = &oct[plane];
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t k = 2; k < 4; ++k) {
+                uint32_t& w = out[plane + (size_t)i * 4 + k];
+                if (w >= n) continue;  // a leaf code, or END
+                uint32_t to = w;
+                while (removed[to]) to = pb[(size_t)to * 4 + 2];  // (a removed node is interior: a node index)
                 if (to != w) {
                     w = to;
                     ++changed;
@@ -412,16 +612,31 @@ int pack_scene_host(const SceneBytes& in, uint32_t top_limit, HostPack* out) {
             build_oct_nodes_grouped(p.oct_nodes_collapsed, nn, RT_GOCT_GROUP, p.goct_nodes_collapsed, &b);
         }
     }
+    // the gate-skipped link set of both layouts, for trees that hold its certificate; kept only where it
+    // differs from the collapsed one
+    if (RT_GATE_SKIP && RT_NODE_COLLAPSE && p.oct_ok && (p.nested = boxes_nest(nd, nn))) {
+        select_gate_skips(nd, nn, p.gate_removed);
+        p.gate_links = gate_skip_oct_links(p.oct_nodes, nn, p.gate_removed, p.oct_nodes_gated);
+        if (p.oct_nodes_gated == (p.collapsed_links ? p.oct_nodes_collapsed : p.oct_nodes)) {
+            p.oct_nodes_gated.clear();
+        } else if (!p.goct_nodes.empty()) {
+            uint32_t b = 0;
+            build_oct_nodes_grouped(p.oct_nodes_gated, nn, RT_GOCT_GROUP, p.goct_nodes_gated, &b);
+        }
+    }
     return RT_SUCCESS;
 }
 
 // The pruned set of both layouts over the collapsed one (the plain one where there is none), kept only
-// where it differs from it.
+// where it differs from it; and, for a scene with a gate-skipped set, the pruned set over that one.
 void pack_pruned_links(const uint8_t* tri_octants, HostPack* pack) {
     HostPack& p = *pack;
     p.pruned_links = 0;
     p.oct_nodes_pruned.clear();
     p.goct_nodes_pruned.clear();
+    p.gated_pruned_links = 0;
+    p.oct_nodes_gated_pruned.clear();
+    p.goct_nodes_gated_pruned.clear();
     if (!RT_OCTANT_CULL || !p.oct_ok || !tri_octants) return;
     const std::vector<uint32_t>& base = p.collapsed_links ? p.oct_nodes_collapsed : p.oct_nodes;
     p.pruned_links = prune_oct_links(p.oct_nodes, base, p.n_nodes, tri_octants, p.oct_nodes_pruned);
@@ -430,6 +645,15 @@ void pack_pruned_links(const uint8_t* tri_octants, HostPack* pack) {
     } else if (!p.goct_nodes.empty()) {
         uint32_t b = 0;
         build_oct_nodes_grouped(p.oct_nodes_pruned, p.n_nodes, RT_GOCT_GROUP, p.goct_nodes_pruned, &b);
+    }
+    // ... and the pruned set over the gate-skipped one, where the scene has that
+    if (p.oct_nodes_gated.empty()) return;
+    p.gated_pruned_links = prune_oct_links(p.oct_nodes, p.oct_nodes_gated, p.n_nodes, tri_octants, p.oct_nodes_gated_pruned);
+    if (p.gated_pruned_links == 0) {
+        p.oct_nodes_gated_pruned.clear();
+    } else if (!p.goct_nodes.empty()) {
+        uint32_t b = 0;
+        build_oct_nodes_grouped(p.oct_nodes_gated_pruned, p.n_nodes, RT_GOCT_GROUP, p.goct_nodes_gated_pruned, &b);
     }
 }
 

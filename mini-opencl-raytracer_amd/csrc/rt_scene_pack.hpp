@@ -33,6 +33,17 @@ inline uint32_t oct_records(uint32_t n) { return oct_b(n) + 8u * oct_stride(n); 
 #ifndef RT_OCTANT_CULL
 #define RT_OCTANT_CULL 1  // ... and the pruned links (prune_oct_links), which contain the collapse
 #endif
+#ifndef RT_GATE_SKIP
+#define RT_GATE_SKIP 1  // ... in the gate-skipped form of both (gate_skip_oct_links; needs RT_NODE_COLLAPSE)
+#endif
+// how select_gate_skips chooses the removed interior nodes: 0 the SAH programme, 1 the plain area ratio
+// (RT_GATE_RATIO_PCT / 100 and above), kept for comparison (profiles/r14/removed_visits.txt)
+#ifndef RT_GATE_SELECT
+#define RT_GATE_SELECT 0
+#endif
+#ifndef RT_GATE_RATIO_PCT
+#define RT_GATE_RATIO_PCT 90
+#endif
 #ifndef RT_GOCT_GROUP
 #define RT_GOCT_GROUP 1  // node-major: bunny proxy fused 1.405 -> 1.393 ms/frame (profiles/r03/goct_layout_ab.txt)
 #endif
@@ -49,6 +60,10 @@ void build_oct_nodes_grouped(const std::vector<uint32_t>& oct, uint32_t n, uint3
 uint32_t collapse_oct_links(const std::vector<uint32_t>& oct, uint32_t n, std::vector<uint32_t>& out);
 uint32_t prune_oct_links(const std::vector<uint32_t>& oct, const std::vector<uint32_t>& base, uint32_t n,
                          const uint8_t* tri_octants, std::vector<uint32_t>& out);
+bool boxes_nest(const rt_cl_bvh_node* nd, uint32_t n);
+void select_gate_skips(const rt_cl_bvh_node* nd, uint32_t n, std::vector<uint8_t>& removed);
+uint32_t gate_skip_oct_links(const std::vector<uint32_t>& oct, uint32_t n, const std::vector<uint8_t>& removed,
+                             std::vector<uint32_t>& out);
 void build_global_nodes(const rt_cl_bvh_node* nd, uint32_t n, const std::vector<uint32_t>& skips,
                         uint32_t top, std::vector<uint32_t>& out, uint32_t* n_top,
                         std::vector<uint32_t>* slot_of = nullptr);
@@ -83,6 +98,19 @@ struct HostPack {
     // -- the collapsed records then serve
     uint32_t pruned_links = 0;
     std::vector<uint32_t> oct_nodes_pruned, goct_nodes_pruned;
+    // The gate-skipped link set (gate_skip_oct_links), which contains the collapse.  nested: the tree holds
+    // the certificate (boxes_nest); gate_removed: the interior nodes no link of the set leads to, one byte per
+    // node (empty without the certificate); gate_links: the link words the set changes against the plain
+    // one.  The records are empty where the certificate is refused and where the set is word for word the
+    // collapsed one -- the collapsed records (or the plain ones) then serve.  Where they exist a launch walks
+    // them in place of the collapsed set, and their own pruned form (pack_pruned_links: prune_oct_links over
+    // them; gated_pruned_links words against them, records empty when 0) in place of the pruned one.
+    bool nested = false;
+    std::vector<uint8_t> gate_removed;
+    uint32_t gate_links = 0;
+    std::vector<uint32_t> oct_nodes_gated, goct_nodes_gated;
+    uint32_t gated_pruned_links = 0;
+    std::vector<uint32_t> oct_nodes_gated_pruned, goct_nodes_gated_pruned;
 };
 
 // Validate the scene and pack every record (top_limit: build_global_nodes' `top`).  On an error
@@ -90,7 +118,8 @@ struct HostPack {
 int pack_scene_host(const SceneBytes& in, uint32_t top_limit, HostPack* out);
 // The third record set of a scene pack_scene_host accepted: tri_octants[t] (n_tris bytes) holds for
 // triangle t the octants whose every ray fails its test (rt_octant_cull.hpp: the caller evaluates the
-// certificate, this file stays free of it).  Nothing in a build with RT_OCTANT_CULL=0.
+// certificate, this file stays free of it), and its twin over the gate-skipped set where the scene has one.
+// Nothing in a build with RT_OCTANT_CULL=0.
 void pack_pruned_links(const uint8_t* tri_octants, HostPack* pack);
 
 }  // namespace rtp

@@ -55,6 +55,10 @@ for name in scheds:
         nc = r.k.node_collapse()
         print(f"  node collapse: {nc['collapsed_links']} link words, scene collapsible: {nc['scene_collapsible']}, "
               f"this launch walked the collapsed links: {nc['launch_collapsed']}")
+        # the gate skip (rtKernelGetGateSkip): where the scene has that set, "the collapsed links" are its
+        gs = r.k.gate_skip()
+        print(f"  gate skip: {gs['gate_links']} link words, scene nested: {gs['scene_nested']}, "
+              f"this launch walked the gate-skipped links: {gs['launch_gate_skipped']}")
         # the octant cull (rtKernelGetOctantCull): likewise, except in a -DRT_OCTANT_CULL_STATS=1 build, whose
         # visits and tests against the default build's are the ones the pruned links remove
         oc = r.k.octant_cull()
